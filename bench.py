@@ -4,6 +4,14 @@ metric), device-resident RGB8 in HBM -> complete .jxl bytes in host memory.
 
   python bench.py --gpus N --steps K --warmup W [--mode shard|replica]
                   [--scaling strong|weak] [--coder prefix|ans] [--config C]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline JSON
+line (metric, value, ms_per_step and the figures the timed steps themselves
+yield: latency, bytes per frame, per-stage and host times, host CPU).
+--dump-outputs DIR also writes the codestream of the last timed step to DIR
+(dump_outputs below).  --full adds every side measurement listed under "With
+--full" below; each takes runs of its own, after the timed steps.
 
 One step = one full encode (front end + merge stage, token statistics, entropy
 codes, bit emission, assembly, D2H of the codestream).  The encode is the one
@@ -50,7 +58,8 @@ Timing: barrier + synchronize on both sides of the K steps, max over ranks.
 thread, context and HIP stream each; the K frames split between them) through
 the one-at-a-time entry point instead (--no-pipeline: S = 1 of those).
 
-The JSON line also carries:
+With --full the JSON line also carries (the --alt-* / --no-* options pick
+among them; a plain run makes none of these measurements):
   roofline     -- the fused front kernel (XYB + homogeneity + AQ + 8x8 ACS +
                   DCT + quant): SURVEY.md §8(d)'s algorithmic bytes (15.078
                   B/px) per launch / its HIP-event duration (its own events, on
@@ -415,6 +424,29 @@ def single_image_probe(img, distance, effort, headline_bytes, device, runs=3):
     return out
 
 
+DUMP_MAX_VALUES = 12 << 20  # float32 values per dumped array (48 MiB)
+
+
+def dump_outputs(path, codestream):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step -- that frame's codestream -- as float32 arrays (a byte value is exact
+    in float32), so that two builds can be compared output for output:
+      codestream.npy        the bytes, in order; of a codestream longer than
+                            DUMP_MAX_VALUES, the bytes at DUMP_MAX_VALUES
+                            positions drawn once with a fixed seed (sorted)
+      codestream_bytes.npy  its length in bytes (float64, one value)
+    The frames are synthetic and seeded and the encode is deterministic: the
+    same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    data = np.frombuffer(codestream, dtype=np.uint8)
+    if data.size > DUMP_MAX_VALUES:
+        pick = np.random.default_rng(0x4A58).choice(data.size, DUMP_MAX_VALUES, replace=False)
+        data = data[np.sort(pick)]
+    np.save(os.path.join(path, "codestream.npy"), data.astype(np.float32))
+    np.save(os.path.join(path, "codestream_bytes.npy"),
+            np.array([len(codestream)], dtype=np.float64))
+
+
 def spawn_ranks(n, argv):
     """Run this script as n ranks under torch.distributed.run (one node,
     rendezvous on 127.0.0.1) in a child process; returns its exit status."""
@@ -439,6 +471,14 @@ def main():
     # (1.1 s of timed encodes at 8K)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also make the side measurements (other coder, "
+                         "preset and proposals, isolated-kernel rooflines, replicas, decoded "
+                         "quality, one-image-at-a-time costs, CPU baseline); the --alt-* and "
+                         "--no-* options choose among them.  Off: only the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the codestream of the last timed step to DIR/codestream.npy "
+                         "(+ codestream_bytes.npy), see dump_outputs")
     ap.add_argument("--config", type=int, default=2, help="BASELINE config index (2 = 8K)")
     ap.add_argument("--distance", type=float, default=1.0)
     ap.add_argument("--effort", type=int, default=7)
@@ -495,6 +535,10 @@ def main():
     ap.add_argument("--no-single", action="store_true",
                     help="skip the untimed one-image-at-a-time probe (single_image)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the timed steps and nothing beside them
+        args.alt_coder = args.alt_replica = args.alt_thesis = args.alt_preset = args.alt_e4 = 0
+        args.no_cpu_baseline = args.no_quality = args.no_single = True
 
     # one process per GPU: with WORLD_SIZE unset, --gpus N > 1 starts the N
     # ranks itself (before this process touches the GPU); a launcher's
@@ -542,7 +586,7 @@ def main():
         return per_step, out
 
     img = None
-    if world == 1:  # quality probe / CPU baseline: the first frame
+    if world == 1 and args.full:  # quality probe / CPU baseline: the first frame
         img = synth_rgb8_device(w, h, SEED_BASE + args.config, local).cpu().numpy()
     torch.cuda.synchronize()
 
@@ -562,9 +606,11 @@ def main():
         encs = [jxg.Encoder(distance=args.distance, effort=args.effort if effort is None else effort,
                             proposals=props, device=local, flags=flags)
                 for _ in range(nstreams)]
-        rec = {"front_ms": [], "host_ms": [], "aq_ms": [], "sizes": [], "last": None}
+        rec = {"front_ms": [], "host_ms": [], "aq_ms": [], "sizes": [], "last": None,
+               "final": None}
+        final_step = [None]  # index of the last timed step, once the timed region starts
 
-        def took(e, k, out):
+        def took(e, k, out, final=False):
             t = e.timings()
             rec["front_ms"].append(t[0])
             rec["host_ms"].append(t[1:4])
@@ -573,6 +619,11 @@ def main():
             if k % nd == 0:
                 # shared-memory views (ShardStream) are recycled: keep a copy
                 rec["last"] = out.tobytes() if isinstance(out, np.ndarray) else out
+            if final:
+                # the last timed step's output (--dump-outputs), kept without a
+                # copy: nothing is received after it, so a view stays valid
+                # until it is copied outside the timed region
+                rec["final"] = out
 
         ss = None
         host = None
@@ -591,6 +642,9 @@ def main():
         def worker(e, ks):
             # the codestream ends in (pinned / shared) host memory; ctypes
             # calls release the GIL, so several encoders' host work overlaps
+            # (fin: where in ks the last timed step is, the streaming loops
+            # receive in submission order)
+            fin = len(ks) - 1 if len(ks) and ks[-1] == final_step[0] else -1
             if ss is not None:
                 # (a received view stays valid until the next receive: took()
                 # keeps only its size, and copies the bytes of the frames it
@@ -599,16 +653,16 @@ def main():
                 for k in ks:
                     ss.submit(d_imgs[k % nd].data_ptr())
                     while ss.pending() >= ss.max_pending or (ss.pending() and ss.ready()):
-                        took(e, got, ss.receive())
+                        took(e, got, ss.receive(), got == fin)
                         got += 1
                 while ss.pending():
-                    took(e, got, ss.receive())
+                    took(e, got, ss.receive(), got == fin)
                     got += 1
             elif mode == "shard-sync":
                 from jxg.dist import encode_sharded
                 for k in ks:
                     took(e, k, encode_sharded(e, d_imgs[k % nd], w, fh, rank, world, bufs=bufs,
-                                              copy=False, host=host))
+                                              copy=False, host=host), k == final_step[0])
             elif pipe:
                 # streaming entry points: submit every frame, receive each
                 # codestream as soon as it is done (more than the library's
@@ -618,14 +672,15 @@ def main():
                 for k in ks:
                     e.submit_device(d_imgs[k % nd].data_ptr(), w, h)
                     while e.pending() > hold:
-                        took(e, got, e.receive(copy=False))
+                        took(e, got, e.receive(copy=False), got == fin)
                         got += 1
                 while e.pending():
-                    took(e, got, e.receive(copy=False))
+                    took(e, got, e.receive(copy=False), got == fin)
                     got += 1
             else:
                 for k in ks:
-                    took(e, k, e.encode_device(d_imgs[k % nd].data_ptr(), w, h, copy=False))
+                    took(e, k, e.encode_device(d_imgs[k % nd].data_ptr(), w, h, copy=False),
+                         k == final_step[0])
 
         for e in encs:  # contexts warmed one after another
             # at least 16 frames when streaming: every lane of the library's
@@ -644,6 +699,7 @@ def main():
             ss.wait_s = 0.0
 
         total = args.steps * per_step
+        final_step[0] = total - 1
         share = [list(range(i, total, nstreams)) for i in range(nstreams)]
         if world > 1:
             dist.barrier()
@@ -686,6 +742,8 @@ def main():
         rec["st"] = encs[0].stats()
         last = rec["last"]
         rec["last"] = last.tobytes() if hasattr(last, "tobytes") else last
+        final = rec["final"] if args.dump_outputs else None
+        rec["final"] = final.tobytes() if hasattr(final, "tobytes") else final
         if ss is not None:
             ss.close()
         for e in encs[1:]:
@@ -704,6 +762,11 @@ def main():
     pipeline = mode == "frames" and not args.no_pipeline
     nstreams = 1 if mode != "frames" else max(1, args.streams)
     R = run(mode, args.coder, nstreams, pipe=pipeline)
+    if args.dump_outputs and rank == 0:
+        # (sharded: rank 0 holds the assembled frame; replicas: rank 0's own)
+        if R["final"] is None:
+            sys.exit("bench.py: --dump-outputs: the last timed step returned no codestream")
+        dump_outputs(args.dump_outputs, R["final"])
     dt, front_ms, host_ms, st = R["dt"], R["front_ms"], R["host_ms"], R["st"]
     per_step = R["per_step"]
     nbytes = R["sizes"][-1] if R["sizes"] else 0
@@ -733,7 +796,7 @@ def main():
         P["enc"].close()
     iso = None
     streamed = mode == "shard"
-    if mode == "frames" and pipeline or streamed:
+    if args.full and (mode == "frames" and pipeline or streamed):
         # the kernels alone on the GPU (one-at-a-time encodes of this rank's
         # frame, same coder): the front kernel's roofline, the rANS chain
         # kernel's duration
@@ -878,6 +941,10 @@ def main():
                                             (iso["st"] if iso else st)["ms_front_kernel"], 4),
                             "valu_issue_frac_pmc": load_merge_pmc(pmc_key)},
         }
+        if not args.full:
+            # kernel figures belong to --full (measured with the kernel alone on
+            # the GPU where the mode allows it): a plain line has one meaning
+            del res["roofline"], res["merge_stage"]
         if iso is not None and args.coder == "ans":
             # the rANS chain: one serial state recurrence per pass group (the
             # format's), so its kernel time is set by the group with the most

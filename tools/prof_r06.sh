@@ -15,6 +15,6 @@ for s in $STEPS; do
     front) EXTRA=1 bash profiles/pmc_front.sh $O/pmc_front ;;
     e4) EXTRA=1 BENCH_ARGS="$B --effort 4" bash profiles/pmc_front.sh $O/pmc_e4 ;;
     merge) KERNEL=merge_eval_kernel bash profiles/pmc_front.sh $O/pmc_merge ;;
-    trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/$O/prof -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-quality --no-single > $O/bench_prof.log 2>&1 ;;
+    trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/$O/prof -o run -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-quality --no-single > $O/bench_prof.log 2>&1 ;;
   esac
 done
