@@ -24,8 +24,8 @@
  * waited on by the library's stream -- no host synchronisation).
  *
  * A context with streamed frames pending (jxg_pending > 0) serves them as a
- * pipeline lane: the one-at-a-time, batch, sharded-begin/end, homogeneity
- * and compare entry points return JXG_ERR_INVALID_ARG until they are
+ * pipeline lane: the one-at-a-time, batch, sharded-begin/end, homogeneity,
+ * compare and reconstruct entry points return JXG_ERR_INVALID_ARG until they are
  * received.
  */
 #ifndef JXG_H_
@@ -333,6 +333,27 @@ jxg_status jxg_compare_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_strid
 jxg_status jxg_compare_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
                                    const void* d_comp, size_t comp_stride, uint32_t xsize,
                                    uint32_t ysize, int want_ssim, jxg_quality* out);
+
+/* ---- decode-side reconstruction: decoded pixels without a decoder ----
+ * The decoded image of the frame this context encoded last with
+ * jxg_encode_rgb8 / jxg_encode_rgb8_device: what a conforming decoder
+ * reconstructs from that codestream (dequantization, inverse transforms,
+ * chroma from luma, Gaborish / EPF as signalled, XYB -> sRGB8), computed from
+ * the context's device-resident coefficients -- no bitstream parse, no
+ * JXG_FLAG_KEEP_MAPS needed, and no buffer the encoder reads is modified (a
+ * later encode gives the same bytes).  rgb / d_rgb: xsize x ysize RGB8
+ * interleaved, row_stride >= 3 * xsize bytes per row, of which only the first
+ * 3 * xsize are written.  Both calls return when the image is complete.  The
+ * float planes they need are allocated by the first call and released by
+ * jxg_destroy.  Arithmetic is f32: against a double-precision decoder a
+ * sample may differ by 1 where a value sits on a rounding boundary.
+ * JXG_ERR_INVALID_ARG: null arguments, a stride too small, no frame encoded
+ * yet, streamed frames pending, or the context's last encode was not a
+ * one-at-a-time encode -- reconstruction of batch, streamed and sharded
+ * frames (and of jxg_warmup's synthetic frame) is out of scope: their
+ * coefficients live in pipeline lanes or on other ranks. */
+jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride);
+jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_stride);
 
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result

@@ -187,7 +187,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr,
                  "usage: %s INPUT OUTPUT [--distance=D] [--effort=E] "
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
-                 "[--epf=-1|0] [--aq=masking|activity] [--device=N]\n"
+                 "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH]\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
                  argv[0]);
     return 1;
@@ -196,6 +196,9 @@ int main(int argc, char** argv) {
   // argv, docker_manager.rs:126-136) gets cjxl's VarDCT defaults [ext]: ANS,
   // Gaborish on, EPF iterations by distance, the masking quant field
   jxg_params p{1.0f, 7, 0, 1, JXG_FLAGS_CJXL_DEFAULTS, 0};
+  // --jxg_recon=PATH (not a cjxl option): also write the decoded image of the
+  // codestream, reconstructed on the GPU (jxg_reconstruct_rgb8), as a binary PPM
+  const char* recon_path = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -235,6 +238,8 @@ int main(int argc, char** argv) {
       }
     } else if (!std::strncmp(a, "--device=", 9))
       p.device = std::atoi(a + 9);
+    else if (!std::strncmp(a, "--jxg_recon=", 12))
+      recon_path = a + 12;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -328,6 +333,22 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::fclose(f);
+  if (recon_path) {
+    std::vector<uint8_t> rec((size_t)w * h * 3);
+    st = jxg_reconstruct_rgb8(ctx, rec.data(), (size_t)w * 3);
+    if (st != JXG_OK) {
+      std::fprintf(stderr, "reconstruct failed: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    FILE* r = std::fopen(recon_path, "wb");
+    const bool wr = r && std::fprintf(r, "P6\n%u %u\n255\n", w, h) > 0 &&
+                    std::fwrite(rec.data(), 1, rec.size(), r) == rec.size();
+    if (r) std::fclose(r);
+    if (!wr) {
+      std::fprintf(stderr, "cannot write %s\n", recon_path);
+      return fail(1);
+    }
+  }
   const auto t_write = Clk::now();
   std::printf("Encoding [VarDCT, d%.3f, effort: %d], %u x %u, %zu bytes, %.3f bpp, %.2f MP/s\n",
               p.distance, p.effort, w, h, out.size, out.size * 8.0 / ((double)w * h),

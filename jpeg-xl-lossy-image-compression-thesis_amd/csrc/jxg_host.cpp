@@ -315,6 +315,18 @@ struct Ctx {
   DevBuf<uint64_t> q_sse;
   DevBuf<double> q_part, q_ssim;
   bool gauss_ready = false;
+  // decode-side reconstruction (jxg_reconstruct_rgb8), allocated by its first
+  // call: tables, two sets of three block-padded f32 planes, the list of
+  // 128 / 256 px varblocks, the host variant's device image
+  DevBuf<float> rc_tab, rc_pa, rc_pb;
+  DevBuf<uint16_t> rc_pos;
+  DevBuf<uint32_t> rc_big;
+  DevBuf<uint8_t> rc_rgb;
+  uint32_t rc_tab_g = 0;  // global scale the EPF sigma table was built for
+  // the last encode was jxg_encode_rgb8[_device] of a recon_w x recon_h frame,
+  // whose coefficients and maps are still in this context's buffers
+  bool recon_ok = false;
+  uint32_t recon_w = 0, recon_h = 0;
   DevBuf<ConcatPiece> pieces, pieces_ac;
   DevBuf<uint8_t> cat;  // stage_concat: [pieces | chunk words], one upload
   PinBuf<uint8_t> h_cat;
@@ -2264,6 +2276,7 @@ static Ctx* pipe_lane(Ctx* c, uint32_t li) { return li == 0 ? c : c->lanes[li - 
 static jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w,
                               uint32_t h, size_t stride, uint32_t rank = 0, uint32_t world = 1,
                               bool shard = false) {
+  c->recon_ok = false;  // the lanes' frames overwrite this context's buffers
   if (!c->pipe) c->pipe.reset(new (std::nothrow) Pipe());
   if (!c->pipe) return JXG_ERR_OOM;
   Pipe& p = *c->pipe;
@@ -2415,6 +2428,7 @@ static jxg_status shard_begin(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t
                               size_t stride, uint32_t rank, uint32_t world, uint32_t* d_hist,
                               uint8_t* d_xbuf) {
   hipStream_t s = c->stream;
+  c->recon_ok = false;
   c->job = std::make_unique<Job>();
   Job& J = *c->job;
   J.f = make_frame(w, h, c->params.distance);
@@ -2803,9 +2817,16 @@ jxg_status jxg_encode_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, u
   out->size = 0;
   if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
-  const jxg_status st = order_input(c, c);
+  c->recon_ok = false;
+  jxg_status st = order_input(c, c);
   if (st) return st;
-  return encode_device(c, static_cast<const uint8_t*>(d_rgb), w, h, stride, out, t0);
+  st = encode_device(c, static_cast<const uint8_t*>(d_rgb), w, h, stride, out, t0);
+  if (!st) {
+    c->recon_ok = true;
+    c->recon_w = w;
+    c->recon_h = h;
+  }
+  return st;
 }
 
 jxg_status jxg_encode_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride,
@@ -2817,13 +2838,20 @@ jxg_status jxg_encode_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;  // c->rgb may be an in-flight lane's input
+  c->recon_ok = false;
   const size_t bytes = stride * (h - 1) + (size_t)w * 3;
   if (c->rgb.ensure(bytes) != hipSuccess) return JXG_ERR_OOM;
   if (hipMemcpyAsync(c->rgb.p, rgb, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return JXG_ERR_HIP;
   out->data = nullptr;
   out->size = 0;
-  return encode_device(c, c->rgb.p, w, h, stride, out, t0);
+  const jxg_status st = encode_device(c, c->rgb.p, w, h, stride, out, t0);
+  if (!st) {
+    c->recon_ok = true;
+    c->recon_w = w;
+    c->recon_h = h;
+  }
+  return st;
 }
 
 // Batched encode (BASELINE config 3: 64 x 1080p) through the streaming
@@ -3272,6 +3300,134 @@ jxg_status jxg_compare_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_strid
   return compare_device(c, c->q_orig.p, row, c->q_comp.p, row, xsize, ysize, want_ssim, out);
 }
 
+// ---- decode-side reconstruction (jxg_recon.hip) ----
+// The decoded image of the last one-at-a-time encode, from the context's
+// coefficient and map buffers (read only): tile transform kernel (+ the
+// 128 / 256 px varblocks at effort >= 8), Gaborish and EPF passes as the frame
+// header signals them; the last kernel of the chain writes RGB8.
+static jxg_status reconstruct_device(Ctx* c, uint8_t* d_rgb, size_t stride) {
+  hipStream_t s = c->stream;
+  const jxg_params& P = c->params;
+  const Frame f = make_frame(c->recon_w, c->recon_h, P.distance);
+  if (!c->rc_tab.p || c->rc_tab_g != f.G) {
+    const ReconTables T = build_recon_tables(f.G);
+    JXG_HIP(c->rc_tab.ensure(T.tab.size()));
+    JXG_HIP(c->rc_pos.ensure(T.pos.size()));
+    JXG_HIP(hipMemcpyAsync(c->rc_tab.p, T.tab.data(), T.tab.size() * 4, hipMemcpyHostToDevice, s));
+    JXG_HIP(hipMemcpyAsync(c->rc_pos.p, T.pos.data(), T.pos.size() * 2, hipMemcpyHostToDevice, s));
+    JXG_HIP(hipStreamSynchronize(s));
+    c->rc_tab_g = f.G;
+  }
+  const size_t plane = (size_t)f.xp * f.yp;
+  const uint32_t ntiles = f.tiles_x * f.tiles_y;
+  const uint32_t lf = lf_code(P.flags, P.distance);
+  const bool gab = lf & 1u;
+  const uint32_t epf = (lf >> 1) & 3u;
+  const bool big = P.effort >= 8;  // varblocks of 128 / 256 px are possible
+  int passes[4], np = 0;           // -1: Gaborish, else the EPF pass
+  if (gab) passes[np++] = -1;
+  if (epf >= 3) passes[np++] = 0;
+  if (epf >= 1) passes[np++] = 1;
+  if (epf >= 2) passes[np++] = 2;
+  const bool to_rgb = np == 0 && !big;
+  if (!to_rgb) JXG_HIP(c->rc_pa.ensure(3 * plane));
+  if (np || big) JXG_HIP(c->rc_pb.ensure(3 * plane));
+  const uint32_t bigcap = ntiles / 2 + 1;
+  JXG_HIP(c->rc_big.ensure(1 + (size_t)bigcap));
+  JXG_HIP(hipMemsetAsync(c->rc_big.p, 0, sizeof(uint32_t), s));
+  ReconArgs a{};
+  a.acs = c->acs.p;
+  a.qf = c->qf.p;
+  a.dc = c->dc.p;
+  a.ac = c->ac.p;
+  a.cmap = c->cmap.p;
+  a.w = f.w;
+  a.h = f.h;
+  a.bxs = f.bxs;
+  a.bys = f.bys;
+  a.xp = f.xp;
+  a.yp = f.yp;
+  a.tiles_x = f.tiles_x;
+  a.ntiles_all = ntiles;
+  a.inv_g = f.inv_g;
+  for (int i = 0; i < 3; i++) a.dc_step[i] = f.dc_step[i];
+  a.bias[0] = (float)(1.0 - 0.05465007330715401);
+  a.bias[1] = (float)(1.0 - 0.07005449891748593);
+  a.bias[2] = (float)(1.0 - 0.049935103337343655);
+  a.bias[3] = 0.145f;
+  a.tab = c->rc_tab.p;
+  a.pos = c->rc_pos.p;
+  a.pa = c->rc_pa.p;
+  a.pb = c->rc_pb.p;
+  a.biglist = c->rc_big.p;
+  a.bigcap = bigcap;
+  a.rgb = d_rgb;
+  a.stride = stride;
+  // XYB -> linear sRGB: the inverse of the opsin absorbance matrix (double)
+  {
+    const double bias = 0.0037930732552754493;
+    const double m[3][3] = {{0.30, 0.622, 0.078},
+                            {0.23, 0.692, 0.078},
+                            {0.24342268924547819, 0.20476744424496821, 0.55180986650955360}};
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) -
+                       m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+        a.cm[i * 3 + j] = (float)((m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0]) / det);
+      }
+    a.cbias = (float)std::cbrt(bias);
+    a.obias = (float)bias;
+  }
+  JXG_HIP(launch_recon_tiles(a, to_rgb, s));
+  if (big) {
+    uint32_t nbig = 0;
+    JXG_HIP(hipMemcpyAsync(&nbig, c->rc_big.p, sizeof(nbig), hipMemcpyDeviceToHost, s));
+    JXG_HIP(hipStreamSynchronize(s));
+    JXG_HIP(launch_recon_big(a, std::min(nbig, bigcap), s));
+  }
+  if (!to_rgb && np == 0) JXG_HIP(launch_recon_colour(a, a.pa, s));
+  float *src = a.pa, *dst = a.pb;
+  for (int i = 0; i < np; i++) {
+    const bool last = i + 1 == np;
+    if (passes[i] < 0)
+      JXG_HIP(launch_recon_gab(a, src, dst, last, s));
+    else
+      JXG_HIP(launch_recon_epf(a, passes[i], src, dst, last, s));
+    std::swap(src, dst);
+  }
+  JXG_HIP(hipStreamSynchronize(s));
+  return JXG_OK;
+}
+
+jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_stride) {
+  if (!ctx || !d_rgb) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
+  if (pipe_busy(c) || !c->recon_ok || row_stride < (size_t)c->recon_w * 3)
+    return JXG_ERR_INVALID_ARG;
+  const jxg_status st = order_input(c, c);  // the caller's earlier use of d_rgb
+  if (st) return st;
+  return reconstruct_device(c, static_cast<uint8_t*>(d_rgb), row_stride);
+}
+
+jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride) {
+  if (!ctx || !rgb) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
+  if (pipe_busy(c) || !c->recon_ok || row_stride < (size_t)c->recon_w * 3)
+    return JXG_ERR_INVALID_ARG;
+  const size_t row = (size_t)c->recon_w * 3;
+  JXG_HIP(c->rc_rgb.ensure(row * c->recon_h));
+  const jxg_status st = reconstruct_device(c, c->rc_rgb.p, row);
+  if (st) return st;
+  JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc_rgb.p, row, row, c->recon_h,
+                           hipMemcpyDeviceToHost, c->stream));
+  JXG_HIP(hipStreamSynchronize(c->stream));
+  return JXG_OK;
+}
+
 // one synthetic frame of the caller's size through the one-at-a-time path:
 // the context's buffers for that size are allocated and every kernel's code
 // object is loaded before the caller's first frame (jxg_cjxl runs it beside
@@ -3282,6 +3438,7 @@ jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->recon_ok = false;
   const size_t stride = (size_t)xsize * 3;
   if (c->rgb.ensure(stride * ysize) != hipSuccess) return JXG_ERR_OOM;  // jxg_encode_rgb8's upload buffer
   JXG_HIP(launch_synth(c->rgb.p, xsize, ysize, stride, 0x5741524Dull, c->stream));

@@ -320,6 +320,55 @@ struct MetricArgs {
 uint32_t ssim_partials(uint32_t w, uint32_t h);
 hipError_t set_gauss_table(const double* g, hipStream_t s);
 void launch_metrics(const MetricArgs& a, hipStream_t s);
+// decode-side reconstruction (jxg_recon.hip): the decoded
+// image from the context's quantized coefficients.  Table blob (floats, built
+// in double by build_recon_tables): inverse-DCT matrices [k][x] for n = 4 ..
+// 256, the LLF forward matrices (normalised DCT / LLF scale) for n = 1 .. 32,
+// the 8x8-class inverse weights in slice order [5 kinds][3][64], the merged
+// kinds' inverse weights in natural order [3][kRcKindOff[10]], the EPF's
+// qf -> inverse sigma table [256] (> 0: the block is not filtered).  Position
+// blob (u16): the zig-zag order of the 8x8 class [64], then every merged
+// kind's natural order [position] -> stored raster index.
+constexpr int kRcKindOff[11] = {0,    128,   384,   896,   1920,  3968,
+                                8064, 16256, 32640, 65408, 130944};
+constexpr int rc_idct_off(int l) { return ((1 << (2 * l)) - 16) / 3; }  // n = 1 << l, l = 2 .. 8
+constexpr int rc_fwd_off(int l) { return ((1 << (2 * l)) - 1) / 3; }    // n = 1 << l, l = 0 .. 5
+constexpr size_t kRcTabIdct = 0, kRcTabFwd = kRcTabIdct + rc_idct_off(9),
+                 kRcTabW8 = kRcTabFwd + rc_fwd_off(6), kRcTabIw = kRcTabW8 + 5 * 3 * 64,
+                 kRcTabSigma = kRcTabIw + 3 * (size_t)kRcKindOff[10],
+                 kRcTabFloats = kRcTabSigma + 256;
+constexpr size_t kRcPosKinds = 64, kRcPosWords = kRcPosKinds + kRcKindOff[10];
+struct ReconArgs {
+  const uint8_t* acs;   // [nb] raw strategy, bit 7 on covered non-first blocks
+  const uint8_t* qf;    // [nb] raw - 1
+  const int32_t* dc;    // [3][nb]
+  const int16_t* ac;    // [nb][3][64] natural-order slices
+  const int8_t* cmap;   // [2][ntiles_all]
+  uint32_t w, h, bxs, bys, xp, yp, tiles_x, ntiles_all;
+  float inv_g;          // 65536 / global_scale
+  float dc_step[3];
+  float bias[4];        // AdjustQuantBias
+  const float* tab;     // kRcTab* blob
+  const uint16_t* pos;  // kRcPos* blob
+  float* pa;            // [3][yp][xp] planes (transform output, filter ping)
+  float* pb;            // [3][yp][xp] planes (filter pong; the big kernel's column pass)
+  uint32_t* biglist;    // [0]: count, then the first blocks of the 128 / 256 px varblocks
+  uint32_t bigcap;      //   capacity of the list
+  uint8_t* rgb;         // RGB8 out
+  size_t stride;
+  float cbias, obias;   // cbrt(opsin bias), opsin bias
+  float cm[9];          // inverse opsin matrix, row-major
+};
+// the 64x64 tiles' varblocks (<= 64 px); to_rgb: no filter follows, RGB8 is written
+hipError_t launch_recon_tiles(const ReconArgs& a, bool to_rgb, hipStream_t s);
+hipError_t launch_recon_big(const ReconArgs& a, uint32_t nbig, hipStream_t s);
+// filters over the planes src -> dst, or -> RGB8 when `last`; epf pass: 0 (12
+// neighbours), 1 (4 neighbours), 2 (4 neighbours, one-pixel SADs)
+hipError_t launch_recon_gab(const ReconArgs& a, const float* src, float* dst, bool last,
+                            hipStream_t s);
+hipError_t launch_recon_epf(const ReconArgs& a, int pass, const float* src, float* dst, bool last,
+                            hipStream_t s);
+hipError_t launch_recon_colour(const ReconArgs& a, const float* src, hipStream_t s);
 // synthetic benchmark input (jxg_synth.hip): RGB8 rows of `stride` bytes
 hipError_t launch_synth(uint8_t* out, uint32_t w, uint32_t h, size_t stride, uint64_t seed,
                         hipStream_t s);

@@ -2,6 +2,7 @@
 #include "jxg_tables.h"
 
 #include <cmath>
+#include <algorithm>
 #include <cstring>
 
 #include "jxg_bitstream.h"
@@ -11,7 +12,7 @@ namespace jxg {
 
 // default dequantization weights (inverse steps) [ext libjxl quant_weights.cc]
 // kinds: 0 DCT8, 1 DCT4X4, 2 DCT4X8 / DCT8X4, 3 IDENTITY, 4 DCT2X2
-void quant_weights(float out[5][3][64]) {
+static void quant_weights_d(double out[5][3][64]) {
   static const double dct8[3][6] = {{3150.0, 0.0, -0.4, -0.4, -0.4, -2.0},
                                     {560.0, 0.0, -0.3, -0.3, -0.3, -0.3},
                                     {512.0, -2.0, -1.0, 0.0, -1.0, -2.0}};
@@ -48,15 +49,15 @@ void quant_weights(float out[5][3][64]) {
   double w[3 * 64];
   weights(8, 8, dct8, 6, w);
   for (int c = 0; c < 3; c++)
-    for (int i = 0; i < 64; i++) out[0][c][i] = (float)w[c * 64 + i];
+    for (int i = 0; i < 64; i++) out[0][c][i] = w[c * 64 + i];
   weights(4, 4, dct4, 4, w);
   for (int c = 0; c < 3; c++)
     for (int y = 0; y < 8; y++)
-      for (int x = 0; x < 8; x++) out[1][c][y * 8 + x] = (float)w[c * 64 + (y / 2) * 4 + x / 2];
+      for (int x = 0; x < 8; x++) out[1][c][y * 8 + x] = w[c * 64 + (y / 2) * 4 + x / 2];
   weights(4, 8, dct4x8, 4, w);
   for (int c = 0; c < 3; c++)
     for (int y = 0; y < 8; y++)
-      for (int x = 0; x < 8; x++) out[2][c][y * 8 + x] = (float)w[c * 64 + (y / 2) * 8 + x];
+      for (int x = 0; x < 8; x++) out[2][c][y * 8 + x] = w[c * 64 + (y / 2) * 8 + x];
   // IDENTITY: weight [0] everywhere, [1] at slots 1 / 8, [2] at slot 9;
   // DCT2X2: [0] slots 1 / 8, [1] slot 9, level-2 quadrants [2] / [3]
   // (off-diagonal / diagonal), level-1 quadrants [4] / [5]
@@ -79,6 +80,14 @@ void quant_weights(float out[5][3][64]) {
         out[4][c][y * 8 + x] = dct2_w[c][k];
       }
   }
+}
+
+void quant_weights(float out[5][3][64]) {
+  static double d[5][3][64];
+  quant_weights_d(d);
+  for (int k = 0; k < 5; k++)
+    for (int c = 0; c < 3; c++)
+      for (int i = 0; i < 64; i++) out[k][c][i] = (float)d[k][c][i];
 }
 
 // fuzzy-erosion weights of the masking quant field (== oracle/aq.c
@@ -395,6 +404,130 @@ BigTables build_big_tables() {
       for (int k = 0; k < M; k++)
         T.tab[kBigTabLlfIb + (l * 32 + nn) * 32 + k] =
             (float)(k ? std::sqrt(2.0) * std::cos(pi * (2 * nn + 1) * k / (2.0 * M)) : 1.0);
+  }
+  return T;
+}
+
+// ---- decode-side reconstruction (jxg_recon.hip): every table in double,
+// rounded once (== oracle/jxl_decode.py default_dequant, kind_tables,
+// _idct_mat, _dct_mat / _llf_scale, epf_inv_sigma) ----
+static void natural_order(int rows, int cols, uint16_t* order) {
+  const int cs = rows / 8, cl = cols / 8, xf = cols / rows;
+  int cur = 0;
+  for (int y = 0; y < cs; y++)
+    for (int x = 0; x < cl; x++) order[cur++] = (uint16_t)(y * cols + x);
+  auto visit = [&](int x, int y, bool skip_llf) {
+    if (y % xf) return;
+    y /= xf;
+    if (skip_llf && x < cl && y < cs) return;
+    order[cur++] = (uint16_t)(y * cols + x);
+  };
+  for (int i = 0; i < cols; i++)
+    for (int j = 0; j <= i; j++) {
+      const bool odd = i & 1;
+      visit(odd ? i - j : j, odd ? j : i - j, true);
+    }
+  for (int ip = cols - 1; ip > 0; ip--) {
+    const int i = ip - 1;
+    for (int j = 0; j <= i; j++) {
+      const int x = cols - 1 - (i - j), y = cols - 1 - j;
+      const bool odd = i & 1;
+      visit(odd ? y : x, odd ? x : y, false);
+    }
+  }
+}
+
+ReconTables build_recon_tables(uint32_t global_scale) {
+  ReconTables T;
+  T.tab.assign(kRcTabFloats, 0.0f);
+  T.pos.assign(kRcPosWords, 0);
+  const double pi = 3.14159265358979323846;
+  for (int l = 2; l <= 8; l++) {  // [k][x]: (k ? sqrt 2 : 1) cos(pi (2x + 1) k / 2n)
+    const int n = 1 << l;
+    float* m = &T.tab[kRcTabIdct + rc_idct_off(l)];
+    for (int k = 0; k < n; k++)
+      for (int x = 0; x < n; x++)
+        m[k * n + x] = (float)((k ? std::sqrt(2.0) : 1.0) * std::cos(pi * (2 * x + 1) * k / (2.0 * n)));
+  }
+  for (int l = 0; l <= 5; l++) {  // [k][i]: normalised forward DCT / LLF scale
+    const int n = 1 << l;
+    float* m = &T.tab[kRcTabFwd + rc_fwd_off(l)];
+    for (int k = 0; k < n; k++) {
+      const double sc = std::cos(pi * k / (16.0 * n)) * std::cos(pi * k / (8.0 * n)) *
+                        std::cos(pi * k / (4.0 * n));
+      for (int i = 0; i < n; i++)
+        m[k * n + i] = (float)((k ? std::sqrt(2.0) : 1.0) * std::cos(pi * (2 * i + 1) * k / (2.0 * n)) /
+                               n / sc);
+    }
+  }
+  // the 8x8 class: zig-zag order, inverse weights in slice order
+  {
+    int cur = 0;
+    uint16_t* o = T.pos.data();
+    o[cur++] = 0;
+    for (int i = 0; i < 8; i++)
+      for (int j = 0; j <= i; j++) {
+        int x = j, y = i - j;
+        if (i & 1) std::swap(x, y);
+        if (x == 0 && y == 0) continue;
+        o[cur++] = (uint16_t)(y * 8 + x);
+      }
+    for (int ip = 7; ip > 0; ip--) {
+      const int i = ip - 1;
+      for (int j = 0; j <= i; j++) {
+        int x = 7 - (i - j), y = 7 - j;
+        if (i & 1) std::swap(x, y);
+        o[cur++] = (uint16_t)(y * 8 + x);
+      }
+    }
+    static double w[5][3][64];
+    quant_weights_d(w);
+    for (int k = 0; k < 5; k++)
+      for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 64; i++)
+          T.tab[kRcTabW8 + (k * 3 + c) * 64 + i] = (float)(1.0 / w[k][c][o[i]]);
+  }
+  // merged kinds 0-5 (library defaults) and 6-9 (the binary16 parameters the
+  // stream carries)
+  static const int kDims[10][2] = {{8, 16},  {16, 16}, {16, 32},  {32, 32},   {32, 64},
+                                   {64, 64}, {64, 128}, {128, 128}, {128, 256}, {256, 256}};
+  for (int kind = 0; kind < 10; kind++) {
+    const int rows = kDims[kind][0], cols = kDims[kind][1];
+    const int nb = kind < kNumKinds ? kKindNumBands[kind] : 8;
+    uint16_t* order = &T.pos[kRcPosKinds + kRcKindOff[kind]];
+    natural_order(rows, cols, order);
+    std::vector<double> w((size_t)rows * cols);
+    for (int c = 0; c < 3; c++) {
+      double bands[8];
+      bands[0] = kind < kNumKinds ? kKindBands[kind][c][0] : big_param(kind - kNumKinds, c, 0);
+      for (int i = 1; i < nb; i++) {
+        const double v = kind < kNumKinds ? kKindBands[kind][c][i] : big_param(kind - kNumKinds, c, i);
+        bands[i] = bands[i - 1] * (v > 0 ? 1.0 + v : 1.0 / (1.0 - v));
+      }
+      const double scale = (nb - 1) / (1.4142135623730951 + 1e-6);
+      const double rc = scale / (cols - 1), rr = scale / (rows - 1);
+      for (int y = 0; y < rows; y++)
+        for (int x = 0; x < cols; x++) {
+          const double dx = x * rc, dy = y * rr;
+          const double pos = std::sqrt(dx * dx + dy * dy);
+          int idx = (int)pos;
+          if (idx > nb - 2) idx = nb - 2;
+          const double frac = pos - idx;
+          const double a = bands[idx], b = bands[idx + 1];
+          w[(size_t)y * cols + x] = a * std::pow(b / a, frac);
+        }
+      float* iw = &T.tab[kRcTabIw + (size_t)c * kRcKindOff[10] + kRcKindOff[kind]];
+      for (int p = 0; p < rows * cols; p++) iw[p] = (float)(1.0 / w[order[p]]);
+    }
+  }
+  // EPF: raw quant field - 1 -> inverse sigma; blocks below the minimum
+  // (not filtered) are marked with +1
+  for (int q = 0; q < 256; q++) {
+    const double scale = (double)global_scale / 65536.0;
+    double sigma = 0.46 / (scale * (double)(q + 1) * -1.1715728752538099) * ((double)kEpfSharpness / 7.0);
+    if (sigma > -1e-4) sigma = -1e-4;
+    const double inv = 1.0 / sigma;
+    T.tab[kRcTabSigma + q] = inv < -3.90625 ? 1.0f : (float)inv;
   }
   return T;
 }

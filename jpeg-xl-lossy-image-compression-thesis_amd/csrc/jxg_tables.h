@@ -29,6 +29,15 @@ struct BigTables {
 };
 BigTables build_big_tables();
 
+// decode-side reconstruction (jxg_recon.hip): the kRcTab* float blob and the
+// kRcPos* position blob of jxg_kernels.h; the EPF sigma table is the only part
+// that depends on the frame (its global scale)
+struct ReconTables {
+  std::vector<float> tab;
+  std::vector<uint16_t> pos;
+};
+ReconTables build_recon_tables(uint32_t global_scale);
+
 // DequantMatrices of HfGlobal [ext quant_weights.cc]: all_default when mask is
 // 0, else Library for every table but those of the big kinds in mask (bit 0
 // 128X64, 1 128X128, 2 256X128, 3 256X256: the kinds the frame uses, effort

@@ -94,6 +94,7 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_set_input_stream", "jxg_pipeline_depth", "jxg_shard_plan",
            "jxg_shard_submit_device", "jxg_shard_next_head", "jxg_shard_write_next",
            "jxg_shard_write_flush", "jxg_set_pipeline_lanes", "jxg_warmup",
+           "jxg_reconstruct_rgb8", "jxg_reconstruct_rgb8_device",
 )
 
 _lib = None
@@ -167,6 +168,8 @@ def load():
     lib.jxg_synth_rgb8_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, sz,
                                           ctypes.c_uint64]
     lib.jxg_warmup.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+    lib.jxg_reconstruct_rgb8.argtypes = [vp, vp, sz]
+    lib.jxg_reconstruct_rgb8_device.argtypes = [vp, vp, sz]
     _lib = lib
     return lib
 
@@ -211,6 +214,7 @@ class Encoder:
         lib = load()
         self.params = _Params(distance, effort, proposals, num_devices, flags, device)
         self._ctx = ctypes.c_void_p()
+        self._last_wh = None  # size of the last one-at-a-time encode (reconstruct)
         _check(lib.jxg_create(ctypes.byref(self.params), ctypes.byref(self._ctx)))
 
     def close(self):
@@ -245,7 +249,27 @@ class Encoder:
             raise ValueError("expected (H, W, 3) uint8")
         buf = _Buffer()
         _check(load().jxg_encode_rgb8(self._ctx, rgb.ctypes.data, w, h, w * 3, ctypes.byref(buf)))
+        self._last_wh = (w, h)
         return self._take(buf)
+
+    def reconstruct(self) -> np.ndarray:
+        """(H, W, 3) uint8: the decoded image of the frame last encoded with
+        :meth:`encode` / :meth:`encode_device`, reconstructed on the GPU from
+        the context's coefficients (jxg_reconstruct_rgb8; no decoder run).
+        Raises JxgError when the last encode was a batch, streamed or sharded
+        one, or none."""
+        w, h = self._last_wh or (1, 1)
+        out = np.empty((h, w, 3), dtype=np.uint8)
+        _check(load().jxg_reconstruct_rgb8(self._ctx, out.ctypes.data, w * 3))
+        return out
+
+    def reconstruct_device(self, ptr: int, row_stride: int | None = None) -> None:
+        """The same image written to a device pointer (rows of `row_stride`
+        bytes, default 3 * width; only the first 3 * width of each are
+        written); returns when it is complete."""
+        w, _ = self._last_wh or (1, 1)
+        _check(load().jxg_reconstruct_rgb8_device(self._ctx, ctypes.c_void_p(ptr),
+                                                  row_stride or w * 3))
 
     def encode_batch(self, frames) -> list:
         """Host frames of equal size, each (H, W, 3) uint8 -> list of codestream
@@ -285,6 +309,7 @@ class Encoder:
         buf = _Buffer()
         _check(load().jxg_encode_rgb8_device(self._ctx, ctypes.c_void_p(ptr), width, height,
                                              row_stride or width * 3, ctypes.byref(buf)))
+        self._last_wh = (width, height)
         return self._take(buf) if copy else Codestream(buf)
 
     # streaming encode (jxg_submit_rgb8[_device] / jxg_receive): a software

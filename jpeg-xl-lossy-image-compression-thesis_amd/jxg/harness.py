@@ -179,6 +179,12 @@ def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_siz
     h, w = orig_rgb.shape[:2]
     raw = w * h * 3
     q = encoder.compare(orig_rgb, comp_rgb, ssim=ssim)
+    return _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_size, raw, q,
+                   ssim, result_file)
+
+
+def _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_size, raw, q, ssim,
+            result_file) -> ComparisonResult:
     res = ComparisonResult(
         orig_name, comp_name, float(np.float32(distance)), int(effort), int(orig_file_size),
         int(comp_file_size), raw, raw,
@@ -189,3 +195,30 @@ def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_siz
         write_csv_header(result_file, RESULT_HEADER)
         write_csv([res], result_file)
     return res
+
+
+def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int,
+                       comp_name: str, distance: float, effort: int,
+                       result_file: str | None = None, ssim: bool = True):
+    """Encode + compare_to_orig in one process with no decoder: the image is
+    encoded from device memory, its decoded pixels are reconstructed on the
+    device (Encoder.reconstruct_device, jxg_reconstruct_rgb8_device) and the
+    metrics run on the two device images.  ``encoder`` carries the distance and
+    effort it was created with; ``distance`` / ``effort`` fill the record.
+    Returns (codestream bytes, ComparisonResult)."""
+    import torch
+
+    o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
+    if o.ndim != 3 or o.shape[2] != 3:
+        raise ValueError("orig_rgb must be (H, W, 3) uint8")
+    h, w = o.shape[:2]
+    dev = "cuda:%d" % encoder.params.device
+    d_orig = torch.from_numpy(o).to(dev)
+    d_comp = torch.empty_like(d_orig)
+    torch.cuda.synchronize(dev)
+    data = encoder.encode_device(d_orig.data_ptr(), w, h)
+    encoder.reconstruct_device(d_comp.data_ptr())
+    q = encoder.compare_device(d_orig.data_ptr(), d_comp.data_ptr(), w, h, ssim=ssim)
+    raw = w * h * 3
+    return data, _record(orig_name, comp_name, distance, effort, orig_file_size, len(data), raw, q,
+                         ssim, result_file)
