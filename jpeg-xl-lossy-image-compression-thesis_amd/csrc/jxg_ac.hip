@@ -644,51 +644,287 @@ __global__ __launch_bounds__(kAcThreads) void ac_emit_kernel(AcArgs a) {
 // sequential dependency), then the group's workgroup places the emitted bits
 // in parallel.
 // ---------------------------------------------------------------------------
-// rANS backwards over each group's records, one wave per group, kAnsWaves
-// groups per workgroup sharing the LDS tables (all alias inverses, 64 KB).
+// Two chain kernels share the step: the streaming pipeline's frames run the
+// lane-per-chain form below (small footprint beside the other frames'
+// kernels), a frame coded by itself the diagonal form after it (shorter span);
+// launch_ans chooses.
 //
-// The state recurrence is the stream's only sequential dependency, so its
+// rANS backwards over each group's records, one LANE per group: workgroup w
+// of a frame takes the slots order[64 w .. 64 w + 63] (longest group first,
+// so its lanes have similar lengths), and lane c of its chain wave (wave 0)
+// runs that slot's chain by itself: at step t the record n_c - 1 - t.  Every
+// lane does useful work at every step, so the 510 chains of an 8K frame are
+// 8 chain waves instead of 510.
+//
+// The state recurrence is the stream's only sequential dependency, so the
 // per-step latency sets the kernel time (a pass group holds up to ~100K
-// tokens).  The chain runs "on the diagonal": lane L holds record L's
-// constants in registers (no readlane per step) and step L is computed in
-// lane L from lane L-1's result, which a DPP wave rotation (wave_ror:1, VALU
-// to VALU) hands over; the other lanes run the same rANS steps on other
-// (valid) states, so every lane's table address stays in range.  The state
-// x = k << 12 | v is kept as (k = quotient of the previous step, v = its
-// inverse-table entry).  One wave issues about one instruction per 4 cycles
-// whatever its dependency depth, so the step is cut to its fewest
-// instructions (15 issue slots; ns per token at 8K: 62.3 -> 56.5 -> 49.6 over
-// the three forms tried, profiles/r03p):
-//   * in the read's shadow: k from lane L-1 (DPP), emission k >= f << 8
-//     (x >= f << 20), which makes the shift sh = 16 (x >> 16 = k >> 4: v
-//     drops out) or 0; lane s-1 saves its pre-step state (constant-mask select);
-//   * after the read: x = k << 12 + v, xs = x >> sh, the quotient
-//     floor(xs / f) = trunc((xs + 0.5) * rcp(f)) in f64 (cvt, fma, cvt; exact:
-//     one rounding, < 2^-19, while (xs + .5) / f stays >= .5 / f from an
-//     integer), the table address base + 2 (xs - q f) (shift-add, 24-bit
-//     multiply-add), the next read.
-// Per 64 records the lanes decode record, f, rcp and table base in parallel
-// (the next 64 records are fetched meanwhile) and store the emitted bits of
-// their record with one coalesced store.
-// (A uniform variant -- every lane runs the same step, the quotient on the
-// scalar unit from readlane'd constants, two vector multiply-adds between the
-// reads -- is exact but took 17.5 vs 6.35 ms: ~60 instructions per step.)
-// Two chain waves per SIMD (8 per workgroup, 68 KB of LDS): the second wave
-// delays every step by its own issue (one frame's chains 6.7 vs 6.0 ms at 8K
-// with 4 per workgroup, profiles/r02g), but the chains of a frame occupy 64
-// CUs instead of 128, so the transform kernels of the frames behind keep full
-// occupancy on the rest (pipelined 8K +3.5 %).  The chain waves
-// run at the highest wave priority so co-resident transform waves only fill
-// their idle issue slots.
-#ifndef JXG_ANS_WAVES  // (experiment builds override it: tools/build_variant.sh)
-#define JXG_ANS_WAVES 8
-#endif
-constexpr int kAnsWaves = JXG_ANS_WAVES;
+// tokens).  The state x = k << 12 | v is kept as (k = quotient of the
+// previous step, v = its inverse-table entry).  The step's dependent path:
+//   emission k >= f << 8 (x >= f << 20) -> the shift sh = 16 or 0,
+//   x = k << 12 + v, xs = x >> sh, the quotient floor(xs / f) =
+//   trunc((xs + 0.5) * rcp(f)) in f64 (cvt, fma, cvt; exact: one rounding,
+//   < 2^-19, while (xs + .5) / f stays >= .5 / f from an integer), the table
+//   address base + 2 (xs - q f) (shift-add, 24-bit multiply-add), the u16 read.
+// The chain wave touches no global memory (64 lanes walking 64 streams are 64
+// cache lines per access, and the CU's memory pipe then sets the step: 8.3 ms
+// a frame against 5.6 with the loads and stores in the chain wave, DESIGN.md
+// §3.5).  It works from two LDS stages of kAnsBlk steps x 64 lanes, double
+// buffered by block:
+//   ea : per step and lane the record's stage word: the byte offset of its
+//        constants entry (one 16-byte entry per (histogram, token): rcp =
+//        1.0 / (double)f computed once per workgroup -- no division in the
+//        loop --, -2 f, and the byte offset of the symbol's inverse row; the
+//        idle entry, f = 4096 on histogram 0, never emits and keeps any state
+//        valid), and beside it the record's raw bits and their count;
+//   x  : the state before the step, which the chain wave writes back.
+// The helper waves fetch the records of block b + 2, fill ea for block b + 1
+// and turn the x and ea of block b - 1 into the records' emitted bits while
+// the chain wave runs block b: a helper wave takes one chain at a time, lane =
+// step, so its loads and stores are contiguous.  A lane past its record 0
+// gets idle entries; the state before the first idle step is the chain's
+// final state (an empty chain: the initial state 0x130000), which the helper
+// stores.  The stage rows are 65 words so that the chain wave's rows and the
+// helpers' columns are both free of bank conflicts.
+//
+// Synchronisation: one workgroup barrier per block and nothing else.  Every
+// wave runs the same number of barriers, NB + 1 with NB taken from the
+// workgroup's longest chain before the loop; no wave waits on a flag.
+//
+// LDS: inverse tables 64 KB + constants 8.02 KB + cluster map 0.5 KB + stages
+// 2 x 2 x 16.25 KB = 65 KB + chain parameters 2 KB = 139.5 KB per workgroup
+// (142 872 bytes in the kernel descriptor), 8 workgroups per 8K frame (the
+// diagonal form: 64 x 68 KB).  20.5 KB of the CU's 160 KB stay free beside a
+// chain workgroup: ans_sums (12.1 KB), ans_emit (14.8 KB), lf_code (17.3 KB),
+// lf_hist, vb_list, merge_resolve and concat workgroups fit there; front (79
+// KB), aq (46 KB), merge_eval / merge_write (37 KB) and ac_hist (31 KB) do not,
+// so the 8 CUs of a frame's chains are lost to the transform kernels of the
+// frames behind it.  The chain wave runs at the highest wave priority.
+// Workgroup shape: ONE chain wave per workgroup, not one per SIMD sharing the
+// tables: in the form where each chain wave did its own loads and stores, 2
+// and 4 chain waves per workgroup ran 1.5x and 2.4x slower;
+// that has not been measured again with helpers.  Wave 4 only takes the
+// barriers: on the assumption (not measured: no 6-against-7-helper A/B was
+// run) that a workgroup's waves go to the SIMDs round robin, it would share
+// the chain wave's SIMD.
+constexpr int kAnsWgWaves = 8;  // wave 0: the chains; waves 1-3, 5-7: helpers; 4: barriers only
+constexpr int kAnsHelpers = 6;
+constexpr int kAnsPieces = (64 + kAnsHelpers - 1) / kAnsHelpers;  // chains per helper
+constexpr int kAnsBlk = 64;     // steps per stage block
+constexpr int kAnsRow = 65;     // stage row stride in words
+constexpr uint32_t kAnsIdle = kAnsHists * 64;  // constants entry of the idle step
+struct AnsConst {
+  double rcp;      // 1.0 / (double)f
+  uint32_t nf2;    // -2 f
+  uint32_t base2;  // byte offset of the symbol's inverse row
+};
+struct AnsChainP {  // a lane's chain, for the helpers
+  int n;            // records
+  uint32_t slot;
+  uint32_t c1, c2, c3;  // first stream position of bands 1-3
+  uint32_t g;       // pass group; ~0u: no chain in this lane
+  uint32_t pad[2];
+};
+struct AnsLds {
+  AnsConst c[kAnsIdle + 1];            // per (histogram, token), then the idle entry
+  uint16_t ent[256];                   // cluster byte -> byte offset of its histogram's 64 entries
+  uint32_t inv[kAnsHists * 4096 / 2];  // alias inverses, u16 pairs
+  uint32_t ea[2][kAnsBlk * kAnsRow];
+  uint32_t x[2][kAnsBlk * kAnsRow];
+  AnsChainP ch[64];
+  int T;                               // steps of the workgroup: its longest chain + 1
+};
+// blk: the chain workgroup's index within its frame
+__device__ __forceinline__ void ans_chain(const AnsArgs& a, uint32_t blk) {
+  // (one object, constants first: every table address is an instruction offset)
+  __shared__ __attribute__((aligned(16))) AnsLds L;
+  const uint32_t c0 = blk * 64;
+  if (c0 >= a.n) return;  // the whole workgroup
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tab);
+  for (uint32_t i = threadIdx.x; i < a.nhist * 512; i += blockDim.x)
+    reinterpret_cast<uint4*>(L.inv)[i] = reinterpret_cast<const uint4*>(src + kAnsInvOff / 4)[i];
+  for (uint32_t i = threadIdx.x; i <= kAnsIdle; i += blockDim.x) {
+    uint32_t f = 4096, row = 0;  // the idle step; also the histograms not in use
+    if (i < a.nhist * 64) {
+      const uint32_t e = src[(i >> 6) * 128 + (i & 63)];
+      f = (e & 0xFFF) + 1;
+      row = (i >> 6) * 4096 + (e >> 12);
+    }
+    L.c[i].rcp = 1.0 / (double)f;
+    L.c[i].nf2 = (uint32_t)(-(int)(2 * f));
+    L.c[i].base2 = 2 * row;
+  }
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
+    L.ent[i] = (uint16_t)(i < 136 ? min((uint32_t)a.tab[kAnsMapOff + i], kAnsHists - 1) * 64 * 16
+                                  : kAnsIdle * 16);
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0) {
+    AnsChainP P = {0, 0, 0, 0, 0, ~0u, {0, 0}};
+    if (c0 + lane < a.n) {
+      P.slot = a.order[c0 + lane];
+      P.g = slot_group(a.glist, a.g0, P.slot);
+      P.n = (int)(a.ntok[P.g * 3] + a.ntok[P.g * 3 + 1] + a.ntok[P.g * 3 + 2]);
+      P.c1 = a.bandtok[P.g * kBands];
+      P.c2 = P.c1 + a.bandtok[P.g * kBands + 1];
+      P.c3 = P.c2 + a.bandtok[P.g * kBands + 2];
+    }
+    L.ch[lane] = P;
+    int m = P.n;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_xor(m, d, 64));
+    if (lane == 0) L.T = m + 1;
+  }
+  __syncthreads();
+  const int NB = (L.T + kAnsBlk - 1) / kAnsBlk;  // blocks: the same in every wave
+  const uint8_t* inv = reinterpret_cast<const uint8_t*>(L.inv);
+  const uint8_t* cst = reinterpret_cast<const uint8_t*>(L.c);
+  // helper h of kAnsHelpers, or none
+  const int h = (wave & 3) ? (int)(wave >> 2) * 3 + (int)(wave & 3) - 1 : -1;
+  // a helper wave takes one chain at a time, lane = step of the block
+  const uint32_t hs = lane;
+  // stage word of a record: its constants entry (byte offset, a multiple of
+  // 16, < 2^14) | raw-bit count | raw bits << 14
+  auto word_of = [&](uint32_t rec) {
+    return ((uint32_t)L.ent[rec & 0xFF] + ((rec >> 4) & 0x3F0)) | ((rec >> 14) & 15) | (rec >> 18) << 14;
+  };
+  auto record = [&](const AnsChainP& P, int i) {  // stream position i of the chain (rec_index)
+    const uint32_t u = (uint32_t)i;
+    const uint32_t j = (u >= P.c1 ? 1u : 0u) + (u >= P.c2 ? 1u : 0u) + (u >= P.c3 ? 1u : 0u);
+    const uint32_t lo = u >= P.c3 ? P.c3 : u >= P.c2 ? P.c2 : u >= P.c1 ? P.c1 : 0u;
+    return a.tokens[(uint64_t)P.slot * kGroupTokStride + j * (uint32_t)kBandTokStride + (u - lo)];
+  };
+  // A helper owns the chains q = h, h + kAnsHelpers, ... (<= kAnsPieces of
+  // them): the same lane fills and flushes a stage slot, so its own program
+  // order is all the ordering a slot's reuse needs.
+  constexpr uint32_t kIdleRec = 0xFFu;  // cluster byte 0xFF -> the idle entry
+  // the records of block b, all loads in flight at once
+  auto fetch = [&](int b, uint32_t* R) {
+#pragma unroll
+    for (int j = 0; j < kAnsPieces; j++) {
+      const int q = h + kAnsHelpers * j;
+      R[j] = kIdleRec;
+      if (q < 64) {
+        const AnsChainP P = L.ch[q];
+        const int i = P.n - 1 - (b * kAnsBlk + (int)hs);
+        if (i >= 0) R[j] = record(P, i);
+      }
+    }
+  };
+  auto fill = [&](int b, const uint32_t* R) {
+#pragma unroll
+    for (int j = 0; j < kAnsPieces; j++) {
+      const int q = h + kAnsHelpers * j;
+      if (q < 64) L.ea[b & 1][hs * kAnsRow + q] = word_of(R[j]);
+    }
+  };
+  // what block b left in the stages: the states and its records' words
+  auto unstage = [&](int b, uint32_t* X, uint32_t* RC) {
+#pragma unroll
+    for (int j = 0; j < kAnsPieces; j++) {
+      const int q = h + kAnsHelpers * j;
+      X[j] = RC[j] = 0;
+      if (q < 64) {
+        X[j] = L.x[b & 1][hs * kAnsRow + q];
+        RC[j] = L.ea[b & 1][hs * kAnsRow + q];
+      }
+    }
+  };
+  auto flush = [&](int b, const uint32_t* X, const uint32_t* RC) {
+#pragma unroll
+    for (int j = 0; j < kAnsPieces; j++) {
+      const int q = h + kAnsHelpers * j;
+      if (q < 64) {
+        const AnsChainP P = L.ch[q];
+        const int i = P.n - 1 - (b * kAnsBlk + (int)hs);
+        const uint32_t x = X[j], w = RC[j];
+        if (i >= 0) {
+          // emitted bits of the record: [16-bit chunk] then its raw bits
+          // (their sums per chunk: ans_sums)
+          const uint32_t nf2 = reinterpret_cast<const AnsConst*>(cst + (w & 0x3FF0))->nf2;
+          const bool em = (x >> 12) >= (uint32_t)__mul24((int)nf2, -128);  // k >= f << 8
+          const uint32_t raw = w >> 14, nb = w & 15;
+          const uint64_t o = (uint64_t)P.slot * kGroupTokStride + (uint32_t)i;
+          a.val[o] = em ? (x & 0xFFFFu) | raw << 16 : raw;
+          a.len[o] = (uint8_t)(em ? nb + 16 : nb);
+        } else if (i == -1 && P.g != ~0u) {
+          a.state[P.g] = x;  // the state after record 0
+        }
+      }
+    }
+  };
+  uint32_t k = 0x130u, v = 0;  // the initial state x = 0x130000 (chain wave)
+  auto chain_block = [&](int b) {
+    const uint32_t* eas = L.ea[b & 1] + lane;
+    uint32_t* xo = L.x[b & 1] + lane;
+    AnsConst Cn = *reinterpret_cast<const AnsConst*>(cst + (eas[0] & 0x3FF0));
+#pragma unroll
+    for (int s = 0; s < kAnsBlk; s++) {
+      const AnsConst C = Cn;  // read one step ahead, off the dependent path
+      if (s + 1 < kAnsBlk) Cn = *reinterpret_cast<const AnsConst*>(cst + (eas[(s + 1) * kAnsRow] & 0x3FF0));
+      const double hr = 0.5 * C.rcp;
+      const uint32_t Fq = (uint32_t)__mul24((int)C.nf2, -128);  // f << 8: emit iff k >= Fq
+      // the dependent path: k, v -> x -> xs -> quotient -> address -> read
+      const uint32_t sh = k >= Fq ? 16u : 0u;
+      const uint32_t x = (k << 12) + v;
+      const uint32_t xs = x >> sh;
+      const uint32_t kk = (uint32_t)__builtin_fma((double)xs, C.rcp, hr);
+      const uint32_t x2 = (xs << 1) + C.base2;
+      uint32_t addr;
+      asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(addr) : "v"(kk), "v"(C.nf2), "v"(x2));
+      v = *reinterpret_cast<const uint16_t*>(inv + addr);
+      k = kk;
+      xo[s * kAnsRow] = x;
+    }
+  };
+  if (wave == 0) __builtin_amdgcn_s_setprio(3);
+  // helpers: the records are fetched two blocks ahead of the chain wave and
+  // staged one block ahead, so a block's global latency is never waited for
+  uint32_t R[kAnsPieces], X[kAnsPieces], RC[kAnsPieces];
+  if (h >= 0) {
+    fetch(0, R);
+    fill(0, R);
+    fetch(1, R);
+  }
+  __syncthreads();
+  for (int b = 0; b < NB; b++) {
+    if (wave == 0) {
+      chain_block(b);
+    } else if (h >= 0) {
+      if (b > 0) unstage(b - 1, X, RC);  // before fill(b + 1) reuses block b - 1's ea slots
+      fill(b + 1, R);
+      fetch(b + 2, R);
+      if (b > 0) flush(b - 1, X, RC);
+    }
+    __syncthreads();
+  }
+  if (h >= 0) {
+    unstage(NB - 1, X, RC);
+    flush(NB - 1, X, RC);
+  }
+}
+__global__ __launch_bounds__(kAnsWgWaves * 64) void ans_encode_kernel(Batch<AnsArgs> bt_) {
+  ans_chain(bt_.a[blockIdx.z], blockIdx.x);
+}
+// The latency form, for a frame coded by itself (one-at-a-time encodes: nothing
+// else wants the GPU, and the frame waits for its longest chain): one WAVE per
+// group "on the diagonal", kAnsDiagWaves groups per workgroup sharing the LDS
+// tables (symbols 4 KB + all alias inverses 64 KB = 68 KB).  Lane L holds
+// record L's constants in registers and step L is computed in lane L from
+// lane L-1's result, which a DPP wave rotation (wave_ror:1, VALU to VALU)
+// hands over; the other lanes run the same rANS steps on other (valid)
+// states, so every lane's table address stays in range.  The same step
+// arithmetic as above in 15 issue slots, with no stage, no barrier and no
+// helper in its way: 5.6 ms for an 8K frame's chains against 6.15 ms for the
+// lane-per-chain form, but 510 waves on 64 CUs, which is what the streamed
+// frames cannot afford.  Per 64 records the lanes decode
+// record, f, rcp and table base in parallel (the next 64 records are fetched
+// meanwhile) and store the emitted bits of their record with one coalesced
+// store.  The lane protocol is pinned by tests/test_ans_lane_model.py.
+constexpr int kAnsDiagWaves = 8;
 __device__ __forceinline__ uint32_t wave_ror1(uint32_t x) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x13C, 0xF, 0xF, false);
 }
 // blk: the chain workgroup's index within its frame
-__device__ __forceinline__ void ans_chain(const AnsArgs& a, uint32_t blk) {
+__device__ __forceinline__ void ans_chain_diag(const AnsArgs& a, uint32_t blk) {
   __shared__ uint32_t sSym[kAnsHists * 128];
   __shared__ uint32_t sInv[kAnsHists * 4096 / 2];  // u16 pairs
   __shared__ uint8_t sMap[136];
@@ -700,10 +936,10 @@ __device__ __forceinline__ void ans_chain(const AnsArgs& a, uint32_t blk) {
   __syncthreads();
   const uint8_t* inv = reinterpret_cast<const uint8_t*>(sInv);
   const uint32_t lane = threadIdx.x & 63;
-  // the chain's group: groups sorted longest first (host), kAnsWaves per
+  // the chain's group: groups sorted longest first (host), kAnsDiagWaves per
   // workgroup, so a workgroup's waves finish at about the same time and the
   // workgroups of short groups free their CUs early
-  const uint32_t gi = __builtin_amdgcn_readfirstlane(blk * kAnsWaves + (threadIdx.x >> 6));
+  const uint32_t gi = __builtin_amdgcn_readfirstlane(blk * kAnsDiagWaves + (threadIdx.x >> 6));
   if (gi >= a.n) return;
   const uint32_t slot = __builtin_amdgcn_readfirstlane(a.order[gi]);
   const uint32_t g = __builtin_amdgcn_readfirstlane(slot_group(a.glist, a.g0, slot));
@@ -791,8 +1027,8 @@ __device__ __forceinline__ void ans_chain(const AnsArgs& a, uint32_t blk) {
   }
   if (n == 0 && lane == 0) a.state[g] = 0x130000u;
 }
-__global__ __launch_bounds__(kAnsWaves * 64) void ans_encode_kernel(Batch<AnsArgs> bt_) {
-  ans_chain(bt_.a[blockIdx.z], blockIdx.x);
+__global__ __launch_bounds__(kAnsDiagWaves * 64) void ans_encode_diag_kernel(Batch<AnsArgs> bt_) {
+  ans_chain_diag(bt_.a[blockIdx.z], blockIdx.x);
 }
 // After the chains, one 256-thread workgroup per group: the emitted bits of
 // every 64-record chunk q (stream order; records [n - 64 (K - q), n - 64 (K -
@@ -929,8 +1165,11 @@ __global__ __launch_bounds__(kEmitThreads) void ans_emit_kernel(Batch<AnsArgs> b
 }
 
 // the chains, then the bit placement, of k frames (same plan: same group
-// count; the segment grid covers the longest group of any of them)
-void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s) {
+// count; the segment grid covers the longest group of any of them).
+// streamed: the frames share the GPU with other frames' kernels -> the
+// lane-per-chain kernel (8 workgroups per 8K frame); a frame coded by itself
+// -> the diagonal kernel, whose chains finish sooner.  Same val / len / state.
+void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s, bool streamed) {
   if (!k || !a[0].n) return;
   const Batch<AnsArgs> b = make_batch(a, k);
   uint32_t n = 0, maxtok = 0;
@@ -938,8 +1177,11 @@ void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s) {
     n = max(n, a[i].n);
     maxtok = max(maxtok, a[i].max_tokens);
   }
-  hipLaunchKernelGGL(ans_encode_kernel, dim3((n + kAnsWaves - 1) / kAnsWaves, 1, k),
-                     dim3(kAnsWaves * 64), 0, s, b);
+  if (streamed)
+    hipLaunchKernelGGL(ans_encode_kernel, dim3((n + 63) / 64, 1, k), dim3(kAnsWgWaves * 64), 0, s, b);
+  else
+    hipLaunchKernelGGL(ans_encode_diag_kernel, dim3((n + kAnsDiagWaves - 1) / kAnsDiagWaves, 1, k),
+                       dim3(kAnsDiagWaves * 64), 0, s, b);
   hipLaunchKernelGGL(ans_sums_kernel, dim3(n, 1, k), dim3(kSumThreads), 0, s, b);
   const uint32_t nseg = (maxtok + kSegChunks * 64 - 1) / (kSegChunks * 64);
   if (nseg) hipLaunchKernelGGL(ans_emit_kernel, dim3(n, nseg, k), dim3(kEmitThreads), 0, s, b);

@@ -1306,10 +1306,11 @@ static jxg_status stage_codes(Ctx* c, Job& J) {
     JXG_HIP(c->ans_state.ensure(f.ngroups));
     JXG_HIP(c->csum.ensure((uint64_t)std::max(1u, J.plan.ng()) * kAnsMaxChunks));
     JXG_HIP(c->ans_tab.ensure(kAnsTabBytes));
-    // chain order: the plan's groups by token count, longest first, so a
-    // chain workgroup holds groups of similar length and the workgroups of
-    // short groups give their CUs (and 68 KB of LDS each) back early -- the
-    // kernel still lasts as long as the longest group
+    // chain order: the plan's groups by token count, longest first, so the
+    // 64 lanes of a chain workgroup hold groups of similar length and the
+    // workgroups of short groups give their CUs (and their LDS, 139.5 KB each
+    // in the streamed form, 68 KB in the one-frame form) back
+    // early -- the kernel still lasts as long as the longest group
     const uint32_t ng = J.plan.ng();
     JXG_HIP(c->h_ans_order.ensure(ng));
     JXG_HIP(c->ans_order.ensure(ng));
@@ -1424,15 +1425,16 @@ static void build_emit(Ctx* c, Job& J) {
 }
 // the emission of k frames sharing a stream (codes built): rANS chains + bit
 // placement and LF streams as one launch each, then each frame's bit counts
-// to the host
-static jxg_status launch_emit(Ctx* const* cs, Job* const* js, uint32_t k) {
+// to the host.  streamed: frames of the streaming pipeline (launch_ans picks
+// the chain kernel by it)
+static jxg_status launch_emit(Ctx* const* cs, Job* const* js, uint32_t k, bool streamed) {
   if (!batch_ok(cs, js, k)) return JXG_ERR_INTERNAL;
   hipStream_t s = cs[0]->stream;
   const Job& J = *js[0];
   for (uint32_t i = 0; i < k; i++) build_emit(cs[i], *js[i]);
   if (J.ans) {
     const auto na = gather<AnsArgs>(js, k, [](Job& j) { return j.na; });
-    launch_ans(na.data(), k, s);
+    launch_ans(na.data(), k, s, streamed);
     JXG_HIP(hipGetLastError());
   }
   const auto la = gather<LfArgs>(js, k, [](Job& j) { return j.la; });
@@ -1455,7 +1457,7 @@ static jxg_status launch_emit(Ctx* const* cs, Job* const* js, uint32_t k) {
 }
 static jxg_status stage_emit(Ctx* c, Job& J, bool sync = true) {
   Job* jp = &J;
-  jxg_status st = launch_emit(&c, &jp, 1);
+  jxg_status st = launch_emit(&c, &jp, 1, false);
   if (!st && sync) st = wait_emission(c, J);
   return st;
 }
@@ -2010,7 +2012,7 @@ static jxg_status pipe_codes(PipeFrame* fr) {
       cs.push_back(q->lane);
       js.push_back(&q->J);
     }
-    const jxg_status e = launch_emit(cs.data(), js.data(), (uint32_t)cs.size());
+    const jxg_status e = launch_emit(cs.data(), js.data(), (uint32_t)cs.size(), true);
     if (e) B.err.store(e);
   }
   return st;

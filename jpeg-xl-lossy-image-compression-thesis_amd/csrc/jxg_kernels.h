@@ -201,8 +201,9 @@ struct AnsArgs {
   uint32_t max_tokens;     // most tokens of any group (ans_emit's segments per group)
 };
 constexpr uint32_t kAnsMaxChunks = (uint32_t)(kGroupTokStride / 64);
-// rANS chains + bit placement of k frames (same plan)
-void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s);
+// rANS chains + bit placement of k frames (same plan); streamed: the frames
+// belong to the streaming pipeline (other frames' kernels share the GPU)
+void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s, bool streamed);
 
 // LF-group modular streams: rows of (lf group, stream, channel, y)
 // One segment of <= kLfSeg samples of a channel row (long rows -- the
