@@ -1,5 +1,6 @@
 /*
- * jxg.h -- C ABI of the MI355X-native JPEG XL VarDCT encode path.
+ * jxg.h -- C ABI of the MI355X-native JPEG XL VarDCT encode path and of the
+ * decoder of the codestreams it writes (jxg_decode_*, at the end).
  *
  * Drop-in boundary: this library replaces what the benchmark harness reaches
  * through `docker exec ... /libjxl/build/tools/cjxl IN OUT --distance=D
@@ -25,8 +26,8 @@
  *
  * A context with streamed frames pending (jxg_pending > 0) serves them as a
  * pipeline lane: the one-at-a-time, batch, sharded-begin/end, homogeneity,
- * compare and reconstruct entry points return JXG_ERR_INVALID_ARG until they are
- * received.
+ * compare, reconstruct and decode entry points return JXG_ERR_INVALID_ARG until
+ * they are received.
  */
 #ifndef JXG_H_
 #define JXG_H_
@@ -349,11 +350,72 @@ jxg_status jxg_compare_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig
  * sample may differ by 1 where a value sits on a rounding boundary.
  * JXG_ERR_INVALID_ARG: null arguments, a stride too small, no frame encoded
  * yet, streamed frames pending, or the context's last encode was not a
- * one-at-a-time encode -- reconstruction of batch, streamed and sharded
- * frames (and of jxg_warmup's synthetic frame) is out of scope: their
- * coefficients live in pipeline lanes or on other ranks. */
+ * one-at-a-time encode (or a decode has used the context's buffers since) --
+ * the coefficients of batch, streamed and sharded frames (and of jxg_warmup's
+ * synthetic frame) live in pipeline lanes or on other ranks: their decoded
+ * pixels come from their codestream, through jxg_decode_rgb8 below. */
 jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride);
 jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_stride);
+
+/* ---- decoder: codestream -> decoded pixels ----
+ * Reads exactly what this encoder writes (one-at-a-time, batch, streamed and
+ * sharded frames alike): bare codestream, SizeHeader, all-default
+ * ImageMetadata, one regular VarDCT frame of one pass with the default LF
+ * dequantization / block context map / colour correlation / coefficient
+ * orders, Gaborish on or off and 0-3 EPF iterations without custom weights,
+ * an unpermuted TOC in either section layout, modular LF groups with local MA
+ * trees, prefix-code or 12-bit rANS entropy streams without LZ77, and
+ * num_hf_presets >= 1 (sharded ANS streams carry one per rank).  Any other
+ * stream returns JXG_ERR_UNSUPPORTED, never a wrong image; a malformed one
+ * (truncated, sizes that do not add up, a symbol outside its alphabet, a
+ * non-zero count too large or not exhausted, overlapping varblocks, a wrong
+ * ANS final state) returns JXG_ERR_INVALID_ARG.  Headers, TOC, LfGlobal,
+ * HfGlobal, the decode tables and the LF groups' streams (one task per LF
+ * group, at most 8 helper threads) are decoded on the host; the pass groups
+ * -- all AC tokens -- on the GPU, one wave per group (csrc/jxg_decode.hip);
+ * the pixels by the reconstruction kernels of jxg_reconstruct_rgb8
+ * (DESIGN.md 3.12). */
+typedef struct {
+  uint32_t xsize, ysize, num_groups, num_lf_groups;
+  uint32_t global_scale, quant_dc, num_hf_presets;
+  uint32_t ans;          /* 1: rANS, 0: prefix codes (the AC stream) */
+  uint32_t gaborish, epf_iters;
+} jxg_stream_info;
+
+/* host only, no context: headers + TOC + LfGlobal / HfGlobal heads (a frame of
+ * one pass group keeps everything in one section, so its LF group is decoded
+ * on the way).  JXG_ERR_INVALID_ARG for null arguments or size == 0. */
+jxg_status jxg_decode_info(const uint8_t* data, size_t size, jxg_stream_info* info);
+
+/* codestream (host memory) -> decoded RGB8, on the GPU.  rgb / d_rgb as for
+ * jxg_reconstruct_rgb8: xsize x ysize interleaved, row_stride >= 3 * xsize, of
+ * which only the first 3 * xsize bytes of a row are written; both calls return
+ * when the image is complete.  The context's distance / effort / flags play no
+ * part.  The decode uses the context's coefficient and map buffers (allocated
+ * or grown on first use, like the reconstruction planes), so afterwards
+ * jxg_reconstruct_rgb8 returns JXG_ERR_INVALID_ARG until the next one-at-a-time
+ * encode; encodes are not affected.  JXG_ERR_INVALID_ARG: null data / rgb,
+ * size == 0, a stride under 3 * xsize, or streamed frames pending. */
+jxg_status jxg_decode_rgb8(jxg_ctx* ctx, const uint8_t* data, size_t size,
+                           uint8_t* rgb, size_t row_stride);
+jxg_status jxg_decode_rgb8_device(jxg_ctx* ctx, const uint8_t* data, size_t size,
+                                  void* d_rgb, size_t row_stride);
+
+/* the decoded maps in jxg_stats' layouts: acs [blocks] raw strategy, qf [blocks]
+ * raw - 1, dc [3][blocks], ac [blocks][3][64], cmap [2][tiles] of int8 chroma
+ * from luma factors per 64 x 64 tile (any may be NULL).
+ * ctx == NULL: the host path of the same decode core, no device touched;
+ * else the pass groups are decoded on the GPU and the maps downloaded (not
+ * while streamed frames are pending). */
+jxg_status jxg_decode_maps(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8_t* acs,
+                           uint8_t* qf, int32_t* dc, int32_t* ac, int8_t* cmap);
+
+/* milliseconds of the context's last jxg_decode_rgb8[_device]: ms[0] host parse
+ * of headers / TOC / LfGlobal / HfGlobal and the decode tables, ms[1] the LF
+ * groups on the host threads, ms[2] the pass-group kernel and ms[3] the
+ * reconstruction chain (device time by events), ms[4] the whole call (host
+ * wall clock) */
+jxg_status jxg_decode_timings(jxg_ctx* ctx, float* ms /* [5] */);
 
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result

@@ -1,0 +1,170 @@
+// jxg_djxl -- djxl-argv-compatible decoder over the C ABI: the counterpart of
+// jxg_cjxl for the harness's decode step (the legacy old_test_jxl.py shells
+// out to `djxl IN.jxl OUT.png`).
+//
+//   jxg_djxl IN.jxl OUT.{ppm,png} [--device=N]
+//
+// .ppm writes a binary P6, .png an 8-bit RGB PNG (filter type 0, zlib level 1;
+// jxg_cjxl's own PNG reader reads it back).  Exit 0 on success; on failure
+// exit 1 with one line on stderr: jxg_status_str of the status, or the I/O
+// error.
+#include <zlib.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/jxg.h"
+
+namespace {
+
+void put_be32(std::vector<uint8_t>& o, uint32_t v) {
+  for (int s = 24; s >= 0; s -= 8) o.push_back((uint8_t)(v >> s));
+}
+
+void put_chunk(std::vector<uint8_t>& o, const char* type, const uint8_t* body, size_t len) {
+  put_be32(o, (uint32_t)len);
+  const size_t at = o.size();
+  o.insert(o.end(), type, type + 4);
+  o.insert(o.end(), body, body + len);
+  put_be32(o, (uint32_t)crc32(0L, o.data() + at, (uInt)(4 + len)));
+}
+
+bool encode_png(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, std::vector<uint8_t>& out) {
+  static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+  out.assign(sig, sig + 8);
+  std::vector<uint8_t> ihdr;
+  put_be32(ihdr, w);
+  put_be32(ihdr, h);
+  const uint8_t tail[5] = {8, 2, 0, 0, 0};  // 8-bit RGB, deflate, adaptive filtering, no interlace
+  ihdr.insert(ihdr.end(), tail, tail + 5);
+  put_chunk(out, "IHDR", ihdr.data(), ihdr.size());
+  const size_t row = (size_t)w * 3;
+  std::vector<uint8_t> raw((row + 1) * h);
+  for (uint32_t y = 0; y < h; y++) {
+    raw[(row + 1) * y] = 0;  // filter type None
+    std::memcpy(&raw[(row + 1) * y + 1], &rgb[row * y], row);
+  }
+  z_stream zs{};
+  if (deflateInit(&zs, 1) != Z_OK) return false;
+  std::vector<uint8_t> buf((size_t)1 << 20);
+  zs.next_in = raw.data();
+  size_t left = raw.size();
+  int zr = Z_OK;
+  while (zr != Z_STREAM_END) {
+    const size_t piece = left < ((size_t)1 << 30) ? left : ((size_t)1 << 30);
+    zs.avail_in = (uInt)piece;
+    left -= piece;
+    do {
+      zs.next_out = buf.data();
+      zs.avail_out = (uInt)buf.size();
+      zr = deflate(&zs, left ? Z_NO_FLUSH : Z_FINISH);
+      if (zr == Z_STREAM_ERROR) {
+        deflateEnd(&zs);
+        return false;
+      }
+      const size_t n = buf.size() - zs.avail_out;
+      if (n) put_chunk(out, "IDAT", buf.data(), n);
+    } while (zs.avail_out == 0 && zr != Z_STREAM_END);
+  }
+  deflateEnd(&zs);
+  put_chunk(out, "IEND", nullptr, 0);
+  return true;
+}
+
+bool ends_with(const std::string& s, const char* suffix) {
+  const size_t n = std::strlen(suffix);
+  if (s.size() < n) return false;
+  for (size_t i = 0; i < n; i++) {
+    char c = s[s.size() - n + i];
+    if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+    if (c != suffix[i]) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  int device = 0;
+  std::vector<const char*> pos;
+  for (int i = 1; i < argc; i++) {
+    if (!std::strncmp(argv[i], "--device=", 9))
+      device = std::atoi(argv[i] + 9);
+    else if (!std::strncmp(argv[i], "--", 2))
+      continue;  // djxl options that do not change the pixels of an 8-bit decode
+    else
+      pos.push_back(argv[i]);
+  }
+  if (pos.size() != 2) {
+    std::fprintf(stderr, "usage: jxg_djxl IN.jxl OUT.{ppm,png} [--device=N]\n");
+    return 1;
+  }
+  const std::string out_path = pos[1];
+  const bool png = ends_with(out_path, ".png");
+  if (!png && !ends_with(out_path, ".ppm")) {
+    std::fprintf(stderr, "%s: output must be .ppm or .png\n", pos[1]);
+    return 1;
+  }
+  std::vector<uint8_t> data;
+  {
+    FILE* f = std::fopen(pos[0], "rb");
+    if (!f) {
+      std::fprintf(stderr, "cannot read %s\n", pos[0]);
+      return 1;
+    }
+    uint8_t buf[1 << 16];
+    size_t n;
+    while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) data.insert(data.end(), buf, buf + n);
+    std::fclose(f);
+  }
+  jxg_stream_info info{};
+  jxg_status st = data.empty() ? JXG_ERR_INVALID_ARG : jxg_decode_info(data.data(), data.size(), &info);
+  if (st != JXG_OK) {
+    std::fprintf(stderr, "%s: %s\n", pos[0], jxg_status_str(st));
+    return 1;
+  }
+  jxg_params p{};
+  p.distance = 1.0f;
+  p.effort = 7;
+  p.num_devices = 1;
+  p.device = device;
+  jxg_ctx* ctx = nullptr;
+  st = jxg_create(&p, &ctx);
+  if (st != JXG_OK) {
+    std::fprintf(stderr, "jxg_create: %s\n", jxg_status_str(st));
+    return 1;
+  }
+  std::vector<uint8_t> rgb((size_t)info.xsize * info.ysize * 3);
+  st = jxg_decode_rgb8(ctx, data.data(), data.size(), rgb.data(), (size_t)info.xsize * 3);
+  jxg_destroy(ctx);
+  if (st != JXG_OK) {
+    std::fprintf(stderr, "%s: %s\n", pos[0], jxg_status_str(st));
+    return 1;
+  }
+  std::vector<uint8_t> file;
+  if (png) {
+    if (!encode_png(rgb, info.xsize, info.ysize, file)) {
+      std::fprintf(stderr, "PNG deflate failed\n");
+      return 1;
+    }
+  } else {
+    char head[64];
+    const int n = std::snprintf(head, sizeof(head), "P6\n%u %u\n255\n", info.xsize, info.ysize);
+    file.assign(head, head + n);
+    file.insert(file.end(), rgb.begin(), rgb.end());
+  }
+  FILE* f = std::fopen(pos[1], "wb");
+  const bool wr = f && std::fwrite(file.data(), 1, file.size(), f) == file.size();
+  if (f && std::fclose(f) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", pos[1]);
+    return 1;
+  }
+  if (!wr) {
+    std::fprintf(stderr, "cannot write %s\n", pos[1]);
+    return 1;
+  }
+  return 0;
+}

@@ -30,6 +30,7 @@
 
 #include "../../include/jxg.h"
 #include "jxg_bitstream.h"
+#include "jxg_decode.h"
 #include "jxg_device.h"
 #include "jxg_kernels.h"
 #include "jxg_helpers.h"
@@ -208,6 +209,19 @@ struct Frame {
   float dc_mul[3], dc_step[3];
 };
 
+// global scale and DC quantizer -> the dequantization steps (the encoder takes
+// the two from the distance, the decoder from LfGlobal)
+static void set_frame_scales(Frame& f, uint32_t G, uint32_t qdc) {
+  f.G = G;
+  f.inv_g = (float)(65536.0 / (double)G);
+  f.qdc = qdc;
+  const double m_lf[3] = {1.0 / 4096.0, 1.0 / 512.0, 1.0 / 256.0};
+  for (int c = 0; c < 3; c++) {
+    f.dc_mul[c] = (float)((double)G * (double)qdc / 65536.0 / m_lf[c]);
+    f.dc_step[c] = (float)(65536.0 / (double)G / (double)qdc * m_lf[c]);
+  }
+}
+
 static Frame make_frame(uint32_t w, uint32_t h, float distance) {
   Frame f{};
   f.w = w;
@@ -229,8 +243,6 @@ static Frame make_frame(uint32_t w, uint32_t h, float distance) {
   f.qf_base = (float)qfb;
   long G = (long)std::floor(qfb * 1024.0 + 0.5);
   G = std::min<long>(std::max<long>(G, 1), 73727);
-  f.G = (uint32_t)G;
-  f.inv_g = (float)(65536.0 / (double)G);
   double t = 0.3 * std::pow(d / 0.3, 0.66);
   if (t > d) t = d;
   if (t < 0.5 * d) t = 0.5 * d;
@@ -238,12 +250,7 @@ static Frame make_frame(uint32_t w, uint32_t h, float distance) {
   if (qdc_f > 50.0) qdc_f = 50.0;
   long qdc = (long)std::floor(qdc_f * 65536.0 / (double)G + 0.5);
   qdc = std::min<long>(std::max<long>(qdc, 1), 65536);
-  f.qdc = (uint32_t)qdc;
-  const double m_lf[3] = {1.0 / 4096.0, 1.0 / 512.0, 1.0 / 256.0};
-  for (int c = 0; c < 3; c++) {
-    f.dc_mul[c] = (float)((double)G * (double)qdc / 65536.0 / m_lf[c]);
-    f.dc_step[c] = (float)(65536.0 / (double)G / (double)qdc * m_lf[c]);
-  }
+  set_frame_scales(f, (uint32_t)G, (uint32_t)qdc);
   return f;
 }
 
@@ -327,6 +334,16 @@ struct Ctx {
   // whose coefficients and maps are still in this context's buffers
   bool recon_ok = false;
   uint32_t recon_w = 0, recon_h = 0;
+  // decoder (jxg_decode_rgb8), allocated by its first call: the codestream's
+  // words, the pass groups' section bounds, the AC stream's decode tables
+  // [ctxmap | histograms | prefix or alias tables], the per-group status
+  DevBuf<uint64_t> dec_stream, dec_sec;
+  DevBuf<uint8_t> dec_tab;
+  DevBuf<uint32_t> dec_status;
+  hipEvent_t dec_ev[3] = {};  // pass-group kernel start / end, reconstruction end
+  // last decode: host parse + tables, LF groups, pass-group kernel,
+  // reconstruction chain (device), the whole call (host wall); milliseconds
+  float dec_ms[5] = {};
   DevBuf<ConcatPiece> pieces, pieces_ac;
   DevBuf<uint8_t> cat;  // stage_concat: [pieces | chunk words], one upload
   PinBuf<uint8_t> h_cat;
@@ -2801,6 +2818,8 @@ void jxg_destroy(jxg_ctx* ctx) {
 #endif
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->dec_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_write) (void)hipEventDestroy(c->ev_write);
   if (c->stream && !c->shared_stream) (void)hipStreamDestroy(c->stream);
@@ -3307,10 +3326,26 @@ jxg_status jxg_compare_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_strid
 // coefficient and map buffers (read only): tile transform kernel (+ the
 // 128 / 256 px varblocks at effort >= 8), Gaborish and EPF passes as the frame
 // header signals them; the last kernel of the chain writes RGB8.
-static jxg_status reconstruct_device(Ctx* c, uint8_t* d_rgb, size_t stride) {
-  hipStream_t s = c->stream;
+// the frame constants of a reconstruction: the encoder fills them from its
+// parameters, the decoder from the parsed headers
+struct ReconFrame {
+  uint32_t w, h;
+  uint32_t global_scale, quant_dc;
+  uint32_t lf;        // loop-filter code (lf_code: bit 0 Gaborish, bits 1-2 EPF iterations)
+  float xmul, bmul;   // x_qm / b_qm multipliers
+  bool maybe_big;     // varblocks of 128 / 256 px are possible
+};
+static ReconFrame recon_frame_of_encode(const Ctx* c) {
   const jxg_params& P = c->params;
   const Frame f = make_frame(c->recon_w, c->recon_h, P.distance);
+  return ReconFrame{c->recon_w, c->recon_h, f.G, f.qdc, lf_code(P.flags, P.distance),
+                    1.0f, 1.0f, P.effort >= 8};
+}
+
+static jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride) {
+  hipStream_t s = c->stream;
+  Frame f = make_frame(R.w, R.h, 1.0f);
+  set_frame_scales(f, R.global_scale, R.quant_dc);
   if (!c->rc_tab.p || c->rc_tab_g != f.G) {
     const ReconTables T = build_recon_tables(f.G);
     JXG_HIP(c->rc_tab.ensure(T.tab.size()));
@@ -3322,10 +3357,10 @@ static jxg_status reconstruct_device(Ctx* c, uint8_t* d_rgb, size_t stride) {
   }
   const size_t plane = (size_t)f.xp * f.yp;
   const uint32_t ntiles = f.tiles_x * f.tiles_y;
-  const uint32_t lf = lf_code(P.flags, P.distance);
+  const uint32_t lf = R.lf;
   const bool gab = lf & 1u;
   const uint32_t epf = (lf >> 1) & 3u;
-  const bool big = P.effort >= 8;  // varblocks of 128 / 256 px are possible
+  const bool big = R.maybe_big;  // the tile kernel may list varblocks of 128 / 256 px
   int passes[4], np = 0;           // -1: Gaborish, else the EPF pass
   if (gab) passes[np++] = -1;
   if (epf >= 3) passes[np++] = 0;
@@ -3382,6 +3417,8 @@ static jxg_status reconstruct_device(Ctx* c, uint8_t* d_rgb, size_t stride) {
     a.cbias = (float)std::cbrt(bias);
     a.obias = (float)bias;
   }
+  a.xmul = R.xmul;
+  a.bmul = R.bmul;
   JXG_HIP(launch_recon_tiles(a, to_rgb, s));
   if (big) {
     uint32_t nbig = 0;
@@ -3411,7 +3448,7 @@ jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_str
     return JXG_ERR_INVALID_ARG;
   const jxg_status st = order_input(c, c);  // the caller's earlier use of d_rgb
   if (st) return st;
-  return reconstruct_device(c, static_cast<uint8_t*>(d_rgb), row_stride);
+  return reconstruct_device(c, recon_frame_of_encode(c), static_cast<uint8_t*>(d_rgb), row_stride);
 }
 
 jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride) {
@@ -3422,11 +3459,233 @@ jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride) {
     return JXG_ERR_INVALID_ARG;
   const size_t row = (size_t)c->recon_w * 3;
   JXG_HIP(c->rc_rgb.ensure(row * c->recon_h));
-  const jxg_status st = reconstruct_device(c, c->rc_rgb.p, row);
+  const jxg_status st = reconstruct_device(c, recon_frame_of_encode(c), c->rc_rgb.p, row);
   if (st) return st;
   JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc_rgb.p, row, row, c->recon_h,
                            hipMemcpyDeviceToHost, c->stream));
   JXG_HIP(hipStreamSynchronize(c->stream));
+  return JXG_OK;
+}
+
+// ---- decoder (jxg_decode.cpp / jxg_decode.hip) ----
+// Host: headers, TOC, LfGlobal, LF groups (helper threads), HfGlobal, decode
+// tables.  Device: the maps are uploaded into the context's own acs / qf / dc /
+// cmap buffers, the pass-group kernel fills ac, and the reconstruction chain
+// above turns them into pixels.  The last encode can no longer be
+// reconstructed from those buffers.
+// F: the parsed stream (decode_parse with its LF groups); nothing of the
+// context is touched before the caller has checked its arguments against it
+static jxg_status decode_to_device(Ctx* c, const DecFrame* F) {
+  hipStream_t s = c->stream;
+  c->recon_ok = false;
+  const size_t nb = (size_t)F->bxs * F->bys;
+  const size_t ntiles = (size_t)F->tiles_x * F->tiles_y;
+  const uint32_t ng = F->info.num_groups;
+  JXG_HIP(c->acs.ensure(nb));
+  JXG_HIP(c->qf.ensure(nb));
+  JXG_HIP(c->dc.ensure(nb * 3));
+  JXG_HIP(c->ac.ensure(nb * 192));
+  JXG_HIP(c->cmap.ensure(ntiles * 2));
+  JXG_HIP(c->dec_stream.ensure(F->words.size()));
+  JXG_HIP(c->dec_sec.ensure(F->sec.size()));
+  JXG_HIP(c->dec_status.ensure(ng));
+  // decode tables, one upload: [hist | atab or ptab | ctxmap], 8-byte aligned parts
+  const DecEntropy& E = F->hf;
+  const size_t b_hist = E.hist.size() * sizeof(dec::HistDesc);
+  const size_t b_atab = E.atab.size() * sizeof(dec::AnsEntry);
+  const size_t b_ptab = E.ptab.size() * sizeof(uint16_t);
+  const size_t o_atab = (b_hist + 7) & ~(size_t)7, o_ptab = (o_atab + b_atab + 7) & ~(size_t)7;
+  const size_t o_map = (o_ptab + b_ptab + 7) & ~(size_t)7;
+  std::vector<uint8_t> blob(o_map + E.ctxmap.size(), 0);
+  std::memcpy(blob.data(), E.hist.data(), b_hist);
+  if (b_atab) std::memcpy(blob.data() + o_atab, E.atab.data(), b_atab);
+  if (b_ptab) std::memcpy(blob.data() + o_ptab, E.ptab.data(), b_ptab);
+  std::memcpy(blob.data() + o_map, E.ctxmap.data(), E.ctxmap.size());
+  JXG_HIP(c->dec_tab.ensure(blob.size()));
+  for (hipEvent_t& e : c->dec_ev)
+    if (!e && make_event(&e, hipEventDefault) != hipSuccess) return JXG_ERR_HIP;
+  JXG_HIP(hipMemcpyAsync(c->acs.p, F->acs.data(), nb, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->qf.p, F->qf.data(), nb, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->dc.p, F->dc.data(), nb * 12, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->cmap.p, F->cmap.data(), ntiles * 2, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->dec_stream.p, F->words.data(), F->words.size() * 8,
+                         hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->dec_sec.p, F->sec.data(), F->sec.size() * 8, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpyAsync(c->dec_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+  DecodeArgs a{};
+  a.stream = c->dec_stream.p;
+  a.sec = c->dec_sec.p;
+  a.sym.hist = reinterpret_cast<const dec::HistDesc*>(c->dec_tab.p);
+  a.sym.atab = reinterpret_cast<const dec::AnsEntry*>(c->dec_tab.p + o_atab);
+  a.sym.ptab = reinterpret_cast<const uint16_t*>(c->dec_tab.p + o_ptab);
+  a.sym.ctxmap = c->dec_tab.p + o_map;
+  a.sym.nctx = (uint32_t)E.ctxmap.size();
+  a.sym.prefix = E.prefix;
+  a.sym.log_alpha = E.log_alpha;
+  a.npresets = F->info.num_hf_presets;
+  a.preset_bits = F->preset_bits;
+  a.acs = c->acs.p;
+  a.ac = c->ac.p;
+  a.status = c->dec_status.p;
+  a.bxs = F->bxs;
+  a.bys = F->bys;
+  a.gxs = F->gxs;
+  a.nhist = (uint32_t)E.hist.size();
+  a.tab_bytes = (uint32_t)(E.prefix ? b_ptab : b_atab);
+  JXG_HIP(hipEventRecord(c->dec_ev[0], s));
+  JXG_HIP(launch_decode_groups(a, ng, s));
+  JXG_HIP(hipEventRecord(c->dec_ev[1], s));
+  std::vector<uint32_t> status(ng, 0);
+  JXG_HIP(hipMemcpyAsync(status.data(), c->dec_status.p, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+  JXG_HIP(hipStreamSynchronize(s));  // (also: the uploads' host vectors may go)
+  for (uint32_t g = 0; g < ng; g++)
+    if (status[g]) return status[g] == (uint32_t)dec::kUnsupported ? JXG_ERR_UNSUPPORTED : JXG_ERR_INVALID_ARG;
+  float ms = 0.0f;
+  (void)hipEventElapsedTime(&ms, c->dec_ev[0], c->dec_ev[1]);
+  c->dec_ms[0] = F->ms_head;
+  c->dec_ms[1] = F->ms_lf;
+  c->dec_ms[2] = ms;
+  c->dec_ms[3] = 0.0f;
+  return JXG_OK;
+}
+
+// what the reconstruction tables cannot honour is refused: a 128 / 256 px
+// varblock whose quant table is not the one this encoder writes in DCT mode,
+// x_qm / b_qm scales outside the header's range
+static jxg_status decode_recon_frame(const DecFrame& F, ReconFrame* R) {
+  for (int k = 0; k < 4; k++) {
+    const bool present = F.qm_mask >> k & 1u;
+    if (present && !dequant_params_match(k, F.qm_bits[k])) return JXG_ERR_UNSUPPORTED;
+    if ((F.big_used >> k & 1u) && !present) return JXG_ERR_UNSUPPORTED;
+  }
+  if (F.info.global_scale == 0 || F.info.quant_dc == 0) return JXG_ERR_INVALID_ARG;
+  R->w = F.info.xsize;
+  R->h = F.info.ysize;
+  R->global_scale = F.info.global_scale;
+  R->quant_dc = F.info.quant_dc;
+  R->lf = (F.info.gaborish ? 1u : 0u) | F.info.epf_iters << 1;
+  R->xmul = (float)std::pow(1.25, 2.0 - (double)F.x_qm);
+  R->bmul = (float)std::pow(1.25, 2.0 - (double)F.b_qm);
+  R->maybe_big = F.big_used != 0;
+  return JXG_OK;
+}
+
+// tight: into the context's own image (rows of 3 * xsize bytes), for the host
+// variant, whose stride `row_stride` is still checked
+static jxg_status decode_rgb8_device(Ctx* c, const uint8_t* data, size_t size, uint8_t* d_rgb,
+                                     size_t row_stride, bool tight, uint32_t* w, uint32_t* h) {
+  const Clock::time_point t0 = Clock::now();
+  DecFrame F;
+  jxg_status st = (jxg_status)decode_parse(data, size, true, &F);
+  if (st) return st;
+  if (row_stride < (size_t)F.info.xsize * 3) return JXG_ERR_INVALID_ARG;
+  ReconFrame R{};
+  st = decode_recon_frame(F, &R);
+  if (st) return st;
+  st = decode_to_device(c, &F);
+  if (st) return st;
+  *w = R.w;
+  *h = R.h;
+  if (tight) {
+    row_stride = (size_t)R.w * 3;
+    JXG_HIP(c->rc_rgb.ensure(row_stride * R.h));
+    d_rgb = c->rc_rgb.p;
+  }
+  st = reconstruct_device(c, R, d_rgb, row_stride);
+  if (st) return st;
+  JXG_HIP(hipEventRecord(c->dec_ev[2], c->stream));
+  JXG_HIP(hipStreamSynchronize(c->stream));
+  (void)hipEventElapsedTime(&c->dec_ms[3], c->dec_ev[1], c->dec_ev[2]);
+  c->dec_ms[4] = ms_since(t0);
+  return JXG_OK;
+}
+
+jxg_status jxg_decode_rgb8_device(jxg_ctx* ctx, const uint8_t* data, size_t size, void* d_rgb,
+                                  size_t row_stride) {
+  if (!ctx || !data || !d_rgb || size == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  const jxg_status st = order_input(c, c);  // the caller's earlier use of d_rgb
+  if (st) return st;
+  uint32_t w = 0, h = 0;
+  try {
+    return decode_rgb8_device(c, data, size, static_cast<uint8_t*>(d_rgb), row_stride, false, &w,
+                              &h);
+  } catch (const std::bad_alloc&) {
+    return JXG_ERR_OOM;
+  } catch (...) {
+    return JXG_ERR_INTERNAL;
+  }
+}
+
+jxg_status jxg_decode_rgb8(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8_t* rgb,
+                           size_t row_stride) {
+  if (!ctx || !data || !rgb || size == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  uint32_t w = 0, h = 0;
+  jxg_status st;
+  try {
+    st = decode_rgb8_device(c, data, size, nullptr, row_stride, true, &w, &h);
+  } catch (const std::bad_alloc&) {
+    st = JXG_ERR_OOM;
+  } catch (...) {
+    st = JXG_ERR_INTERNAL;
+  }
+  if (st) return st;
+  const size_t row = (size_t)w * 3;
+  JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc_rgb.p, row, row, h,
+                           hipMemcpyDeviceToHost, c->stream));
+  JXG_HIP(hipStreamSynchronize(c->stream));
+  return JXG_OK;
+}
+
+static jxg_status decode_maps_device(Ctx* c, const uint8_t* data, size_t size, uint8_t* acs,
+                                     uint8_t* qf, int32_t* dc, int32_t* ac, int8_t* cmap);
+
+jxg_status jxg_decode_maps(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8_t* acs,
+                           uint8_t* qf, int32_t* dc, int32_t* ac, int8_t* cmap) {
+  if (!data || size == 0) return JXG_ERR_INVALID_ARG;
+  if (!ctx) return (jxg_status)decode_maps_host(data, size, acs, qf, dc, ac, cmap);
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice(c->params.device) != hipSuccess) return JXG_ERR_HIP;
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  try {
+    return decode_maps_device(c, data, size, acs, qf, dc, ac, cmap);
+  } catch (const std::bad_alloc&) {
+    return JXG_ERR_OOM;
+  } catch (...) {
+    return JXG_ERR_INTERNAL;
+  }
+}
+
+static jxg_status decode_maps_device(Ctx* c, const uint8_t* data, size_t size, uint8_t* acs,
+                                     uint8_t* qf, int32_t* dc, int32_t* ac, int8_t* cmap) {
+  DecFrame F;
+  jxg_status st = (jxg_status)decode_parse(data, size, true, &F);
+  if (st) return st;
+  st = decode_to_device(c, &F);
+  if (st) return st;
+  const size_t nb = (size_t)F.bxs * F.bys;
+  if (acs) std::memcpy(acs, F.acs.data(), nb);
+  if (qf) std::memcpy(qf, F.qf.data(), nb);
+  if (dc) std::memcpy(dc, F.dc.data(), nb * 12);
+  if (cmap) std::memcpy(cmap, F.cmap.data(), F.cmap.size());
+  if (ac) {
+    std::vector<int16_t> ac16(nb * 192);
+    JXG_HIP(hipMemcpyAsync(ac16.data(), c->ac.p, nb * 192 * 2, hipMemcpyDeviceToHost, c->stream));
+    JXG_HIP(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < nb * 192; i++) ac[i] = ac16[i];
+  }
+  return JXG_OK;
+}
+
+jxg_status jxg_decode_timings(jxg_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return JXG_ERR_INVALID_ARG;
+  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+  for (int i = 0; i < 5; i++) ms[i] = c->dec_ms[i];
   return JXG_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "jxg_decode_core.h"
+
 namespace jxg {
 
 // Batched launches (the streaming pipeline's super-frames): up
@@ -358,6 +360,7 @@ struct ReconArgs {
   uint8_t* rgb;         // RGB8 out
   size_t stride;
   float cbias, obias;   // cbrt(opsin bias), opsin bias
+  float xmul, bmul;     // frame header x_qm / b_qm: 1.25^(2 - scale), 1 for this encoder
   float cm[9];          // inverse opsin matrix, row-major
 };
 // the 64x64 tiles' varblocks (<= 64 px); to_rgb: no filter follows, RGB8 is written
@@ -370,6 +373,28 @@ hipError_t launch_recon_gab(const ReconArgs& a, const float* src, float* dst, bo
 hipError_t launch_recon_epf(const ReconArgs& a, int pass, const float* src, float* dst, bool last,
                             hipStream_t s);
 hipError_t launch_recon_colour(const ReconArgs& a, const float* src, hipStream_t s);
+// the decoder's pass groups (jxg_decode.hip): one wave per
+// group walks its section of the codestream with the decode core and writes
+// the non-zero coefficients into `ac` (it zeroes the group's area first)
+struct DecodeArgs {
+  const uint64_t* stream;  // the codestream as 64-bit words, zero padded
+  const uint64_t* sec;     // [ngroups][2] first / end bit of every pass group
+  dec::SymReader sym;      // the AC stream's decode tables (device pointers)
+  uint32_t npresets, preset_bits;
+  const uint8_t* acs;      // [nb] decoded strategy map
+  int16_t* ac;             // [nb][3][64] out
+  uint32_t* status;        // [ngroups] out: 0 or a dec::k* code
+  uint32_t bxs, bys, gxs;
+  // LDS staging of the decode tables (every token reads a context-map byte, a
+  // histogram descriptor and a table entry, each depending on the one before):
+  // the group's preset's slice of the context map and the descriptors always,
+  // the symbol tables (tab_bytes of alias entries or prefix table words) when
+  // they fit (stage_tab)
+  uint32_t nhist, tab_bytes, stage_tab;
+};
+// the kernel's dynamic LDS for these arguments; sets stage_tab
+uint32_t decode_groups_lds(DecodeArgs* a);
+hipError_t launch_decode_groups(const DecodeArgs& a, uint32_t ngroups, hipStream_t s);
 // synthetic benchmark input (jxg_synth.hip): RGB8 rows of `stride` bytes
 hipError_t launch_synth(uint8_t* out, uint32_t w, uint32_t h, size_t stride, uint64_t seed,
                         hipStream_t s);

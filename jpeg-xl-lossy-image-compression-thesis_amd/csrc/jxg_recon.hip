@@ -149,8 +149,8 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     const float sc = a.inv_g / (float)((int)a.qf[gh] + 1);
     const int16_t* q = a.ac + gb * 192 + k;
     const float vy = (rc_adjust(q[64], a.bias[1], a.bias[3]) * wy) * sc;
-    const float vx = (rc_adjust(q[0], a.bias[0], a.bias[3]) * wx) * sc + cfx * vy;
-    const float vb = (rc_adjust(q[128], a.bias[2], a.bias[3]) * wb) * sc + cfb * vy;
+    const float vx = ((rc_adjust(q[0], a.bias[0], a.bias[3]) * wx) * sc) * a.xmul + cfx * vy;
+    const float vb = ((rc_adjust(q[128], a.bias[2], a.bias[3]) * wb) * sc) * a.bmul + cfb * vy;
     const int o = (hy * 8 + ky) * kRS + hx * 8 + kx;
     sC[o] = vx;
     sC[kRP + o] = vy;
@@ -370,8 +370,9 @@ __global__ __launch_bounds__(kRB) void recon_big_kernel(ReconArgs a) {
     const float* iw = tab + kRcTabIw + c_rc_koff[kind] + p;
     const int16_t* q = a.ac + gb * 192 + k;
     const float vy = (rc_adjust(q[64], a.bias[1], a.bias[3]) * iw[kRcKindOff[10]]) * sc;
-    const float vx = (rc_adjust(q[0], a.bias[0], a.bias[3]) * iw[0]) * sc + cfx * vy;
-    const float vb = (rc_adjust(q[128], a.bias[2], a.bias[3]) * iw[2 * kRcKindOff[10]]) * sc + cfb * vy;
+    const float vx = ((rc_adjust(q[0], a.bias[0], a.bias[3]) * iw[0]) * sc) * a.xmul + cfx * vy;
+    const float vb = ((rc_adjust(q[128], a.bias[2], a.bias[3]) * iw[2 * kRcKindOff[10]]) * sc) * a.bmul +
+                     cfb * vy;
     const size_t o = org + (size_t)ky * a.xp + kx;
     a.pa[o] = vx;
     a.pa[plane + o] = vy;

@@ -330,6 +330,15 @@ void write_dequant_matrices(BitWriter& w, uint32_t mask) {
   }
 }
 
+bool dequant_params_match(int k, const uint16_t* bits) {
+  for (int c = 0; c < 3; c++)
+    for (int i = 0; i < 8; i++) {
+      const double v = big_param(k, c, i);
+      if (bits[c * 8 + i] != f16_bits(i ? v : v / 64.0)) return false;
+    }
+  return true;
+}
+
 BigTables build_big_tables() {
   static const int kDims[4][2] = {{64, 128}, {128, 128}, {128, 256}, {256, 256}};
   BigTables T;

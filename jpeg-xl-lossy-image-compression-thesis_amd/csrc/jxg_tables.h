@@ -46,6 +46,10 @@ ReconTables build_recon_tables(uint32_t global_scale);
 // so no decoder default is involved for them
 class BitWriter;
 void write_dequant_matrices(BitWriter& w, uint32_t mask);
+// whether bits[channel][band] (binary16 words of a DCT-mode table as the
+// stream carries them) are the parameters write_dequant_matrices writes for
+// big kind k -- the ones build_recon_tables reconstructs with (the decoder)
+bool dequant_params_match(int k, const uint16_t* bits /* [3][8] */);
 // the binary16 value nearest v (ties to even) and its bits (== oracle/merge.c)
 double f16_round(double v);
 uint32_t f16_bits(double v);

@@ -27,6 +27,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JXG_LIB_PATH") or os.path.join(HERE, "libjxg.so")  # override: experiments only
 CLI_PATH = os.path.join(HERE, "jxg_cjxl")
+DJXL_PATH = os.path.join(HERE, "jxg_djxl")
 
 PROPOSAL_P = 1
 PROPOSAL_F = 2
@@ -77,6 +78,12 @@ class _Stats(ctypes.Structure):
                 ("ms_front_kernel", ctypes.c_float), ("ms_aq", ctypes.c_float)]
 
 
+class _StreamInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in (
+        "xsize", "ysize", "num_groups", "num_lf_groups", "global_scale", "quant_dc",
+        "num_hf_presets", "ans", "gaborish", "epf_iters")]
+
+
 class _Quality(ctypes.Structure):
     _fields_ = [("sse", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("mse", ctypes.c_double),
                 ("psnr", ctypes.c_double), ("ssim", ctypes.c_double)]
@@ -95,6 +102,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_shard_submit_device", "jxg_shard_next_head", "jxg_shard_write_next",
            "jxg_shard_write_flush", "jxg_set_pipeline_lanes", "jxg_warmup",
            "jxg_reconstruct_rgb8", "jxg_reconstruct_rgb8_device",
+           "jxg_decode_info", "jxg_decode_rgb8", "jxg_decode_rgb8_device", "jxg_decode_maps",
+           "jxg_decode_timings",
 )
 
 _lib = None
@@ -170,6 +179,11 @@ def load():
     lib.jxg_warmup.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
     lib.jxg_reconstruct_rgb8.argtypes = [vp, vp, sz]
     lib.jxg_reconstruct_rgb8_device.argtypes = [vp, vp, sz]
+    lib.jxg_decode_info.argtypes = [vp, sz, ctypes.POINTER(_StreamInfo)]
+    lib.jxg_decode_rgb8.argtypes = [vp, vp, sz, vp, sz]
+    lib.jxg_decode_rgb8_device.argtypes = [vp, vp, sz, vp, sz]
+    lib.jxg_decode_maps.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.jxg_decode_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -270,6 +284,34 @@ class Encoder:
         w, _ = self._last_wh or (1, 1)
         _check(load().jxg_reconstruct_rgb8_device(self._ctx, ctypes.c_void_p(ptr),
                                                   row_stride or w * 3))
+
+    def decode(self, data: bytes) -> np.ndarray:
+        """Codestream bytes -> (H, W, 3) uint8, decoded on the GPU
+        (jxg_decode_rgb8): any codestream this encoder writes -- one-at-a-time,
+        batch, streamed or sharded.  The context's parameters play no part;
+        afterwards :meth:`reconstruct` raises until the next :meth:`encode`."""
+        data = bytes(data)
+        info = stream_info(data)
+        w, h = info["xsize"], info["ysize"]
+        out = np.empty((h, w, 3), dtype=np.uint8)
+        _check(load().jxg_decode_rgb8(self._ctx, data, len(data), out.ctypes.data, w * 3))
+        return out
+
+    def decode_device(self, data: bytes, ptr: int, row_stride: int | None = None) -> None:
+        """The same image written to a device pointer (rows of `row_stride`
+        bytes, default 3 * width); returns when it is complete."""
+        data = bytes(data)
+        if row_stride is None:
+            row_stride = stream_info(data)["xsize"] * 3
+        _check(load().jxg_decode_rgb8_device(self._ctx, data, len(data), ctypes.c_void_p(ptr),
+                                             row_stride))
+
+    def decode_timings(self) -> dict:
+        """Milliseconds of the last :meth:`decode` / :meth:`decode_device`
+        (jxg_decode_timings)."""
+        ms = (ctypes.c_float * 5)()
+        _check(load().jxg_decode_timings(self._ctx, ms))
+        return dict(zip(("ms_head", "ms_lf", "ms_groups", "ms_recon", "ms_call"), map(float, ms)))
 
     def encode_batch(self, frames) -> list:
         """Host frames of equal size, each (H, W, 3) uint8 -> list of codestream
@@ -525,6 +567,35 @@ class Encoder:
             self._ctx, ctypes.c_void_p(d_orig), orig_stride or width * 3, ctypes.c_void_p(d_comp),
             comp_stride or width * 3, width, height, 1 if ssim else 0, ctypes.byref(q)))
         return {"sse": q.sse, "samples": q.samples, "mse": q.mse, "psnr": q.psnr, "ssim": q.ssim}
+
+
+# ---------------------------------------------------------------------------
+# decoder (host side: no device needed without an encoder)
+# ---------------------------------------------------------------------------
+def stream_info(data: bytes) -> dict:
+    """jxg_decode_info: size, group counts, scales, HF presets, coder (ans 1 /
+    prefix codes 0) and loop filters of a codestream; host only."""
+    data = bytes(data)
+    info = _StreamInfo()
+    _check(load().jxg_decode_info(data, len(data), ctypes.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in _StreamInfo._fields_}
+
+
+def decode_maps(data: bytes, encoder: "Encoder | None" = None) -> dict:
+    """jxg_decode_maps: the decoded maps shaped like :meth:`Encoder.stats` --
+    acs and qf (H/8, W/8), dc (3, H/8, W/8), ac (H/8, W/8, 3, 64), cmap
+    (2, tiles down, tiles across).  Without an encoder everything is decoded
+    on the host; with one, the pass groups are decoded on its GPU."""
+    data = bytes(data)
+    info = stream_info(data)
+    bxs, bys = (info["xsize"] + 7) // 8, (info["ysize"] + 7) // 8
+    out = {"acs": np.zeros((bys, bxs), np.uint8), "qf": np.zeros((bys, bxs), np.uint8),
+           "dc": np.zeros((3, bys, bxs), np.int32), "ac": np.zeros((bys, bxs, 3, 64), np.int32),
+           "cmap": np.zeros((2, (bys + 7) // 8, (bxs + 7) // 8), np.int8)}
+    ctx = encoder._ctx if encoder is not None else None
+    _check(load().jxg_decode_maps(ctx, data, len(data), *[out[k].ctypes.data for k in
+                                                        ("acs", "qf", "dc", "ac", "cmap")]))
+    return out
 
 
 # ---------------------------------------------------------------------------

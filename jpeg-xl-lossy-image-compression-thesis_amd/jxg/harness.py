@@ -169,13 +169,20 @@ def compare_results(results_1: str, results_2: str):
 
 
 def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int,
-                    comp_name: str, comp_rgb: np.ndarray, comp_file_size: int,
+                    comp_name: str, comp_rgb, comp_file_size: int,
                     distance: float, effort: int, result_file: str | None = None,
-                    ssim: bool = True) -> ComparisonResult:
+                    ssim: bool = True, decode_with=None) -> ComparisonResult:
     """benchmark.rs:895-972 with the metrics on the GPU.  ``encoder`` is a
     jxg.Encoder (its context runs jxg_compare_rgb8); ``comp_rgb`` is the
-    decoded image (stock djxl where present, any decoder otherwise).  Raw
-    sizes are width * height * 3 (image_reader.rs:523-540, Rgb8)."""
+    decoded image (stock djxl where present, any decoder otherwise) -- or,
+    with ``decode_with`` (a jxg.Encoder, which may be ``encoder``), the
+    codestream bytes of the compressed file, which that context decodes on the
+    GPU (Encoder.decode, jxg_decode_rgb8): the reference harnesses' step of
+    decoding the file that was written (image_reader.rs:555-606 through
+    jpegxl-rs; ``djxl IN.jxl OUT.png``).  Raw sizes are width * height * 3
+    (image_reader.rs:523-540, Rgb8)."""
+    if decode_with is not None:
+        comp_rgb = decode_with.decode(comp_rgb)
     h, w = orig_rgb.shape[:2]
     raw = w * h * 3
     q = encoder.compare(orig_rgb, comp_rgb, ssim=ssim)

@@ -21,8 +21,8 @@ mkdir -p $T/x && ln -s $T/csrc $T/x/csrc && ln -s $T/include $T/include_ && true
 mkdir -p $T/r/pkg && mv $T/csrc $T/r/pkg/csrc && mv $T/include $T/r/include
 HF="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function"
 pids=()
-for f in $T/r/pkg/csrc/*.hip $(ls $T/r/pkg/csrc/*.cpp | grep -v jxg_cjxl); do
-  b=$(basename $f); /opt/rocm/bin/hipcc $HF -c $f -o $T/${b%.*}.o & pids+=($!)
+for f in $T/r/pkg/csrc/*.hip $(ls $T/r/pkg/csrc/*.cpp | grep -v -e jxg_cjxl -e jxg_djxl); do
+  b=$(basename $f); /opt/rocm/bin/hipcc $HF -c $f -o $T/$b.o & pids+=($!)
 done
 for p in ${pids[@]}; do wait $p; done
 mkdir -p $D/tools/ab

@@ -15,8 +15,8 @@ for FILE in $FILES; do
 done
 HIPFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function"
 pids=()
-for f in $T/p/csrc/*.hip $(ls $T/p/csrc/*.cpp | grep -v jxg_cjxl); do
-  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $T/${b%.*}.o & pids+=($!)
+for f in $T/p/csrc/*.hip $(ls $T/p/csrc/*.cpp | grep -v -e jxg_cjxl -e jxg_djxl); do
+  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $T/$b.o & pids+=($!)
 done
 for p in ${pids[@]}; do wait $p; done
 mkdir -p $D/tools/var

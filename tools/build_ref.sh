@@ -11,8 +11,8 @@ P=$T/jpeg-xl-lossy-image-compression-thesis_amd
 for f in "$@"; do cp $D/jpeg-xl-lossy-image-compression-thesis_amd/csrc/$f $P/csrc/$f; done
 HIPFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function"
 pids=()
-for f in $P/csrc/*.hip $(ls $P/csrc/*.cpp | grep -v jxg_cjxl); do
-  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $T/${b%.*}.o & pids+=($!)
+for f in $P/csrc/*.hip $(ls $P/csrc/*.cpp | grep -v -e jxg_cjxl -e jxg_djxl); do
+  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $T/$b.o & pids+=($!)
 done
 for p in ${pids[@]}; do wait $p; done
 mkdir -p $D/tools/var

@@ -9,8 +9,8 @@ O=$D/tools/var/obj_$NAME
 mkdir -p $O
 HIPFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function $FLAGS"
 pids=()
-for f in $P/csrc/*.hip $(ls $P/csrc/*.cpp | grep -v jxg_cjxl); do
-  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $O/${b%.*}.o 2>/dev/null & pids+=($!)
+for f in $P/csrc/*.hip $(ls $P/csrc/*.cpp | grep -v -e jxg_cjxl -e jxg_djxl); do
+  b=$(basename $f); /opt/rocm/bin/hipcc $HIPFLAGS -c $f -o $O/$b.o 2>/dev/null & pids+=($!)
 done
 for p in ${pids[@]}; do wait $p; done
 /opt/rocm/bin/hipcc $HIPFLAGS -shared -o $D/tools/var/libjxg_$NAME.so $O/*.o 2>/dev/null
