@@ -1,0 +1,374 @@
+// jxg_abi.cpp -- the C ABI (include/jxg.h): every entry point checks its
+// arguments, makes the context's device current (ctx_enter) and calls one
+// internal function.  (jxg_decode_info is jxg_decode.cpp's: it needs no device.)
+#include <cstring>
+
+#include "jxg_ctx.h"
+#include "jxg_decode.h"
+
+using namespace jxg;
+
+extern "C" {
+
+const char* jxg_status_str(jxg_status s) {
+  switch (s) {
+    case JXG_OK: return "ok";
+    case JXG_ERR_INVALID_ARG: return "invalid argument";
+    case JXG_ERR_NO_DEVICE: return "no HIP device";
+    case JXG_ERR_HIP: return "HIP runtime error";
+    case JXG_ERR_OOM: return "out of memory";
+    case JXG_ERR_UNSUPPORTED: return "unsupported";
+    default: return "internal error";
+  }
+}
+
+jxg_status jxg_create(const jxg_params* params, jxg_ctx** out) {
+  if (!params || !out) return JXG_ERR_INVALID_ARG;
+  return ctx_create(*params, reinterpret_cast<Ctx**>(out));
+}
+
+void jxg_destroy(jxg_ctx* ctx) { ctx_destroy(reinterpret_cast<Ctx*>(ctx)); }
+
+jxg_status jxg_encode_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                  size_t stride, jxg_buffer* out) {
+  if (!ctx || !d_rgb || !out || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  const Clock::time_point t0 = Clock::now();
+  *out = jxg_buffer{nullptr, 0};
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : encode_one(c, static_cast<const uint8_t*>(d_rgb), true, w, h, stride, out, t0);
+}
+
+jxg_status jxg_encode_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride,
+                           jxg_buffer* out) {
+  if (!ctx || !rgb || !out || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  const Clock::time_point t0 = Clock::now();
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);  // (c->rgb may be an in-flight lane's input)
+  if (st) return st;
+  *out = jxg_buffer{nullptr, 0};
+  return encode_one(c, rgb, false, w, h, stride, out, t0);
+}
+
+jxg_status jxg_encode_batch_rgb8(jxg_ctx* ctx, const uint8_t* const* rgbs, uint32_t n, uint32_t w,
+                                 uint32_t h, size_t stride, jxg_buffer* outs) {
+  if (!ctx || !rgbs || !outs || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++)
+    if (!rgbs[i]) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : batch_encode(c, rgbs, false, n, w, h, stride, outs);
+}
+
+jxg_status jxg_encode_batch_rgb8_device(jxg_ctx* ctx, const void* const* d_rgbs, uint32_t n,
+                                        uint32_t w, uint32_t h, size_t stride,
+                                        jxg_buffer* outs) {
+  if (!ctx || !d_rgbs || !outs || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++)
+    if (!d_rgbs[i]) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st
+            : batch_encode(c, reinterpret_cast<const uint8_t* const*>(d_rgbs), true, n, w, h,
+                           stride, outs);
+}
+
+jxg_status jxg_submit_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                  size_t stride) {
+  if (!ctx || !d_rgb || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : pipe_submit(c, static_cast<const uint8_t*>(d_rgb), true, w, h, stride);
+}
+
+jxg_status jxg_submit_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride) {
+  if (!ctx || !rgb || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : pipe_submit(c, rgb, false, w, h, stride);
+}
+
+jxg_status jxg_receive(jxg_ctx* ctx, jxg_buffer* out) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  *out = jxg_buffer{nullptr, 0};
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : pipe_receive(c, out);
+}
+
+jxg_status jxg_pending(jxg_ctx* ctx, uint32_t* n) {
+  if (!ctx || !n) return JXG_ERR_INVALID_ARG;
+  *n = pipe_pending(reinterpret_cast<Ctx*>(ctx));
+  return JXG_OK;
+}
+
+jxg_status jxg_get_stats(jxg_ctx* ctx, jxg_stats* stats) {
+  if (!ctx || !stats) return JXG_ERR_INVALID_ARG;
+  *stats = reinterpret_cast<Ctx*>(ctx)->stats;
+  return JXG_OK;
+}
+
+void jxg_buffer_free(jxg_buffer* buf) {
+  if (!buf) return;
+  out_release(buf->data);
+  *buf = jxg_buffer{nullptr, 0};
+}
+
+jxg_status jxg_shard_sizes(uint32_t xsize, uint32_t ysize, uint32_t world, size_t* hist_words,
+                           size_t* slot_bytes) {
+  if (!hist_words || !slot_bytes || xsize == 0 || ysize == 0 || world == 0)
+    return JXG_ERR_INVALID_ARG;
+  *hist_words = (size_t)kMaxClusters * kAlpha + 4;  // + the varblocks per big kind
+  *slot_bytes = exchange_slot_records(make_frame(xsize, ysize, 1.0f), world) * kGroupRecordBytes;
+  return JXG_OK;
+}
+
+jxg_status jxg_shard_exchange(uint32_t xsize, uint32_t ysize, uint32_t world, uint32_t rank,
+                              size_t* send_bytes, size_t* recv_bytes) {
+  if (!send_bytes || !recv_bytes || xsize == 0 || ysize == 0 || world == 0 || rank >= world)
+    return JXG_ERR_INVALID_ARG;
+  const Frame f = make_frame(xsize, ysize, 1.0f);
+  const Exchange X = make_exchange(f, make_partition(f, world), rank, world);
+  for (uint32_t p = 0; p < world; p++) {
+    send_bytes[p] = (size_t)X.nsend[p] * kGroupRecordBytes;
+    recv_bytes[p] = (size_t)X.nrecv[p] * kGroupRecordBytes;
+  }
+  return JXG_OK;
+}
+
+jxg_status jxg_shard_begin(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h, size_t stride,
+                           uint32_t rank, uint32_t world, uint32_t* d_hist, void* d_xbuf) {
+  if (!ctx || !d_rgb || !d_hist || !d_xbuf || !frame_args_ok(w, h, stride))
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : shard_begin(c, static_cast<const uint8_t*>(d_rgb), w, h, stride, rank, world, d_hist,
+                          static_cast<uint8_t*>(d_xbuf));
+}
+
+jxg_status jxg_shard_end(jxg_ctx* ctx, const uint32_t* d_hist, const void* d_xbuf,
+                         size_t* payload_bytes) {
+  if (!ctx || !d_hist || !d_xbuf || !payload_bytes) return JXG_ERR_INVALID_ARG;
+  *payload_bytes = 0;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : shard_end(c, d_hist, static_cast<const uint8_t*>(d_xbuf), payload_bytes);
+}
+
+jxg_status jxg_shard_payload(jxg_ctx* ctx, void* dst, int dst_on_device) {
+  if (!ctx || !dst) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : shard_payload(c, dst, dst_on_device != 0);
+}
+
+jxg_status jxg_shard_assemble_device(jxg_ctx* ctx, const void* d_payloads, const size_t* offsets,
+                                     const size_t* sizes, uint32_t n, jxg_buffer* out) {
+  if (!ctx || !d_payloads || !offsets || !sizes || !out || n == 0) return JXG_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++)
+    if (offsets[i] % 4) return JXG_ERR_INVALID_ARG;
+  *out = jxg_buffer{nullptr, 0};
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : shard_assemble_device(c, static_cast<const uint8_t*>(d_payloads), offsets, sizes, n,
+                                    out);
+}
+
+jxg_status jxg_shard_head(jxg_ctx* ctx, uint32_t* dst, size_t* nwords) {
+  if (!ctx || !nwords) return JXG_ERR_INVALID_ARG;
+  return shard_head(reinterpret_cast<Ctx*>(ctx), dst, nwords);
+}
+
+jxg_status jxg_shard_write_host(jxg_ctx* ctx, const uint32_t* const* heads, const size_t* head_words,
+                                uint32_t n, void* dst, size_t dst_size, size_t* total) {
+  if (!ctx || !heads || !head_words || !total || n == 0) return JXG_ERR_INVALID_ARG;
+  *total = 0;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : shard_write_host(c, heads, head_words, n, static_cast<uint8_t*>(dst), dst_size, total);
+}
+
+jxg_status jxg_host_register(void* ptr, size_t size) {
+  if (!ptr || size == 0) return JXG_ERR_INVALID_ARG;
+  return hipHostRegister(ptr, size, hipHostRegisterDefault) == hipSuccess ? JXG_OK : JXG_ERR_HIP;
+}
+
+jxg_status jxg_host_unregister(void* ptr) {
+  if (!ptr) return JXG_ERR_INVALID_ARG;
+  return hipHostUnregister(ptr) == hipSuccess ? JXG_OK : JXG_ERR_HIP;
+}
+
+jxg_status jxg_shard_assemble(const uint8_t* const* payloads, const size_t* sizes, uint32_t n,
+                              jxg_buffer* out) {
+  if (!out) return JXG_ERR_INVALID_ARG;
+  *out = jxg_buffer{nullptr, 0};
+  return shard_assemble(payloads, sizes, n, out);
+}
+
+jxg_status jxg_shard_plan(uint32_t xsize, uint32_t ysize, uint32_t world, uint32_t* group_owner,
+                          uint32_t* lf_owner, int* kind) {
+  if (world == 0 || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
+  const Frame f = make_frame(xsize, ysize, 1.0f);
+  const Partition part = make_partition(f, world);
+  if (group_owner) std::copy(part.group.begin(), part.group.end(), group_owner);
+  if (lf_owner) std::copy(part.lf.begin(), part.lf.end(), lf_owner);
+  if (kind) *kind = part.kind;
+  return JXG_OK;
+}
+
+jxg_status jxg_set_input_stream(jxg_ctx* ctx, void* stream) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  reinterpret_cast<Ctx*>(ctx)->in_stream = static_cast<hipStream_t>(stream);
+  return JXG_OK;
+}
+
+jxg_status jxg_pipeline_depth(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize, uint32_t rank,
+                              uint32_t world, uint32_t* depth) {
+  if (!ctx || !depth || xsize == 0 || ysize == 0 || world == 0 || rank >= world)
+    return JXG_ERR_INVALID_ARG;
+  return pipe_depth(reinterpret_cast<Ctx*>(ctx), xsize, ysize, rank, world, depth);
+}
+
+jxg_status jxg_set_pipeline_lanes(jxg_ctx* ctx, uint32_t lanes) {
+  if (!ctx || lanes > kPipeMaxLanes) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->lane_cap = lanes;
+  return JXG_OK;
+}
+
+jxg_status jxg_shard_submit_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                   size_t stride, uint32_t rank, uint32_t world) {
+  if (!ctx || !d_rgb || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st
+            : pipe_submit(c, static_cast<const uint8_t*>(d_rgb), true, w, h, stride, rank, world,
+                          true);
+}
+
+jxg_status jxg_shard_next_head(jxg_ctx* ctx, uint32_t* dst, size_t* nwords) {
+  if (!ctx || !nwords) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : shard_next_head(c, dst, nwords);
+}
+
+jxg_status jxg_shard_write_next(jxg_ctx* ctx, const uint32_t* const* heads, const size_t* head_words,
+                                uint32_t n, void* dst, size_t dst_size, size_t* total) {
+  if (!ctx || !heads || !head_words || !total || n == 0) return JXG_ERR_INVALID_ARG;
+  *total = 0;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st
+            : shard_write_next(c, heads, head_words, n, static_cast<uint8_t*>(dst), dst_size, total);
+}
+
+jxg_status jxg_shard_write_flush(jxg_ctx* ctx) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : shard_write_flush(c);
+}
+
+jxg_status jxg_homogeneity_map(jxg_ctx* ctx, const float* xyb, uint32_t xsize, uint32_t ysize,
+                               float distance, uint32_t flags, float* r3, uint8_t* type) {
+  if (!ctx || !xyb || !r3 || !type || xsize == 0 || ysize == 0 || xsize % 8 || ysize % 8)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : homogeneity_map(c, xyb, xsize, ysize, distance, flags, r3, type);
+}
+
+jxg_status jxg_compare_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
+                                   const void* d_comp, size_t comp_stride, uint32_t xsize,
+                                   uint32_t ysize, int want_ssim, jxg_quality* out) {
+  if (!ctx || !d_orig || !d_comp || !out || xsize == 0 || ysize == 0 ||
+      orig_stride < (size_t)xsize * 3 || comp_stride < (size_t)xsize * 3)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  jxg_status st = ctx_enter(ctx, true, &c);
+  if (!st) st = order_input(c, c);
+  return st ? st
+            : compare_device(c, static_cast<const uint8_t*>(d_orig), orig_stride,
+                             static_cast<const uint8_t*>(d_comp), comp_stride, xsize, ysize,
+                             want_ssim, out);
+}
+
+jxg_status jxg_compare_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
+                            const uint8_t* comp, size_t comp_stride, uint32_t xsize,
+                            uint32_t ysize, int want_ssim, jxg_quality* out) {
+  if (!ctx || !orig || !comp || !out || xsize == 0 || ysize == 0 ||
+      orig_stride < (size_t)xsize * 3 || comp_stride < (size_t)xsize * 3)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : compare_host(c, orig, orig_stride, comp, comp_stride, xsize, ysize, want_ssim, out);
+}
+
+jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_stride) {
+  if (!ctx || !d_rgb) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : reconstruct_last(c, static_cast<uint8_t*>(d_rgb), row_stride, true);
+}
+
+jxg_status jxg_reconstruct_rgb8(jxg_ctx* ctx, uint8_t* rgb, size_t row_stride) {
+  if (!ctx || !rgb) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : reconstruct_last(c, rgb, row_stride, false);
+}
+
+jxg_status jxg_decode_rgb8_device(jxg_ctx* ctx, const uint8_t* data, size_t size, void* d_rgb,
+                                  size_t row_stride) {
+  if (!ctx || !data || !d_rgb || size == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : decode_rgb8(c, data, size, static_cast<uint8_t*>(d_rgb), row_stride, true);
+}
+
+jxg_status jxg_decode_rgb8(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8_t* rgb,
+                           size_t row_stride) {
+  if (!ctx || !data || !rgb || size == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : decode_rgb8(c, data, size, rgb, row_stride, false);
+}
+
+jxg_status jxg_decode_maps(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8_t* acs,
+                           uint8_t* qf, int32_t* dc, int32_t* ac, int8_t* cmap) {
+  if (!data || size == 0) return JXG_ERR_INVALID_ARG;
+  if (!ctx) return (jxg_status)decode_maps_host(data, size, acs, qf, dc, ac, cmap);
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : guarded([&] { return decode_maps_device(c, data, size, acs, qf, dc, ac, cmap); });
+}
+
+jxg_status jxg_decode_timings(jxg_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return JXG_ERR_INVALID_ARG;
+  std::memcpy(ms, reinterpret_cast<const Ctx*>(ctx)->dec.ms, sizeof(float) * 5);
+  return JXG_OK;
+}
+
+jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
+  if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : warmup(c, xsize, ysize);
+}
+
+jxg_status jxg_synth_rgb8_device(jxg_ctx* ctx, void* d_out, uint32_t xsize, uint32_t ysize,
+                                 size_t row_stride, uint64_t seed) {
+  if (!ctx || !d_out || xsize == 0 || ysize == 0 || row_stride < (size_t)xsize * 3)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, false, &c);
+  return st ? st : synth_device(c, static_cast<uint8_t*>(d_out), xsize, ysize, row_stride, seed);
+}
+
+}  // extern "C"

@@ -1,0 +1,421 @@
+// jxg_ctx.h -- what the host translation units share: the encoder context
+// (Ctx), the state of one encode (Job), device / pinned buffers, and the
+// functions that cross files.  Internal: nothing here is exported; the C ABI
+// (include/jxg.h) is jxg_abi.cpp.
+//
+// One encode = one stream-ordered pipeline on the context's HIP stream:
+//   front (RGB8 -> ACS/QF/DC/AC)            [jxg_front.hip]
+//   ac_hist + lf_hist (token statistics)     [jxg_entropy.hip]
+//   -> D2H histograms; host builds prefix codes, LfGlobal/HfGlobal and the
+//      LF-group stream preludes (a few KB of header bits)
+//   ac_emit or the rANS chain + ans_emit, lf_code (bit emission into scratch)
+//   -> D2H section sizes; host writes headers + TOC and the piece list
+//   concat (bit-exact assembly) -> D2H codestream
+// The byte stream equals the CPU oracle's (oracle/encode.c) bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/jxg.h"
+#include "jxg_bitstream.h"
+#include "jxg_device.h"
+#include "jxg_kernels.h"
+#include "jxg_plan.h"
+
+#pragma GCC visibility push(hidden)
+namespace jxg {
+
+#define JXG_HIP(expr)                                                          \
+  do {                                                                         \
+    hipError_t e_ = (expr);                                                    \
+    if (e_ != hipSuccess) {                                                    \
+      std::fprintf(stderr, "jxg: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
+      return JXG_ERR_HIP;                                                      \
+    }                                                                          \
+  } while (0)
+
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  bool n_grow = false;  // allocated before
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    // a regrowth gets 1/8 headroom: per-frame sizes (bit scratch, output)
+    // vary a little between frames, and a reallocation in a streamed frame
+    // costs ~0.1 ms of host time (hipFree + hipMalloc)
+    size_t want = n_grow ? std::max<size_t>(count + count / 8, 1) : std::max<size_t>(count, 1);
+    n_grow = true;
+    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
+    if (e == hipSuccess) n = want;
+    return e;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// A typed window into an arena (Ctx::stat / up and their host mirrors): the
+// arena is laid out per frame by stage_alloc, so ensure() only checks.
+template <class T>
+struct View {
+  T* p = nullptr;
+  size_t n = 0;
+  hipError_t ensure(size_t count) const { return count <= n ? hipSuccess : hipErrorInvalidValue; }
+  void set(void* base, size_t byte_off, size_t count) {
+    p = reinterpret_cast<T*>(static_cast<uint8_t*>(base) + byte_off);
+    n = count;
+  }
+};
+
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    n = 0;
+    size_t want = std::max<size_t>(count, 1);
+    hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) n = want;
+    return e;
+  }
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+using Clock = std::chrono::steady_clock;
+inline float ms_since(Clock::time_point t0) {
+  return std::chrono::duration<float, std::milli>(Clock::now() - t0).count();
+}
+
+struct Ctx;
+struct Job;
+struct Pipe;
+// batch lanes (jxg_encode_batch_rgb8[_device]): extra contexts of the same
+// parameters, each with its own stream and pinned staging, owned by the
+// context that ran the batch
+struct CtxDeleter {
+  void operator()(Ctx* c) const;
+};
+struct PipeDeleter {  // (Pipe is private to jxg_pipe.cpp)
+  void operator()(Pipe* p) const;
+};
+struct Ctx {
+  jxg_params params{};
+  std::vector<std::unique_ptr<Ctx, CtxDeleter>> lanes;
+  PinBuf<uint8_t> h_stage;  // pinned staging of one host frame (pipeline lanes)
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr;  // AC-block concat + D2H (stage_concat_split)
+  // ev[6]: AC statistics downloaded (stage_download_ac); ev[7]: AC emission
+  // done and its bit counts on the host; ev[8]: AC block in host memory;
+  // ev[9]: masking quant field done (front kernel start)
+  hipEvent_t ev[10] = {};
+  bool constants_ready = false;
+  // device
+  DevBuf<uint8_t> rgb, acs, qf, aqf;  // aqf: masking quant field (JXG_FLAG_AQ_MASKING)
+  DevBuf<float> lut;                   // sRGB8 -> linear (the AQ kernel)
+  DevBuf<int8_t> cmap;  // [2][tiles] chroma from luma (front kernel)
+  DevBuf<uint16_t> nz, mnat;
+  DevBuf<float> ent, mwk, msdk, miwy, xyb_tiles, mcost;
+  // merge levels 128 / 256 px (effort >= 8): tables (uploaded once), scratch
+  // planes of the persistent workgroups, candidate estimates, chosen list
+  DevBuf<float> big_tab, big_scratch, big_cost;
+  DevBuf<uint16_t> big_nat;
+  DevBuf<uint32_t> big_work;
+  bool big_ready = false;
+  DevBuf<uint32_t> vb, mwork, xlist;
+  DevBuf<uint8_t> lf_mine;  // shard: [nlf] owned LF groups (vb_list)
+  DevBuf<int32_t> dc;
+  DevBuf<int16_t> ac;
+  DevBuf<float> homog, xyb, r3;
+  DevBuf<uint8_t> type;
+  DevBuf<uint32_t> stream_chunks, scratch, scratch_lf, out;
+  DevBuf<uint64_t> lfstatus;  // [nchunks] lf_code look-back words
+  // Per-frame statistics, zeroed by the front kernel and downloaded by two copies
+  // (AC part, LF part): [hist_ac | bound | ntok | bandtok | bigcount][lfhist | sbound | vcount]
+  DevBuf<uint8_t> stat;
+  PinBuf<uint8_t> h_stat;
+  View<uint32_t> hist_ac, bound, ntok, bandtok, bigcount, lfhist, sbound, vcount;
+  View<uint32_t> h_hist_ac, h_bound, h_ntok, h_bigcount, h_lfhist, h_sbound, h_vcount;
+  size_t stat_lf = 0, stat_bytes = 0;  // byte offset of the LF part, total
+  // Per-frame code tables, uploaded by one copy (ANS) or two (prefix codes:
+  // the AC part ahead of the AC emission): [codes_ac | gbase | ans_order |
+  // ans_tab][lfcodes | stream_base]
+  DevBuf<uint8_t> up;
+  PinBuf<uint8_t> h_up;
+  View<uint32_t> codes_ac, ans_order, lfcodes, h_codes_ac, h_ans_order, h_lfcodes;
+  View<uint64_t> gbase, stream_base, h_gbase, h_sbase;
+  View<uint8_t> ans_tab, h_ans_tab;
+  size_t up_gbase = 0, up_ac = 0, up_lf = 0, up_bytes = 0;
+  // emitted bit counts, one download: [gbits | stream_bits]
+  DevBuf<uint32_t> bits;
+  PinBuf<uint32_t> h_bits;
+  View<uint32_t> gbits, stream_bits, h_gbits, h_sbits;
+  uint32_t* lf_scratch = nullptr;  // LF-stream bit arena (scratch_lf, or in scratch)
+  DevBuf<uint32_t> tile_list, glist;  // shard: tile ids, pass groups (non-contiguous plans)
+  DevBuf<uint32_t> tokens, tval, ans_state, csum;  // ANS coder
+  DevBuf<uint8_t> tlen;
+  DevBuf<LfRow> rows;
+  DevBuf<LfChunk> lfchunks;
+  // decode-side quality (jxg_compare_rgb8; jxg_quality.cpp)
+  struct Quality {
+    DevBuf<uint8_t> orig, comp;
+    DevBuf<uint64_t> sse;
+    DevBuf<double> part, ssim;
+    bool gauss_ready = false;
+  } q;
+  // decode-side reconstruction (jxg_reconstruct_rgb8; jxg_reconstruct.cpp),
+  // allocated by its first call: tables, two sets of three block-padded f32
+  // planes, the list of 128 / 256 px varblocks, the host variant's device image
+  struct Recon {
+    DevBuf<float> tab, pa, pb;
+    DevBuf<uint16_t> pos;
+    DevBuf<uint32_t> big;
+    DevBuf<uint8_t> rgb;
+    uint32_t tab_g = 0;  // global scale the EPF sigma table was built for
+    // the last encode was jxg_encode_rgb8[_device] of a w x h frame, whose
+    // coefficients and maps are still in this context's buffers
+    bool ok = false;
+    uint32_t w = 0, h = 0;
+  } rc;
+  // decoder (jxg_decode_rgb8; jxg_decode_dev.cpp), allocated by its first
+  // call: the codestream's words, the pass groups' section bounds, the AC
+  // stream's decode tables [ctxmap | histograms | prefix or alias tables], the
+  // per-group status
+  struct Dec {
+    DevBuf<uint64_t> stream, sec;
+    DevBuf<uint8_t> tab;
+    DevBuf<uint32_t> status;
+    hipEvent_t ev[3] = {};  // pass-group kernel start / end, reconstruction end
+    // last decode: host parse + tables, LF groups, pass-group kernel,
+    // reconstruction chain (device), the whole call (host wall); milliseconds
+    float ms[5] = {};
+  } dec;
+  // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
+  // assemblers)
+  struct Concat {
+    DevBuf<ConcatPiece> pieces, pieces_ac;
+    DevBuf<uint8_t> buf;  // stage_concat: [pieces | chunk words], one upload
+    PinBuf<uint8_t> h_buf;
+    PinBuf<ConcatPiece> h_pieces_ac;
+    DevBuf<uint32_t> chunks, out_ac;
+  } cat;
+  // host
+
+  // LF row segments cached per frame size and shard
+  uint32_t rows_w = 0, rows_h = 0, rows_rank = 0, rows_world = 1;
+  std::vector<LfRow> rows_h_cache;
+  std::vector<LfChunk> chunks_h_cache;
+  std::vector<uint32_t> schunks_cache;
+  // serialised AC context map of the previous frame (reused when equal)
+  std::vector<uint8_t> cm_last;
+  int cm_nhist = -1;
+  BitWriter cm_bits;
+  std::vector<uint8_t> m_acs, m_qf;
+  std::vector<int32_t> m_dc, m_ac;
+  std::vector<uint32_t> m_ntok;
+  std::vector<float> m_homog;
+  jxg_stats stats{};
+  // ordering of device inputs (jxg_set_input_stream): the caller's stream
+  // whose work so far every device-input entry point orders itself after
+  hipStream_t in_stream = nullptr;
+  hipEvent_t ev_in = nullptr;
+  hipEvent_t ev_write = nullptr;  // jxg_shard_write_next: this slot's section copies
+  uint32_t lane_cap = 0;          // jxg_set_pipeline_lanes (0: the queues' limit)
+  bool owned_lane = false;  // a pipeline / batch lane of another context
+  // a pipeline lane's extra slots: contexts with their own buffers that share
+  // this context's stream (super-frames: k frames per batched launch)
+  std::vector<std::unique_ptr<Ctx, CtxDeleter>> slots;
+  bool shared_stream = false;  // `stream` belongs to the lane that owns this slot
+  std::unique_ptr<Job> job;                 // sharded encode in flight (begin -> end)
+  std::unique_ptr<Pipe, PipeDeleter> pipe;  // streaming encode (jxg_submit_* / jxg_receive)
+  std::vector<uint32_t> payload_head;  // last jxg_shard_end: payload head words
+  size_t payload_body = 0;             //   and body bytes (in `out`)
+};
+
+// state carried between the stages of one encode
+struct Job {
+  Frame f;
+  Plan plan;
+  uint32_t w = 0, h = 0;
+  size_t stride = 0;
+  const uint8_t* d_rgb = nullptr;
+  int max_s = 0;
+  bool homog = false;
+  bool ans = false;  // ANS instead of prefix codes for the AC stream
+  uint32_t lf = 0;   // frame header loop-filter code (lf_code: Gaborish / EPF)
+  uint32_t nhist_ans = 0, max_tokens = 0;
+  uint32_t nrows = 0, nchunks = 0, nstreams = 0;
+  AcArgs aa{};
+  LfArgs la{};
+  // argument blocks of the front / merge / LF-list stages and the rANS coder
+  // (build_front, build_emit): the batched launches gather them per frame
+  FrontArgs fa{};
+  AqArgs qa{};
+  MergeArgs ma{};
+  BigArgs ba{};
+  bool big = false;  // merge levels 128 / 256 px (effort >= 8)
+  VbArgs va{};
+  AnsArgs na{};
+  bool aq = false;  // masking quant field (aq_kernel before the front kernel)
+  // host stage results
+  std::vector<BitWriter> preA, preB;
+  BitWriter lfglobal, hfglobal;
+  // sharded ANS encode with one HF preset per rank: no histogram
+  // all-reduce; the rank's clustered histograms travel in its payload head and
+  // HfGlobal is written at assembly (build_hf_presets)
+  bool presets = false;
+  std::vector<uint8_t> pre_ctxmap;   // [kAcCtx] context -> the rank's dense histogram
+  std::vector<uint32_t> pre_counts;  // [nhist][kAlpha] clustered counts
+  std::vector<uint64_t> gbase, sbase;
+  float ms_codes = 0.0f;
+  float ms_layout = 0.0f;  // stage_concat_split host layout
+  // enc_finish_start -> enc_finish_end: the codestream (pinned pool block,
+  // D2H in flight), its size, the host layout time
+  uint8_t* host_out = nullptr;
+  size_t out_bytes = 0;
+  float ms_finish_layout = 0.0f;
+};
+
+// ---- jxg_ctx.cpp: context lifetime, constants, the pinned output pool ----
+constexpr size_t kOutHdr = 64;  // bytes in front of every output block
+uint8_t* out_alloc(size_t bytes);
+uint8_t* out_alloc_heap(size_t bytes);  // host-only outputs (no device needed)
+void out_set_backref(uint8_t* data, uint8_t* data0);
+void out_release(uint8_t* data);
+extern std::mutex g_const_mu;  // device __constant__ tables are shared by all contexts
+bool lone_context();           // at most one caller-created context is alive
+jxg_status ctx_create(const jxg_params& params, Ctx** out);
+jxg_status ctx_new_lane(const jxg_params& params, Ctx** out);
+void ctx_destroy(Ctx* c);
+jxg_status init_constants(Ctx* c);
+hipError_t make_event(hipEvent_t* e, unsigned flags);
+float elapsed(hipEvent_t a, hipEvent_t b);
+uint32_t hw_queues();
+jxg_status order_input(Ctx* owner, Ctx* lane);
+
+// ---- jxg_encode.cpp: stages A-H and the phases of one frame ----
+uint32_t big_mask(const uint32_t* count);
+jxg_status stage_alloc(Ctx* c, Job& J);
+jxg_status build_front(Ctx* c, Job& J);
+jxg_status stage_download_ac(Ctx* c, Job& J, const uint32_t* hist);
+jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k);
+jxg_status launch_lf_stats(Ctx* const* cs, Job* const* js, uint32_t k);
+jxg_status launch_stats(Ctx* const* cs, Job* const* js, uint32_t k);
+jxg_status stage_codes(Ctx* c, Job& J);
+jxg_status launch_emit(Ctx* const* cs, Job* const* js, uint32_t k, bool streamed);
+jxg_status stage_emit(Ctx* c, Job& J, bool sync = true);
+jxg_status wait_emission(Ctx* c, Job& J);
+jxg_status stage_concat(Ctx* c, Job& J, bool full, std::vector<uint32_t>* section_ids,
+                        std::vector<uint32_t>* section_bytes, uint8_t** host_out,
+                        size_t* out_bytes);
+jxg_status enc_prepare(Ctx* c, Job& J, const uint8_t* d_rgb, uint32_t w, uint32_t h,
+                       size_t stride, uint32_t rank, uint32_t world);
+jxg_status enc_finish_start(Ctx* c, Job& J, bool split);
+void enc_stats(Ctx* c, Job& J, size_t out_bytes, float ms_layout, bool assembled,
+               const std::vector<int16_t>* m_ac16, Clock::time_point t_call);
+jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out, Clock::time_point t_call);
+// one frame through the one-at-a-time path, with the bookkeeping of what
+// jxg_reconstruct_rgb8 may read afterwards (src: host memory, or device memory
+// ordered after the caller's input stream)
+jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
+                      size_t stride, jxg_buffer* out, Clock::time_point t_call);
+jxg_status warmup(Ctx* c, uint32_t w, uint32_t h);
+
+// ---- jxg_pipe.cpp: the streaming pipeline ----
+bool pipe_busy(const Ctx* c);
+uint32_t pipe_pending(const Ctx* c);
+void pipe_abort(Ctx* c);
+void pipe_drop_done(Ctx* c);
+jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
+                       size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false);
+jxg_status pipe_receive(Ctx* c, jxg_buffer* out);
+jxg_status pipe_depth(const Ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t world,
+                      uint32_t* depth);
+jxg_status batch_encode(Ctx* c, const uint8_t* const* frames, bool on_device, uint32_t n,
+                        uint32_t w, uint32_t h, size_t stride, jxg_buffer* outs);
+jxg_status shard_next_head(Ctx* c, uint32_t* dst, size_t* nwords);
+jxg_status shard_write_next(Ctx* c, const uint32_t* const* heads, const size_t* head_words,
+                            uint32_t n, uint8_t* dst, size_t dst_size, size_t* total);
+jxg_status shard_write_flush(Ctx* c);
+
+// ---- jxg_shard_host.cpp: sharded encode and the shard assemblers ----
+jxg_status shard_begin(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h, size_t stride,
+                       uint32_t rank, uint32_t world, uint32_t* d_hist, uint8_t* d_xbuf);
+jxg_status shard_end(Ctx* c, const uint32_t* d_hist, const uint8_t* d_xbuf, size_t* payload_bytes);
+jxg_status shard_finish(Ctx* c, Job& J, size_t* payload_bytes, bool sync = true);
+jxg_status shard_payload(Ctx* c, void* dst, bool on_device);
+jxg_status shard_head(const Ctx* c, uint32_t* dst, size_t* nwords);
+jxg_status shard_assemble_device(Ctx* c, const uint8_t* d_base, const size_t* offsets,
+                                 const size_t* psizes, uint32_t n, jxg_buffer* out);
+jxg_status shard_write_host(Ctx* c, const uint32_t* const* heads_in, const size_t* words,
+                            uint32_t n, uint8_t* dst, size_t dst_size, size_t* total,
+                            bool sync = true);
+jxg_status shard_assemble(const uint8_t* const* payloads, const size_t* sizes, uint32_t n,
+                          jxg_buffer* out);
+
+// ---- jxg_quality.cpp: quality metrics, homogeneity map, synthetic image ----
+jxg_status homogeneity_map(Ctx* c, const float* xyb, uint32_t xsize, uint32_t ysize,
+                           float distance, uint32_t flags, float* r3, uint8_t* type);
+jxg_status synth_device(Ctx* c, uint8_t* d_out, uint32_t w, uint32_t h, size_t stride,
+                        uint64_t seed);
+jxg_status compare_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_t* d_comp,
+                          size_t sc, uint32_t w, uint32_t h, int want_ssim, jxg_quality* out);
+jxg_status compare_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* comp, size_t sc,
+                        uint32_t w, uint32_t h, int want_ssim, jxg_quality* out);
+
+// ---- jxg_reconstruct.cpp ----
+// the frame constants of a reconstruction: the encoder fills them from its
+// parameters, the decoder from the parsed headers
+struct ReconFrame {
+  uint32_t w, h;
+  uint32_t global_scale, quant_dc;
+  uint32_t lf;        // loop-filter code (lf_code: bit 0 Gaborish, bits 1-2 EPF iterations)
+  float xmul, bmul;   // x_qm / b_qm multipliers
+  bool maybe_big;     // varblocks of 128 / 256 px are possible
+};
+jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride);
+// the last one-at-a-time encode's decoded image, into device / host memory
+jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_device);
+
+// ---- jxg_decode_dev.cpp ----
+jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, size_t row_stride,
+                       bool on_device);
+jxg_status decode_maps_device(Ctx* c, const uint8_t* data, size_t size, uint8_t* acs, uint8_t* qf,
+                              int32_t* dc, int32_t* ac, int8_t* cmap);
+
+// ---- entry-point helpers (jxg_abi.cpp) ----
+// jxg_ctx -> Ctx with its device current; idle: a context whose pipeline
+// holds frames is refused (they use it as a lane, and its host state)
+inline jxg_status ctx_enter(jxg_ctx* ctx, bool idle, Ctx** c) {
+  *c = reinterpret_cast<Ctx*>(ctx);
+  if (hipSetDevice((*c)->params.device) != hipSuccess) return JXG_ERR_HIP;
+  return idle && pipe_busy(*c) ? JXG_ERR_INVALID_ARG : JXG_OK;
+}
+template <class F>
+jxg_status guarded(F f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return JXG_ERR_OOM;
+  } catch (...) {
+    return JXG_ERR_INTERNAL;
+  }
+}
+
+}  // namespace jxg
+#pragma GCC visibility pop

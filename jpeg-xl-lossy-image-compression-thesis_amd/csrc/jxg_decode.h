@@ -1,7 +1,7 @@
 // jxg_decode.h -- host side of the decoder (jxg_decode.cpp; plain C++, no
 // HIP): headers, TOC, LfGlobal, the LF groups' modular streams, HfGlobal and
 // the entropy decode tables, and a host loop over the pass groups through the
-// walk of jxg_decode_core.h.  jxg_host.cpp uploads what this produces and runs
+// walk of jxg_decode_core.h.  jxg_decode_dev.cpp uploads what this produces and runs
 // the pass groups on the GPU (jxg_decode.hip).
 #pragma once
 #include <stddef.h>

@@ -1,4 +1,4 @@
-// jxg_helpers.h -- the streaming pipeline's helper threads (jxg_host.cpp):
+// jxg_helpers.h -- the streaming pipeline's helper threads (jxg_pipe.cpp):
 // a fixed pool that runs the per-frame code builds (clustering, ANS tables,
 // headers, LF-group codes) off the submitting thread.
 #pragma once

@@ -119,19 +119,24 @@ jxg_status parse_payload_heads(const std::vector<std::vector<uint32_t>>& heads,
 }
 
 std::vector<uint32_t> read_head(const uint8_t* p, size_t size) {
-  if (size < 28) return {};
-  std::vector<uint32_t> hw(7);
-  std::memcpy(hw.data(), p, 28);
-  const size_t base = 7 + 2 * (size_t)hw[6];
-  if (hw[1] == 2 && size >= (base + 1) * 4) {  // version 2: the preset block's length
-    hw.resize(base + 1);
-    std::memcpy(hw.data(), p, (base + 1) * 4);
-  }
-  const size_t words = head_words(hw.data(), hw.size());
-  if (!words || size < words * 4) return {};
-  hw.resize(words);
-  std::memcpy(hw.data(), p, words * 4);
+  std::vector<uint32_t> hw;
+  const jxg_status st = read_head_from(size, [p](size_t nwords, uint32_t* dst) {
+    std::memcpy(dst, p, nwords * 4);
+    return JXG_OK;
+  }, hw);
+  if (st) hw.clear();
   return hw;
+}
+
+jxg_status frame_of_heads(const std::vector<std::vector<uint32_t>>& heads,
+                          const std::vector<size_t>& psizes, bool hf_bytes, ShardFrame* F) {
+  uint32_t w = 0, h = 0, lf = 0;
+  const jxg_status st = parse_payload_heads(heads, psizes, &w, &h, F->secs, F->hf, &lf, hf_bytes);
+  if (st) return st;
+  std::vector<uint32_t> sizes(F->secs.size());
+  for (size_t i = 0; i < sizes.size(); i++) sizes[i] = F->secs[i].size;
+  F->lay = stream_layout(w, h, lf, sizes);
+  return JXG_OK;
 }
 
 }  // namespace jxg

@@ -1,5 +1,5 @@
 // jxg_tables.h -- host-side constant tables of the encoder (built once per
-// process, uploaded to __constant__ / device memory by jxg_host.cpp):
+// process, uploaded to __constant__ / device memory by jxg_ctx.cpp init_constants and the stages):
 // default quantization weights, the sRGB8 -> linear table, the masking AQ's
 // erosion weights, and the merge stage's per-shape weight / distortion /
 // natural-order tables and DCT constants.  [ext libjxl quant_weights.cc,

@@ -673,7 +673,7 @@ def shard_sections(width: int, height: int, rank: int, world: int, ans: bool = F
 
 
 def make_payload(rank: int, world: int, width: int, height: int, sections) -> bytes:
-    """The shard payload format of jxg_host.cpp (``JXGS`` v1) for a list of
+    """The shard payload format of jxg_shard_host.cpp / jxg_payload.h (``JXGS`` v1) for a list of
     (TOC index, bytes) -- used by tests to feed jxg_shard_assemble."""
     head = np.array([0x5347584A, 1, rank, world, width, height, len(sections)] +
                     [v for i, b in sections for v in (i, len(b))], dtype="<u4").tobytes()

@@ -53,7 +53,7 @@ def psnr(mse_value: float, max_value: float = 255.0) -> float:
 
 
 def gaussian_window():
-    """== gauss_window() in csrc/jxg_host.cpp (libm exp on both sides)."""
+    """== gauss_window() in csrc/jxg_quality.cpp (libm exp on both sides)."""
     g = [math.exp(-((k - 5.0) * (k - 5.0)) / (2.0 * 1.5 * 1.5)) for k in range(11)]
     s = 0.0
     for v in g:

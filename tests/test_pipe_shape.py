@@ -1,4 +1,4 @@
-"""The streaming pipeline's shape (csrc/jxg_host.cpp pipe_shape), restated:
+"""The streaming pipeline's shape (csrc/jxg_plan.cpp pipe_shape), restated:
 lanes x frames per lane from the pass groups and 64x64 tiles of a frame or
 shard, and jxg_pipeline_depth = (lanes - 1) x batch + 1.  DESIGN.md §3.7's
 table (8K 7 x 1, 4K 12 x 1, 1080p 12 x 4, a rank's eighth of 8K 10 x 4) and

@@ -1,5 +1,5 @@
 """Group sharding, host side (no GPU): the payload format, the section
-ownership of jxg_host.cpp make_plan and the host-only jxg_shard_assemble,
+ownership of jxg_plan.cpp make_plan and the host-only jxg_shard_assemble,
 pinned against the CPU oracle's codestream -- split into per-rank payloads
 by the TOC, exchanged over torch.distributed (gloo, world size 2) and
 re-assembled byte for byte.  The GPU side of the same path (jxg_shard_begin /
@@ -105,7 +105,7 @@ def test_gloo_world2_gather_and_assemble(jxg_mod, oracle, decoder):
 
 
 def partition_py(w, h, world):
-    """Restatement of jxg_host.cpp make_partition (include/jxg.h): kind 0
+    """Restatement of jxg_plan.cpp make_partition (include/jxg.h): kind 0
     contiguous raster ranges when no LF group is split over ranks; else kind 1
     whole LF groups (largest pixel area first, ties by index, to the
     least-loaded rank, ties to the lower rank) when the largest load is within
@@ -206,7 +206,7 @@ def test_record_exchange_plan(jxg_mod, w, h, world):
 
 
 def _v2_payload(rank, world, w, h, sections, nh=1, cm=None, counts=None, fix_b=None):
-    """A version-2 payload (one HF preset per rank, jxg_host.cpp shard_finish):
+    """A version-2 payload (one HF preset per rank, jxg_shard_host.cpp shard_finish):
     head, [B][nhist][context map bytes in words][counts nhist x 128], body."""
     cw = (7425 + 3) // 4
     cm = np.zeros(7425, dtype=np.uint8) if cm is None else cm
