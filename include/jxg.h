@@ -417,6 +417,56 @@ jxg_status jxg_decode_maps(jxg_ctx* ctx, const uint8_t* data, size_t size, uint8
  * wall clock) */
 jxg_status jxg_decode_timings(jxg_ctx* ctx, float* ms /* [5] */);
 
+/* ---- batch decode: n codestreams in one call ----
+ * The pass-group kernel of one frame lasts as long as its longest pass group
+ * and leaves most of the GPU idle; a batch puts the pass
+ * groups of many frames into one launch.  datas[i] / sizes[i]: the codestreams
+ * (host memory); rgbs[i] / d_rgbs[i] with row_strides[i]: each frame's output
+ * as for jxg_decode_rgb8[_device].  Frames may differ in size, coder, presets
+ * and filters.  Every frame is parsed on the host (at most 8 helper threads
+ * for all frames' LF groups), frames are taken in consecutive chunks whose
+ * device footprint -- per frame blocks * 398 bytes of maps and coefficients,
+ * its stream, tables and section bounds -- fits the byte budget of
+ * jxg_set_decode_batch_bytes (default 2 GiB: 64 1080p frames of about 13 MB or
+ * nine 8K frames of about 206 MB; a frame that alone exceeds it is a chunk of
+ * its own, never refused for its size), each chunk's pass groups run in one
+ * launch (two when the chunk mixes frames whose symbol tables fit LDS with
+ * frames whose tables do not), then each frame's reconstruction chain.
+ * Outputs are byte-identical to jxg_decode_rgb8 of each stream.
+ * Call-level errors, nothing touched: JXG_ERR_INVALID_ARG for a null ctx /
+ * datas / sizes / rgbs / row_strides, n == 0, or streamed frames pending.
+ * Otherwise every frame gets its own status in statuses[i] (may be NULL):
+ * JXG_ERR_INVALID_ARG for a null or empty stream, a null output or a stride
+ * under 3 * xsize, and JXG_ERR_UNSUPPORTED / JXG_ERR_INVALID_ARG as
+ * jxg_decode_rgb8 gives them; a refused frame's buffer is not written and the
+ * other frames complete.  Returns the first non-OK frame status in index
+ * order, or JXG_OK.  JXG_ERR_HIP and JXG_ERR_OOM are call-level and fill every
+ * status.  Like jxg_decode_rgb8 the call ends what jxg_reconstruct_rgb8 could
+ * read; encodes are not affected. */
+jxg_status jxg_decode_batch_rgb8(jxg_ctx* ctx, const uint8_t* const* datas, const size_t* sizes,
+                                 uint32_t n, uint8_t* const* rgbs, const size_t* row_strides,
+                                 jxg_status* statuses /* [n] or NULL */);
+jxg_status jxg_decode_batch_rgb8_device(jxg_ctx* ctx, const uint8_t* const* datas,
+                                        const size_t* sizes, uint32_t n, void* const* d_rgbs,
+                                        const size_t* row_strides,
+                                        jxg_status* statuses /* [n] or NULL */);
+/* the device-memory budget of a chunk, bytes; 0: the default (2 GiB).  Not
+ * while streamed frames are pending. */
+jxg_status jxg_set_decode_batch_bytes(jxg_ctx* ctx, size_t bytes);
+
+/* the context's last jxg_decode_batch_rgb8[_device] */
+typedef struct {
+  uint32_t frames;           /* n of the call */
+  uint32_t chunks;           /* arenas filled, one or two launches each */
+  uint32_t items_staged;     /* work items (pass groups) launched with their symbol tables in LDS */
+  uint32_t items_unstaged;   /*   and with the tables in memory */
+  float ms_parse;            /* host: every frame's parse and LF groups (wall clock) */
+  float ms_groups;           /* the pass-group launches, device time by events, summed over chunks */
+  float ms_recon;            /* the reconstruction chains, by events, summed over chunks */
+  float ms_call;             /* the whole call, host wall clock */
+} jxg_decode_batch_stats;
+jxg_status jxg_decode_batch_timings(jxg_ctx* ctx, jxg_decode_batch_stats* stats);
+
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result
  * discarded), which allocates the size's device buffers and loads every

@@ -355,6 +355,40 @@ jxg_status jxg_decode_timings(jxg_ctx* ctx, float* ms) {
   return JXG_OK;
 }
 
+jxg_status jxg_decode_batch_rgb8(jxg_ctx* ctx, const uint8_t* const* datas, const size_t* sizes,
+                                 uint32_t n, uint8_t* const* rgbs, const size_t* row_strides,
+                                 jxg_status* statuses) {
+  if (!ctx || !datas || !sizes || !rgbs || !row_strides || n == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : decode_batch_rgb8(c, datas, sizes, n, rgbs, row_strides, statuses, false);
+}
+
+jxg_status jxg_decode_batch_rgb8_device(jxg_ctx* ctx, const uint8_t* const* datas,
+                                        const size_t* sizes, uint32_t n, void* const* d_rgbs,
+                                        const size_t* row_strides, jxg_status* statuses) {
+  if (!ctx || !datas || !sizes || !d_rgbs || !row_strides || n == 0) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : decode_batch_rgb8(c, datas, sizes, n, reinterpret_cast<uint8_t* const*>(d_rgbs),
+                                row_strides, statuses, true);
+}
+
+jxg_status jxg_set_decode_batch_bytes(jxg_ctx* ctx, size_t bytes) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->decb.budget = bytes;
+  return JXG_OK;
+}
+
+jxg_status jxg_decode_batch_timings(jxg_ctx* ctx, jxg_decode_batch_stats* stats) {
+  if (!ctx || !stats) return JXG_ERR_INVALID_ARG;
+  *stats = reinterpret_cast<const Ctx*>(ctx)->decb.stats;
+  return JXG_OK;
+}
+
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
   Ctx* c;

@@ -241,6 +241,8 @@ void ctx_destroy(Ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->dec.ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->decb.ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_write) (void)hipEventDestroy(c->ev_write);
   if (c->stream && !c->shared_stream) (void)hipStreamDestroy(c->stream);

@@ -205,6 +205,17 @@ struct Ctx {
     // reconstruction chain (device), the whole call (host wall); milliseconds
     float ms[5] = {};
   } dec;
+  // batch decoder (jxg_decode_batch_rgb8; jxg_decode_batch.cpp), allocated by
+  // its first call: one arena for the maps, coefficients, streams and tables
+  // of a chunk's frames (jxg_decode_plan.h), the frame descriptors and work
+  // lists of the two launches, the per-group status of the chunk
+  struct DecBatch {
+    DevBuf<uint8_t> arena, desc;
+    DevBuf<uint32_t> status;
+    hipEvent_t ev[4] = {};  // pass-group launches start / end, reconstruction chains start / end
+    size_t budget = 0;      // jxg_set_decode_batch_bytes (0: kDecBatchDefaultBytes)
+    jxg_decode_batch_stats stats{};
+  } decb;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
   struct Concat {
@@ -389,6 +400,16 @@ struct ReconFrame {
   bool maybe_big;     // varblocks of 128 / 256 px are possible
 };
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride);
+// the same from maps and coefficients that are not the context's own buffers
+// (the batch decoder's arena slices; layouts of ReconArgs)
+struct ReconMaps {
+  const uint8_t *acs, *qf;
+  const int32_t* dc;
+  const int16_t* ac;
+  const int8_t* cmap;
+};
+jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
+                              size_t stride);
 // the last one-at-a-time encode's decoded image, into device / host memory
 jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_device);
 
@@ -397,6 +418,14 @@ jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, s
                        bool on_device);
 jxg_status decode_maps_device(Ctx* c, const uint8_t* data, size_t size, uint8_t* acs, uint8_t* qf,
                               int32_t* dc, int32_t* ac, int8_t* cmap);
+struct DecFrame;
+// what the reconstruction tables cannot honour is refused (JXG_ERR_UNSUPPORTED)
+jxg_status decode_recon_frame(const DecFrame& F, ReconFrame* R);
+
+// ---- jxg_decode_batch.cpp ----
+jxg_status decode_batch_rgb8(Ctx* c, const uint8_t* const* datas, const size_t* sizes, uint32_t n,
+                             uint8_t* const* rgbs, const size_t* row_strides, jxg_status* statuses,
+                             bool on_device);
 
 // ---- entry-point helpers (jxg_abi.cpp) ----
 // jxg_ctx -> Ctx with its device current; idle: a context whose pipeline

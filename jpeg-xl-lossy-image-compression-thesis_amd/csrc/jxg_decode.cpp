@@ -735,7 +735,7 @@ float ms_between(WallClock::time_point a, WallClock::time_point b) {
   return std::chrono::duration<float, std::milli>(b - a).count();
 }
 
-int parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F) {
+int parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F, uint32_t lf_threads = 8) {
   const auto t0 = WallClock::now();
   if (!data || size == 0 || size > ((size_t)1 << 40)) return kInv;
   F->words.assign(size / 8 + dec::kStreamPadWords, 0);
@@ -847,7 +847,7 @@ int parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F) {
       DEC_TRY(decode_lf_group(shared, F, 0, &F->big_used));
     } else {
       // one task per LF group on helper threads, as the encoder's host code
-      const uint32_t nthreads = std::min(nlf, 8u);
+      const uint32_t nthreads = std::min(nlf, std::max(lf_threads, 1u));
       std::vector<int> status(nlf, 0);
       std::vector<uint32_t> used(nlf, 0);
       auto work = [&](uint32_t first) {
@@ -909,9 +909,9 @@ int parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F) {
 
 }  // namespace
 
-int decode_parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F) {
+int decode_parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F, uint32_t lf_threads) {
   try {
-    return parse(data, size, want_lf, F);
+    return parse(data, size, want_lf, F, lf_threads);
   } catch (const std::bad_alloc&) {
     return JXG_ERR_OOM;
   } catch (...) {  // e.g. std::system_error when a helper thread cannot be started

@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <vector>
 
 #include "../../include/jxg.h"
@@ -26,6 +27,31 @@ struct DecEntropy {
                           (uint32_t)ctxmap.size(), prefix, log_alpha, 0u};
   }
 };
+
+// the decode tables as the pass-group kernels take them, one upload: [hist |
+// atab or ptab | ctxmap], 8-byte aligned parts; tab_bytes: the symbol tables'
+// (DecodeArgs.tab_bytes)
+struct DecTableBlob {
+  std::vector<uint8_t> bytes;
+  size_t o_atab = 0, o_ptab = 0, o_map = 0;
+  uint32_t tab_bytes = 0;
+};
+inline DecTableBlob decode_table_blob(const DecEntropy& E) {
+  DecTableBlob B;
+  const size_t b_hist = E.hist.size() * sizeof(dec::HistDesc);
+  const size_t b_atab = E.atab.size() * sizeof(dec::AnsEntry);
+  const size_t b_ptab = E.ptab.size() * sizeof(uint16_t);
+  B.o_atab = (b_hist + 7) & ~(size_t)7;
+  B.o_ptab = (B.o_atab + b_atab + 7) & ~(size_t)7;
+  B.o_map = (B.o_ptab + b_ptab + 7) & ~(size_t)7;
+  B.bytes.assign(B.o_map + E.ctxmap.size(), 0);
+  std::memcpy(B.bytes.data(), E.hist.data(), b_hist);
+  if (b_atab) std::memcpy(B.bytes.data() + B.o_atab, E.atab.data(), b_atab);
+  if (b_ptab) std::memcpy(B.bytes.data() + B.o_ptab, E.ptab.data(), b_ptab);
+  std::memcpy(B.bytes.data() + B.o_map, E.ctxmap.data(), E.ctxmap.size());
+  B.tab_bytes = (uint32_t)(E.prefix ? b_ptab : b_atab);
+  return B;
+}
 
 struct DecFrame {
   jxg_stream_info info{};
@@ -53,8 +79,11 @@ struct DecFrame {
 
 // want_lf false: the LF groups are skipped where the layout allows it (frames
 // of several sections) -- enough for jxg_decode_info.  JXG_OK or a negative
-// jxg_status.
-int decode_parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F);
+// jxg_status.  lf_threads: the most threads the frame's LF groups may take (this
+// one included); the batch decoder, which parses several frames at a time,
+// shares the 8 between them.
+int decode_parse(const uint8_t* data, size_t size, bool want_lf, DecFrame* F,
+                 uint32_t lf_threads = 8);
 // the pass groups on the host; ac: [blocks][3][64] int16, zeroed by the caller
 int decode_groups_host(const DecFrame& F, int16_t* ac);
 // jxg_decode_maps with ctx == NULL

@@ -21,6 +21,7 @@
 
 #define JXG_WAVE_SYNC() __syncthreads()
 #define JXG_UNIFORM32(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+#include "jxg_decode_plan.h"
 #include "jxg_kernels.h"
 
 namespace jxg {
@@ -31,6 +32,10 @@ constexpr int kDecLanes = 64;
 constexpr uint32_t kDecNzs = 3 * 1024 + dec::kPendCoefs * 4;  // and the pending coefficients
 constexpr uint32_t kDecMap = (dec::kAcCtxPerPreset + 7) & ~7u;
 constexpr uint32_t kDecLdsMax = 60 * 1024;  // of the 64 KB a workgroup gets by default
+// the batch planner (jxg_decode_plan.cpp, host only) restates the layout
+static_assert(kDecPlanNzs == kDecNzs && kDecPlanMap == kDecMap && kDecPlanLdsMax == kDecLdsMax &&
+                  kDecPlanHistBytes == sizeof(dec::HistDesc),
+              "jxg_decode_plan.h: the LDS layout of the pass-group kernels");
 
 uint32_t decode_groups_lds(DecodeArgs* a) {
   const uint32_t base = kDecNzs + kDecMap + ((a->nhist * (uint32_t)sizeof(dec::HistDesc) + 7) & ~7u);
@@ -49,12 +54,14 @@ struct SymReaderLds {
   uint32_t nctx, prefix, log_alpha, ctx_bias;
 };
 
+// one pass group `g` of the frame `a`, by the one-wave workgroup: the body of
+// both kernels below
 template <bool kTabLds>
-__global__ __launch_bounds__(kDecLanes) void decode_groups_kernel(DecodeArgs a) {
+__device__ __forceinline__ void decode_group(const DecodeArgs& a, const uint32_t g) {
   extern __shared__ __align__(8) uint8_t lds[];
   JXG_LDS uint8_t* nzs = (JXG_LDS uint8_t*)lds;
   JXG_LDS uint32_t* pend = (JXG_LDS uint32_t*)(lds + 3 * 1024);
-  const uint32_t g = blockIdx.x, lane = threadIdx.x;
+  const uint32_t lane = threadIdx.x;
   const uint32_t gx = g % a.gxs, gy = g / a.gxs;
   dec::GroupGeom geom;
   geom.bx0 = gx * 32;
@@ -111,6 +118,72 @@ __global__ __launch_bounds__(kDecLanes) void decode_groups_kernel(DecodeArgs a) 
   const int st = dec::decode_pass_group(br, S, a.npresets, a.preset_bits, a.acs, geom, nzs, pend,
                                         a.ac, lane, kDecLanes);
   if (lane == 0) a.status[g] = (uint32_t)st;
+}
+
+template <bool kTabLds>
+__global__ __launch_bounds__(kDecLanes) void decode_groups_kernel(DecodeArgs a) {
+  decode_group<kTabLds>(a, blockIdx.x);
+}
+
+// Batch (jxg_decode_batch_rgb8): one wave per work item (frame, group) of a
+// list that spans the frames of a chunk; the frame's arguments come from a
+// descriptor in memory.  Work item and descriptor are read at addresses that
+// depend on kernel arguments and blockIdx only, and every field is named
+// uniform, so the walk's state stays in scalar registers as in the kernel
+// above.  a.status of a descriptor is the frame's first status word.
+
+// A pointer read from the descriptor: uniform, and named a global-memory
+// pointer -- one loaded from memory is generic to the compiler, which would
+// make every access through it a flat operation (they wait on both memory
+// counters) where the kernel above, whose pointers are kernel arguments, has
+// global loads and scalar loads.
+template <class T>
+__device__ __forceinline__ T* uni_global(T* p) {
+  typedef T __attribute__((address_space(1))) * Global;
+  return (T*)(Global)dec::uni64(reinterpret_cast<uint64_t>(p));
+}
+
+template <bool kTabLds>
+__global__ __launch_bounds__(kDecLanes) void decode_batch_kernel(
+    const DecodeArgs* __restrict__ frames, const DecWork* __restrict__ work) {
+  const uint32_t frame = dec::uni(work[blockIdx.x].frame);
+  const uint32_t g = dec::uni(work[blockIdx.x].group);
+  const DecodeArgs* d = frames + frame;
+  DecodeArgs a;
+  a.stream = uni_global(d->stream);
+  a.sec = uni_global(d->sec);
+  a.sym.ctxmap = uni_global(d->sym.ctxmap);
+  a.sym.hist = uni_global(d->sym.hist);
+  a.sym.ptab = uni_global(d->sym.ptab);
+  a.sym.atab = uni_global(d->sym.atab);
+  a.sym.nctx = dec::uni(d->sym.nctx);
+  a.sym.prefix = dec::uni(d->sym.prefix);
+  a.sym.log_alpha = dec::uni(d->sym.log_alpha);
+  a.sym.ctx_bias = 0u;
+  a.npresets = dec::uni(d->npresets);
+  a.preset_bits = dec::uni(d->preset_bits);
+  a.acs = uni_global(d->acs);
+  a.ac = uni_global(d->ac);
+  a.status = uni_global(d->status);
+  a.bxs = dec::uni(d->bxs);
+  a.bys = dec::uni(d->bys);
+  a.gxs = dec::uni(d->gxs);
+  a.nhist = dec::uni(d->nhist);
+  a.tab_bytes = dec::uni(d->tab_bytes);
+  a.stage_tab = kTabLds ? 1u : 0u;
+  decode_group<kTabLds>(a, g);
+}
+
+hipError_t launch_decode_batch(const DecodeArgs* d_frames, const DecWork* d_work, uint32_t nwork,
+                               bool staged, uint32_t lds, hipStream_t s) {
+  if (nwork == 0) return hipSuccess;
+  if (staged)
+    hipLaunchKernelGGL(decode_batch_kernel<true>, dim3(nwork), dim3(kDecLanes), lds, s, d_frames,
+                       d_work);
+  else
+    hipLaunchKernelGGL(decode_batch_kernel<false>, dim3(nwork), dim3(kDecLanes), lds, s, d_frames,
+                       d_work);
+  return hipGetLastError();
 }
 
 hipError_t launch_decode_groups(const DecodeArgs& a, uint32_t ngroups, hipStream_t s) {

@@ -32,16 +32,9 @@ static jxg_status decode_to_device(Ctx* c, const DecFrame* F) {
   JXG_HIP(D.status.ensure(ng));
   // decode tables, one upload: [hist | atab or ptab | ctxmap], 8-byte aligned parts
   const DecEntropy& E = F->hf;
-  const size_t b_hist = E.hist.size() * sizeof(dec::HistDesc);
-  const size_t b_atab = E.atab.size() * sizeof(dec::AnsEntry);
-  const size_t b_ptab = E.ptab.size() * sizeof(uint16_t);
-  const size_t o_atab = (b_hist + 7) & ~(size_t)7, o_ptab = (o_atab + b_atab + 7) & ~(size_t)7;
-  const size_t o_map = (o_ptab + b_ptab + 7) & ~(size_t)7;
-  std::vector<uint8_t> blob(o_map + E.ctxmap.size(), 0);
-  std::memcpy(blob.data(), E.hist.data(), b_hist);
-  if (b_atab) std::memcpy(blob.data() + o_atab, E.atab.data(), b_atab);
-  if (b_ptab) std::memcpy(blob.data() + o_ptab, E.ptab.data(), b_ptab);
-  std::memcpy(blob.data() + o_map, E.ctxmap.data(), E.ctxmap.size());
+  const DecTableBlob B = decode_table_blob(E);
+  const std::vector<uint8_t>& blob = B.bytes;
+  const size_t o_atab = B.o_atab, o_ptab = B.o_ptab, o_map = B.o_map;
   JXG_HIP(D.tab.ensure(blob.size()));
   for (hipEvent_t& e : D.ev)
     if (!e && make_event(&e, hipEventDefault) != hipSuccess) return JXG_ERR_HIP;
@@ -72,7 +65,7 @@ static jxg_status decode_to_device(Ctx* c, const DecFrame* F) {
   a.bys = F->bys;
   a.gxs = F->gxs;
   a.nhist = (uint32_t)E.hist.size();
-  a.tab_bytes = (uint32_t)(E.prefix ? b_ptab : b_atab);
+  a.tab_bytes = B.tab_bytes;
   JXG_HIP(hipEventRecord(D.ev[0], s));
   JXG_HIP(launch_decode_groups(a, ng, s));
   JXG_HIP(hipEventRecord(D.ev[1], s));
@@ -93,7 +86,7 @@ static jxg_status decode_to_device(Ctx* c, const DecFrame* F) {
 // what the reconstruction tables cannot honour is refused: a 128 / 256 px
 // varblock whose quant table is not the one this encoder writes in DCT mode,
 // x_qm / b_qm scales outside the header's range
-static jxg_status decode_recon_frame(const DecFrame& F, ReconFrame* R) {
+jxg_status decode_recon_frame(const DecFrame& F, ReconFrame* R) {
   for (int k = 0; k < 4; k++) {
     const bool present = F.qm_mask >> k & 1u;
     if (present && !dequant_params_match(k, F.qm_bits[k])) return JXG_ERR_UNSUPPORTED;

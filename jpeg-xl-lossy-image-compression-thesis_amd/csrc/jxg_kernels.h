@@ -395,6 +395,14 @@ struct DecodeArgs {
 // the kernel's dynamic LDS for these arguments; sets stage_tab
 uint32_t decode_groups_lds(DecodeArgs* a);
 hipError_t launch_decode_groups(const DecodeArgs& a, uint32_t ngroups, hipStream_t s);
+// the batch form (jxg_decode_batch.cpp): one wave per work item of d_work
+// (jxg_decode_plan.h), whose frame indexes d_frames -- descriptors in device
+// memory with `status` the frame's first status word; every frame of a launch
+// is of one class (symbol tables staged in LDS or not) and `lds` the largest
+// decode_lds_bytes of them
+struct DecWork;
+hipError_t launch_decode_batch(const DecodeArgs* d_frames, const DecWork* d_work, uint32_t nwork,
+                               bool staged, uint32_t lds, hipStream_t s);
 // synthetic benchmark input (jxg_synth.hip): RGB8 rows of `stride` bytes
 hipError_t launch_synth(uint8_t* out, uint32_t w, uint32_t h, size_t stride, uint64_t seed,
                         hipStream_t s);

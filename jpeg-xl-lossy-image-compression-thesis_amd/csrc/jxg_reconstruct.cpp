@@ -19,6 +19,12 @@ static ReconFrame recon_frame_of_encode(const Ctx* c) {
 }
 
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride) {
+  return reconstruct_device(c, R, ReconMaps{c->acs.p, c->qf.p, c->dc.p, c->ac.p, c->cmap.p}, d_rgb,
+                            stride);
+}
+
+jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
+                              size_t stride) {
   hipStream_t s = c->stream;
   Ctx::Recon& rc = c->rc;
   Frame f = make_frame(R.w, R.h, 1.0f);
@@ -50,11 +56,11 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_
   JXG_HIP(rc.big.ensure(1 + (size_t)bigcap));
   JXG_HIP(hipMemsetAsync(rc.big.p, 0, sizeof(uint32_t), s));
   ReconArgs a{};
-  a.acs = c->acs.p;
-  a.qf = c->qf.p;
-  a.dc = c->dc.p;
-  a.ac = c->ac.p;
-  a.cmap = c->cmap.p;
+  a.acs = M.acs;
+  a.qf = M.qf;
+  a.dc = M.dc;
+  a.ac = M.ac;
+  a.cmap = M.cmap;
   a.w = f.w;
   a.h = f.h;
   a.bxs = f.bxs;

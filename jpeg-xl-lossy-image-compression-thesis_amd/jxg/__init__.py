@@ -84,6 +84,12 @@ class _StreamInfo(ctypes.Structure):
         "num_hf_presets", "ans", "gaborish", "epf_iters")]
 
 
+class _DecodeBatchStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("frames", "chunks", "items_staged",
+                                               "items_unstaged")] + [
+        (k, ctypes.c_float) for k in ("ms_parse", "ms_groups", "ms_recon", "ms_call")]
+
+
 class _Quality(ctypes.Structure):
     _fields_ = [("sse", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("mse", ctypes.c_double),
                 ("psnr", ctypes.c_double), ("ssim", ctypes.c_double)]
@@ -103,7 +109,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_shard_write_flush", "jxg_set_pipeline_lanes", "jxg_warmup",
            "jxg_reconstruct_rgb8", "jxg_reconstruct_rgb8_device",
            "jxg_decode_info", "jxg_decode_rgb8", "jxg_decode_rgb8_device", "jxg_decode_maps",
-           "jxg_decode_timings",
+           "jxg_decode_timings", "jxg_decode_batch_rgb8", "jxg_decode_batch_rgb8_device",
+           "jxg_set_decode_batch_bytes", "jxg_decode_batch_timings",
 )
 
 _lib = None
@@ -184,6 +191,12 @@ def load():
     lib.jxg_decode_rgb8_device.argtypes = [vp, vp, sz, vp, sz]
     lib.jxg_decode_maps.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.jxg_decode_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.jxg_decode_batch_rgb8.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz),
+                                          ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz),
+                                          ctypes.POINTER(ctypes.c_int)]
+    lib.jxg_decode_batch_rgb8_device.argtypes = lib.jxg_decode_batch_rgb8.argtypes
+    lib.jxg_set_decode_batch_bytes.argtypes = [vp, sz]
+    lib.jxg_decode_batch_timings.argtypes = [vp, ctypes.POINTER(_DecodeBatchStats)]
     _lib = lib
     return lib
 
@@ -312,6 +325,80 @@ class Encoder:
         ms = (ctypes.c_float * 5)()
         _check(load().jxg_decode_timings(self._ctx, ms))
         return dict(zip(("ms_head", "ms_lf", "ms_groups", "ms_recon", "ms_call"), map(float, ms)))
+
+    def _decode_batch_call(self, fn, datas, ptrs, strides):
+        """one jxg_decode_batch_rgb8[_device] call -> (call status, frame statuses)"""
+        n = len(datas)
+        sz = ctypes.c_size_t
+        c_datas = (ctypes.c_char_p * n)(*[d if d else None for d in datas])
+        c_sizes = (sz * n)(*[len(d) for d in datas])
+        c_ptrs = (ctypes.c_void_p * n)(*ptrs)
+        c_strides = (sz * n)(*strides)
+        st = (ctypes.c_int * n)()
+        ret = fn(self._ctx, c_datas, c_sizes, n, c_ptrs, c_strides, st)
+        return ret, [int(v) for v in st]
+
+    @staticmethod
+    def _batch_call_failed(ret, st):
+        """the call itself failed (as opposed to frames of it): its arguments were
+        refused with no status written, or a device / memory error filled them all"""
+        return ret != 0 and (not any(st) or ret not in (-1, -5))
+
+    def decode_batch(self, datas, strict: bool = True):
+        """Codestreams -> list of (H, W, 3) uint8 arrays, decoded on the GPU in
+        one call (jxg_decode_batch_rgb8): the pass groups of all frames share
+        the pass-group launches.  Frames may differ in size, coder, presets and
+        filters; each result equals :meth:`decode` of that stream.  Raises
+        JxgError on the first frame that is refused; with ``strict=False``
+        returns ``(arrays, statuses)`` instead, with None for a refused frame
+        and its jxg_status (0 for a decoded one).  Afterwards
+        :meth:`reconstruct` raises until the next :meth:`encode`."""
+        datas = [bytes(d) for d in datas]
+        if not datas:
+            return [] if strict else ([], [])
+        outs = []
+        for d in datas:
+            info = _StreamInfo()
+            if d and load().jxg_decode_info(d, len(d), ctypes.byref(info)) == 0:
+                outs.append(np.empty((info.ysize, info.xsize, 3), dtype=np.uint8))
+            else:  # the call refuses the stream as well, with the frame's status
+                outs.append(np.empty((1, 1, 3), dtype=np.uint8))
+        ret, st = self._decode_batch_call(load().jxg_decode_batch_rgb8, datas,
+                                          [o.ctypes.data for o in outs],
+                                          [o.shape[1] * 3 for o in outs])
+        if strict or self._batch_call_failed(ret, st):
+            _check(ret)
+        if strict:
+            return outs
+        return [o if s == 0 else None for o, s in zip(outs, st)], st
+
+    def decode_batch_device(self, datas, ptrs, row_strides=None) -> list:
+        """The same images written to device pointers (rows of row_strides[i]
+        bytes, default 3 * width); returns the frames' statuses when the images
+        are complete (jxg_decode_batch_rgb8_device)."""
+        datas = [bytes(d) for d in datas]
+        if row_strides is None:
+            row_strides = [stream_info(d)["xsize"] * 3 for d in datas]
+        ret, st = self._decode_batch_call(load().jxg_decode_batch_rgb8_device, datas, list(ptrs),
+                                          list(row_strides))
+        if self._batch_call_failed(ret, st):
+            _check(ret)
+        return st
+
+    def decode_batch_timings(self) -> dict:
+        """Counts and milliseconds of the last :meth:`decode_batch`
+        (jxg_decode_batch_timings): frames, chunks, work items launched with
+        their tables staged in LDS / not, host parse, pass-group launches and
+        reconstruction chains (device time by events), the whole call."""
+        s = _DecodeBatchStats()
+        _check(load().jxg_decode_batch_timings(self._ctx, ctypes.byref(s)))
+        return {k: (int if t is ctypes.c_uint32 else float)(getattr(s, k))
+                for k, t in _DecodeBatchStats._fields_}
+
+    def set_decode_batch_bytes(self, nbytes: int = 0) -> None:
+        """Device-memory budget of one chunk of :meth:`decode_batch`
+        (jxg_set_decode_batch_bytes); 0: the default, 2 GiB."""
+        _check(load().jxg_set_decode_batch_bytes(self._ctx, nbytes))
 
     def encode_batch(self, frames) -> list:
         """Host frames of equal size, each (H, W, 3) uint8 -> list of codestream

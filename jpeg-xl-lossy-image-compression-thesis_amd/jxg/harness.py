@@ -190,6 +190,23 @@ def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_siz
                    ssim, result_file)
 
 
+def compare_batch_to_orig(encoder, items, decode_with, result_file: str | None = None,
+                          ssim: bool = True):
+    """compare_to_orig(..., decode_with=) of many files with one decode: the
+    harness decodes every compressed file it wrote (benchmark.rs:637-660), and
+    one frame's pass-group kernel leaves the GPU almost idle, so all items'
+    codestreams go through ``decode_with.decode_batch`` (jxg_decode_batch_rgb8)
+    and each decoded image is then compared as compare_to_orig does.  ``items``:
+    tuples ``(orig_name, orig_rgb, orig_file_size, comp_name, codestream,
+    comp_file_size, distance, effort)``.  Returns the records in order, equal
+    to per-item compare_to_orig; the CSV rows are written in that order."""
+    items = list(items)
+    decoded = decode_with.decode_batch([it[4] for it in items])
+    return [compare_to_orig(encoder, it[0], it[1], it[2], it[3], rgb, it[5], it[6], it[7],
+                            result_file=result_file, ssim=ssim)
+            for it, rgb in zip(items, decoded)]
+
+
 def _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_size, raw, q, ssim,
             result_file) -> ComparisonResult:
     res = ComparisonResult(

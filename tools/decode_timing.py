@@ -5,11 +5,14 @@ benchmark's headline frame (8K synth_rgb8, d1 e7, cjxl defaults) and of a
 the pass-group kernel and the reconstruction chain (device time by events),
 next to jxg_reconstruct_rgb8_device of the same encode.
 
-    python tools/decode_timing.py [--reps 15] [--recon-only]
+    python tools/decode_timing.py [--reps 15] [--recon-only] [--batch N]
 
 Warm context, `--reps` repetitions, median and min..max.  --recon-only: the
 reconstruct time alone (what a library without the decoder can run, for the
-comparison with the commit before it).  Prints one JSON line per frame."""
+comparison with the commit before it).  --batch N: N 1080p frames and N / 8
+8K frames (different seeds) through one jxg_decode_batch_rgb8_device call,
+next to the same frames through jxg_decode_rgb8_device one at a time.  Prints
+one JSON line per frame size."""
 import argparse
 import json
 import os
@@ -31,11 +34,73 @@ def spread(v):
             "max": round(max(v), 3)}
 
 
+def batch(args):
+    """the batch call against the sequence of single calls on the same frames"""
+    for name, w, h, seed, n in (("1080p", 1920, 1080, SEED_BASE + 3, args.batch),
+                                ("8k", 7680, 4320, SEED_BASE + 2, max(1, args.batch // 8))):
+        with jxg.Encoder(distance=1.0, effort=7, flags=jxg.FLAGS_CJXL_DEFAULTS) as enc:
+            datas, longest = [], 0
+            for i in range(n):
+                img = synth_rgb8_device(w, h, seed + 16 * i, 0)
+                torch.cuda.synchronize()
+                datas.append(enc.encode_device(img.data_ptr(), w, h))
+                longest = max(longest, int(enc.stats()["ac_tokens"].sum(axis=1).max()))
+            del img
+            outs = [torch.empty((h, w, 3), dtype=torch.uint8, device="cuda") for _ in range(n)]
+            ptrs = [o.data_ptr() for o in outs]
+            torch.cuda.synchronize()
+            seq_keys = ("ms_head", "ms_lf", "ms_groups", "ms_recon", "ms_call")
+            seq = {k: [] for k in ("ms_wall",) + seq_keys}
+            for rep in range(args.reps + 2):
+                t0 = time.perf_counter()
+                acc = dict.fromkeys(seq_keys, 0.0)
+                for d, p in zip(datas, ptrs):
+                    enc.decode_device(d, p, w * 3)
+                    t = enc.decode_timings()
+                    for k in seq_keys:
+                        acc[k] += t[k]
+                if rep >= 2:
+                    seq["ms_wall"].append((time.perf_counter() - t0) * 1e3)
+                    for k in seq_keys:
+                        seq[k].append(acc[k])
+            want = [o.clone() for o in outs]
+            for o in outs:
+                o.zero_()
+            torch.cuda.synchronize()
+            bat_keys = ("ms_parse", "ms_groups", "ms_recon", "ms_call")
+            bat = {k: [] for k in ("ms_wall",) + bat_keys}
+            for rep in range(args.reps + 2):
+                t0 = time.perf_counter()
+                st = enc.decode_batch_device(datas, ptrs, [w * 3] * n)
+                wall = (time.perf_counter() - t0) * 1e3
+                assert not any(st), st
+                t = enc.decode_batch_timings()
+                if rep >= 2:
+                    bat["ms_wall"].append(wall)
+                    for k in bat_keys:
+                        bat[k].append(t[k])
+            assert all(torch.equal(o, r) for o, r in zip(outs, want)), "batch differs from single"
+            res = {"frames": "%d x %s %dx%d synth_rgb8 d1 e7 cjxl defaults" % (n, name, w, h),
+                   "bytes": sum(map(len, datas)), "reps": args.reps,
+                   "chunks": t["chunks"], "items_staged": t["items_staged"],
+                   "items_unstaged": t["items_unstaged"], "longest_group_tokens": longest,
+                   "sequence": {k: spread(v) for k, v in seq.items()},
+                   "batch": {k: spread(v) for k, v in bat.items()}}
+            res["speedup_wall"] = round(statistics.median(seq["ms_wall"]) /
+                                        statistics.median(bat["ms_wall"]), 2)
+            res["batch_ns_per_token_longest_chain"] = round(
+                1e6 * statistics.median(bat["ms_groups"]) / longest, 2)
+            print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--recon-only", action="store_true")
+    ap.add_argument("--batch", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.batch:
+        return batch(args)
     for name, w, h, seed in (("8k", 7680, 4320, SEED_BASE + 2), ("1080p", 1920, 1080, SEED_BASE + 3)):
         with jxg.Encoder(distance=1.0, effort=7, flags=jxg.FLAGS_CJXL_DEFAULTS) as enc:
             img = synth_rgb8_device(w, h, seed, 0)
