@@ -349,6 +349,9 @@ static size_t group_tokens(const jxo_frame* f, const jxo_result* r, int g,
   const uint32_t gw = (f->bxs - bx0) < 32 ? f->bxs - bx0 : 32;
   const uint32_t gh = (f->bys - by0) < 32 ? f->bys - by0 : 32;
   int32_t nzs[3][32 * 32];
+  /* (blocks a varblock of a neighbouring group covers are never filled here:
+   * they predict from 0, as jxl_decode.py's zero-initialised map does) */
+  memset(nzs, 0, sizeof(nzs));
   size_t n = 0;
   for (uint32_t by = 0; by < gh; by++)
     for (uint32_t bx = 0; bx < gw; bx++) {
@@ -376,8 +379,10 @@ static size_t group_tokens(const jxo_frame* f, const jxo_result* r, int g,
           pred = nzs[c][by * 32 + bx - 1];
         else
           pred = (nzs[c][(by - 1) * 32 + bx] + nzs[c][by * 32 + bx - 1] + 1) / 2;
-        for (int iy = 0; iy < cyb; iy++)
-          for (int ix = 0; ix < cxb; ix++)
+        /* (a varblock that jxo_encode_maps lets cross its pass group: the
+         * part inside, as jxl_decode.py's slice assignment clips it) */
+        for (int iy = 0; iy < cyb && by + iy < 32; iy++)
+          for (int ix = 0; ix < cxb && bx + ix < 32; ix++)
             nzs[c][(by + iy) * 32 + bx + ix] = (nz + cb - 1) >> lcb;
         const int bctx = jxo_default_ctx_map[(c < 2 ? c ^ 1 : 2) * JXO_NUM_ORDERS + ord];
         size_t n0 = n;
@@ -464,6 +469,206 @@ static void put_toc_entry(jxo_bw* w, uint32_t s) {
   else if (s < 17408) put_u32_sel(w, 1, 14, s - 1024);
   else if (s < 4211712) put_u32_sel(w, 2, 22, s - 17408);
   else put_u32_sel(w, 3, 30, s - 4211712);
+}
+
+/* ---------------------- codestream from the maps ---------------------- */
+/* everything after the transform stages: reads only the frame geometry, the
+ * parameters and out's maps (acs, qf, dc, ac, cmap, sizes, scales); fills
+ * out->ac_tokens and out->bytes */
+static int encode_from_maps(const jxo_frame* f, const jxo_params* p, jxo_result* out) {
+  /* ---- AC tokens and clustered histograms ---- */
+  /* (debug: the largest count of one (static cluster, token) bin inside one
+   * pass group -- what a group's LDS histogram on the GPU must hold) */
+  uint32_t dbg_max_bin = 0;
+  actok** gt = (actok**)malloc(sizeof(actok*) * f->ngroups);
+  size_t* gn = (size_t*)malloc(sizeof(size_t) * f->ngroups);
+  static uint32_t hist[JXO_MAX_CLUSTERS][JXO_ALPHA];
+  memset(hist, 0, sizeof(hist));
+#pragma omp parallel
+  {
+    static _Thread_local uint32_t lh[JXO_MAX_CLUSTERS][JXO_ALPHA];
+    memset(lh, 0, sizeof(lh));
+    /* one worst-case token buffer per thread, reused by its groups; each
+     * group keeps an exact-size copy (510 concurrent 1.5 MB allocations per
+     * 8K frame used to serialise the threads on page faults) */
+    actok* scratch = (actok*)malloc(sizeof(actok) * 32 * 32 * 3 * 64);
+#pragma omp for schedule(dynamic)
+    for (uint32_t g = 0; g < f->ngroups; g++) {
+      gn[g] = group_tokens(f, out, (int)g, scratch, out->ac_tokens + g * 3);
+      gt[g] = (actok*)malloc(sizeof(actok) * (gn[g] ? gn[g] : 1));
+      memcpy(gt[g], scratch, sizeof(actok) * gn[g]);
+      for (size_t i = 0; i < gn[g]; i++) {
+        uint32_t tok, nbt, bits;
+        jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nbt, &bits);
+        lh[jxo_ac_cluster(gt[g][i].ctx)][tok]++;
+      }
+      if (jxo_debug_group_bins) {
+        uint32_t* gh = (uint32_t*)calloc(JXO_MAX_CLUSTERS * JXO_ALPHA, 4);
+        uint32_t mx = 0;
+        for (size_t i = 0; i < gn[g]; i++) {
+          uint32_t tok, nbt, bits;
+          jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nbt, &bits);
+          const uint32_t v = ++gh[jxo_ac_cluster(gt[g][i].ctx) * JXO_ALPHA + tok];
+          mx = v > mx ? v : mx;
+        }
+        free(gh);
+#pragma omp critical
+        dbg_max_bin = mx > dbg_max_bin ? mx : dbg_max_bin;
+      }
+    }
+    free(scratch);
+#pragma omp critical
+    for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++)
+      for (int s = 0; s < JXO_ALPHA; s++) hist[cl][s] += lh[cl][s];
+  }
+  if (jxo_debug_group_bins) *jxo_debug_group_bins = dbg_max_bin;
+  /* prefix codes: one histogram per static cluster.  ANS: the static
+   * clusters are clustered again into <= JXO_ANS_MAX_HISTS centres
+   * (jxo_ans_cluster).  Dense ids in order of first appearance over contexts. */
+  int group[JXO_MAX_CLUSTERS]; /* static cluster -> histogram group (-1: empty) */
+  int ngrp = 0;
+  if (p->coder == 1) {
+    ngrp = jxo_ans_cluster((const uint32_t(*)[JXO_ALPHA])hist, JXO_MAX_CLUSTERS, group);
+  } else {
+    for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++) {
+      uint64_t tot = 0;
+      for (int s = 0; s < JXO_ALPHA; s++) tot += hist[cl][s];
+      group[cl] = tot ? ngrp++ : -1;
+    }
+  }
+  int dense[JXO_MAX_CLUSTERS];
+  for (int i = 0; i < JXO_MAX_CLUSTERS; i++) dense[i] = -1;
+  int nhist = 0;
+  uint8_t* ctxmap = (uint8_t*)malloc(JXO_AC_CTX);
+  for (int ctx = 0; ctx < JXO_AC_CTX; ctx++) {
+    const int gr = group[jxo_ac_cluster(ctx)];
+    if (gr >= 0 && dense[gr] < 0) dense[gr] = nhist++;
+    ctxmap[ctx] = (uint8_t)(gr < 0 ? 0 : dense[gr]);
+  }
+  static uint32_t dhist[JXO_MAX_CLUSTERS][JXO_ALPHA];
+  memset(dhist, 0, sizeof(dhist));
+  for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++)
+    if (group[cl] >= 0 && dense[group[cl]] >= 0)
+      for (int s = 0; s < JXO_ALPHA; s++) dhist[dense[group[cl]]][s] += hist[cl][s];
+  jxo_prefix* codes = (jxo_prefix*)malloc(sizeof(jxo_prefix) * (nhist ? nhist : 1));
+  jxo_ans* ans = p->coder == 1 ? (jxo_ans*)malloc(sizeof(jxo_ans) * (nhist ? nhist : 1)) : NULL;
+  for (int h = 0; h < nhist; h++) {
+    if (ans)
+      jxo_ans_normalize(dhist[h], &ans[h]);
+    else
+      jxo_build_prefix(dhist[h], JXO_ALPHA, &codes[h]);
+  }
+
+  /* ---- sections ---- */
+  const int nsec = (f->ngroups == 1) ? 1 : (int)(2 + f->nlf + f->ngroups);
+  jxo_bw* sec = (jxo_bw*)malloc(sizeof(jxo_bw) * (2 + f->nlf + f->ngroups));
+  const int nparts = (int)(2 + f->nlf + f->ngroups);
+  for (int i = 0; i < nparts; i++) jxo_bw_init(&sec[i]);
+  /* LfGlobal */
+  {
+    jxo_bw* s = &sec[0];
+    jxo_bw_put(s, 1, 1); /* LfChannelDequantization.all_default */
+    if (f->G <= 2048) put_u32_sel(s, 0, 11, f->G - 1);
+    else if (f->G <= 4096) put_u32_sel(s, 1, 11, f->G - 2049);
+    else if (f->G <= 8192) put_u32_sel(s, 2, 12, f->G - 4097);
+    else put_u32_sel(s, 3, 16, f->G - 8193);
+    if (f->qdc == 16) jxo_bw_put(s, 2, 0);
+    else if (f->qdc <= 32) put_u32_sel(s, 1, 5, f->qdc - 1);
+    else if (f->qdc <= 256) put_u32_sel(s, 2, 8, f->qdc - 1);
+    else put_u32_sel(s, 3, 16, f->qdc - 1);
+    jxo_bw_put(s, 1, 1); /* BlockCtxMap default */
+    jxo_bw_put(s, 1, 1); /* ColorCorrelation DC all_default */
+    jxo_bw_put(s, 1, 0); /* GlobalModular: no global tree; 0 channels */
+  }
+#pragma omp parallel for schedule(dynamic)
+  for (uint32_t lg = 0; lg < f->nlf; lg++) lf_group_section(f, out, (int)lg, p->filters, &sec[1 + lg]);
+  {
+    jxo_bw* s = &sec[1 + f->nlf];
+    put_dequant_matrices(s, big_kind_mask(out->acs, (size_t)f->bxs * f->bys));
+    jxo_bw_put(s, ceil_log2(f->ngroups), 0); /* num_hf_presets - 1 */
+    put_u32_sel(s, 2, 0, 0);                /* used_orders = 0 */
+    if (!ans) {
+      put_histograms(s, JXO_AC_CTX, ctxmap, nhist, codes, &kCfg);
+    } else {
+      /* ANS: lz77 off, context map, use_prefix_code = 0, log_alpha 7 */
+      jxo_bw_put(s, 1, 0);
+      put_context_map(s, JXO_AC_CTX, ctxmap, nhist);
+      jxo_bw_put(s, 1, 0);
+      jxo_bw_put(s, 2, 7 - 5);
+      for (int h = 0; h < nhist; h++) { /* uint config at log_alpha 7 */
+        jxo_bw_put(s, 3, kCfg.split_exp);
+        if (kCfg.split_exp != 7) {
+          jxo_bw_put(s, ceil_log2(kCfg.split_exp + 1), kCfg.msb);
+          jxo_bw_put(s, ceil_log2(kCfg.split_exp - kCfg.msb + 1), kCfg.lsb);
+        }
+      }
+      for (int h = 0; h < nhist; h++) jxo_ans_write_hist(s, &ans[h]);
+    }
+  }
+#pragma omp parallel for schedule(dynamic)
+  for (uint32_t g = 0; g < f->ngroups; g++) {
+    jxo_bw* s = &sec[2 + f->nlf + g];
+    if (!ans) {
+      for (size_t i = 0; i < gn[g]; i++)
+        put_token(s, &codes[ctxmap[gt[g][i].ctx]], &kCfg, gt[g][i].v);
+    } else {
+      const size_t n = gn[g];
+      uint8_t* th = (uint8_t*)malloc(n + 1);
+      uint8_t* ts = (uint8_t*)malloc(n + 1);
+      uint8_t* tn = (uint8_t*)malloc(n + 1);
+      uint32_t* tb = (uint32_t*)malloc(sizeof(uint32_t) * (n + 1));
+      for (size_t i = 0; i < n; i++) {
+        uint32_t tok, nb, bits;
+        jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nb, &bits);
+        th[i] = ctxmap[gt[g][i].ctx];
+        ts[i] = (uint8_t)tok;
+        tn[i] = (uint8_t)nb;
+        tb[i] = bits;
+      }
+      jxo_ans_write_stream(s, ans, n, th, ts, tn, tb);
+      free(th);
+      free(ts);
+      free(tn);
+      free(tb);
+    }
+  }
+  free(ans);
+
+  /* ---- assemble ---- */
+  jxo_bw o;
+  jxo_bw_init(&o);
+  put_headers(&o, out->xsize, out->ysize, jxo_lf_code(p->filters, p->distance));
+  jxo_bw_put(&o, 1, 0); /* TOC not permuted */
+  jxo_bw_pad(&o);
+  if (nsec == 1) {
+    jxo_bw all;
+    jxo_bw_init(&all);
+    for (int i = 0; i < nparts; i++) jxo_bw_append(&all, &sec[i]);
+    put_toc_entry(&o, (uint32_t)((all.nbits + 7) / 8));
+    jxo_bw_pad(&o);
+    jxo_bw_pad(&all);
+    jxo_bw_append(&o, &all);
+    jxo_bw_free(&all);
+  } else {
+    for (int i = 0; i < nparts; i++) put_toc_entry(&o, (uint32_t)((sec[i].nbits + 7) / 8));
+    jxo_bw_pad(&o);
+    for (int i = 0; i < nparts; i++) {
+      jxo_bw_pad(&sec[i]);
+      jxo_bw_append(&o, &sec[i]);
+    }
+  }
+  out->nbytes = (o.nbits + 7) / 8;
+  out->bytes = (uint8_t*)malloc(out->nbytes);
+  memcpy(out->bytes, o.buf, out->nbytes);
+  jxo_bw_free(&o);
+  for (int i = 0; i < nparts; i++) jxo_bw_free(&sec[i]);
+  free(sec);
+  for (uint32_t g = 0; g < f->ngroups; g++) free(gt[g]);
+  free(gt);
+  free(gn);
+  free(ctxmap);
+  free(codes);
+  return 0;
 }
 
 /* ------------------------------ encode ------------------------------ */
@@ -604,199 +809,88 @@ int jxo_encode_rgb8(const uint8_t* rgb, uint32_t w, uint32_t h, size_t row_strid
   free(xyb);
   free(aqraw);
 
-  /* ---- AC tokens and clustered histograms ---- */
-  /* (debug: the largest count of one (static cluster, token) bin inside one
-   * pass group -- what a group's LDS histogram on the GPU must hold) */
-  uint32_t dbg_max_bin = 0;
-  actok** gt = (actok**)malloc(sizeof(actok*) * f.ngroups);
-  size_t* gn = (size_t*)malloc(sizeof(size_t) * f.ngroups);
-  static uint32_t hist[JXO_MAX_CLUSTERS][JXO_ALPHA];
-  memset(hist, 0, sizeof(hist));
-#pragma omp parallel
-  {
-    static _Thread_local uint32_t lh[JXO_MAX_CLUSTERS][JXO_ALPHA];
-    memset(lh, 0, sizeof(lh));
-    /* one worst-case token buffer per thread, reused by its groups; each
-     * group keeps an exact-size copy (510 concurrent 1.5 MB allocations per
-     * 8K frame used to serialise the threads on page faults) */
-    actok* scratch = (actok*)malloc(sizeof(actok) * 32 * 32 * 3 * 64);
-#pragma omp for schedule(dynamic)
-    for (uint32_t g = 0; g < f.ngroups; g++) {
-      gn[g] = group_tokens(&f, out, (int)g, scratch, out->ac_tokens + g * 3);
-      gt[g] = (actok*)malloc(sizeof(actok) * (gn[g] ? gn[g] : 1));
-      memcpy(gt[g], scratch, sizeof(actok) * gn[g]);
-      for (size_t i = 0; i < gn[g]; i++) {
-        uint32_t tok, nbt, bits;
-        jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nbt, &bits);
-        lh[jxo_ac_cluster(gt[g][i].ctx)][tok]++;
-      }
-      if (jxo_debug_group_bins) {
-        uint32_t* gh = (uint32_t*)calloc(JXO_MAX_CLUSTERS * JXO_ALPHA, 4);
-        uint32_t mx = 0;
-        for (size_t i = 0; i < gn[g]; i++) {
-          uint32_t tok, nbt, bits;
-          jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nbt, &bits);
-          const uint32_t v = ++gh[jxo_ac_cluster(gt[g][i].ctx) * JXO_ALPHA + tok];
-          mx = v > mx ? v : mx;
-        }
-        free(gh);
-#pragma omp critical
-        dbg_max_bin = mx > dbg_max_bin ? mx : dbg_max_bin;
-      }
-    }
-    free(scratch);
-#pragma omp critical
-    for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++)
-      for (int s = 0; s < JXO_ALPHA; s++) hist[cl][s] += lh[cl][s];
-  }
-  if (jxo_debug_group_bins) *jxo_debug_group_bins = dbg_max_bin;
-  /* prefix codes: one histogram per static cluster.  ANS: the static
-   * clusters are clustered again into <= JXO_ANS_MAX_HISTS centres
-   * (jxo_ans_cluster).  Dense ids in order of first appearance over contexts. */
-  int group[JXO_MAX_CLUSTERS]; /* static cluster -> histogram group (-1: empty) */
-  int ngrp = 0;
-  if (p->coder == 1) {
-    ngrp = jxo_ans_cluster((const uint32_t(*)[JXO_ALPHA])hist, JXO_MAX_CLUSTERS, group);
-  } else {
-    for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++) {
-      uint64_t tot = 0;
-      for (int s = 0; s < JXO_ALPHA; s++) tot += hist[cl][s];
-      group[cl] = tot ? ngrp++ : -1;
-    }
-  }
-  int dense[JXO_MAX_CLUSTERS];
-  for (int i = 0; i < JXO_MAX_CLUSTERS; i++) dense[i] = -1;
-  int nhist = 0;
-  uint8_t* ctxmap = (uint8_t*)malloc(JXO_AC_CTX);
-  for (int ctx = 0; ctx < JXO_AC_CTX; ctx++) {
-    const int gr = group[jxo_ac_cluster(ctx)];
-    if (gr >= 0 && dense[gr] < 0) dense[gr] = nhist++;
-    ctxmap[ctx] = (uint8_t)(gr < 0 ? 0 : dense[gr]);
-  }
-  static uint32_t dhist[JXO_MAX_CLUSTERS][JXO_ALPHA];
-  memset(dhist, 0, sizeof(dhist));
-  for (int cl = 0; cl < JXO_MAX_CLUSTERS; cl++)
-    if (group[cl] >= 0 && dense[group[cl]] >= 0)
-      for (int s = 0; s < JXO_ALPHA; s++) dhist[dense[group[cl]]][s] += hist[cl][s];
-  jxo_prefix* codes = (jxo_prefix*)malloc(sizeof(jxo_prefix) * (nhist ? nhist : 1));
-  jxo_ans* ans = p->coder == 1 ? (jxo_ans*)malloc(sizeof(jxo_ans) * (nhist ? nhist : 1)) : NULL;
-  for (int h = 0; h < nhist; h++) {
-    if (ans)
-      jxo_ans_normalize(dhist[h], &ans[h]);
-    else
-      jxo_build_prefix(dhist[h], JXO_ALPHA, &codes[h]);
-  }
+  return encode_from_maps(&f, p, out);
+}
 
-  /* ---- sections ---- */
-  const int nsec = (f.ngroups == 1) ? 1 : (int)(2 + f.nlf + f.ngroups);
-  jxo_bw* sec = (jxo_bw*)malloc(sizeof(jxo_bw) * (2 + f.nlf + f.ngroups));
-  const int nparts = (int)(2 + f.nlf + f.ngroups);
-  for (int i = 0; i < nparts; i++) jxo_bw_init(&sec[i]);
-  /* LfGlobal */
-  {
-    jxo_bw* s = &sec[0];
-    jxo_bw_put(s, 1, 1); /* LfChannelDequantization.all_default */
-    if (f.G <= 2048) put_u32_sel(s, 0, 11, f.G - 1);
-    else if (f.G <= 4096) put_u32_sel(s, 1, 11, f.G - 2049);
-    else if (f.G <= 8192) put_u32_sel(s, 2, 12, f.G - 4097);
-    else put_u32_sel(s, 3, 16, f.G - 8193);
-    if (f.qdc == 16) jxo_bw_put(s, 2, 0);
-    else if (f.qdc <= 32) put_u32_sel(s, 1, 5, f.qdc - 1);
-    else if (f.qdc <= 256) put_u32_sel(s, 2, 8, f.qdc - 1);
-    else put_u32_sel(s, 3, 16, f.qdc - 1);
-    jxo_bw_put(s, 1, 1); /* BlockCtxMap default */
-    jxo_bw_put(s, 1, 1); /* ColorCorrelation DC all_default */
-    jxo_bw_put(s, 1, 0); /* GlobalModular: no global tree; 0 channels */
-  }
-#pragma omp parallel for schedule(dynamic)
-  for (uint32_t lg = 0; lg < f.nlf; lg++) lf_group_section(&f, out, (int)lg, p->filters, &sec[1 + lg]);
-  {
-    jxo_bw* s = &sec[1 + f.nlf];
-    put_dequant_matrices(s, big_kind_mask(out->acs, (size_t)f.bxs * f.bys));
-    jxo_bw_put(s, ceil_log2(f.ngroups), 0); /* num_hf_presets - 1 */
-    put_u32_sel(s, 2, 0, 0);                /* used_orders = 0 */
-    if (!ans) {
-      put_histograms(s, JXO_AC_CTX, ctxmap, nhist, codes, &kCfg);
-    } else {
-      /* ANS: lz77 off, context map, use_prefix_code = 0, log_alpha 7 */
-      jxo_bw_put(s, 1, 0);
-      put_context_map(s, JXO_AC_CTX, ctxmap, nhist);
-      jxo_bw_put(s, 1, 0);
-      jxo_bw_put(s, 2, 7 - 5);
-      for (int h = 0; h < nhist; h++) { /* uint config at log_alpha 7 */
-        jxo_bw_put(s, 3, kCfg.split_exp);
-        if (kCfg.split_exp != 7) {
-          jxo_bw_put(s, ceil_log2(kCfg.split_exp + 1), kCfg.msb);
-          jxo_bw_put(s, ceil_log2(kCfg.split_exp - kCfg.msb + 1), kCfg.lsb);
-        }
-      }
-      for (int h = 0; h < nhist; h++) jxo_ans_write_hist(s, &ans[h]);
-    }
-  }
-#pragma omp parallel for schedule(dynamic)
-  for (uint32_t g = 0; g < f.ngroups; g++) {
-    jxo_bw* s = &sec[2 + f.nlf + g];
-    if (!ans) {
-      for (size_t i = 0; i < gn[g]; i++)
-        put_token(s, &codes[ctxmap[gt[g][i].ctx]], &kCfg, gt[g][i].v);
-    } else {
-      const size_t n = gn[g];
-      uint8_t* th = (uint8_t*)malloc(n + 1);
-      uint8_t* ts = (uint8_t*)malloc(n + 1);
-      uint8_t* tn = (uint8_t*)malloc(n + 1);
-      uint32_t* tb = (uint32_t*)malloc(sizeof(uint32_t) * (n + 1));
-      for (size_t i = 0; i < n; i++) {
-        uint32_t tok, nb, bits;
-        jxo_hybrid(gt[g][i].v, &kCfg, &tok, &nb, &bits);
-        th[i] = ctxmap[gt[g][i].ctx];
-        ts[i] = (uint8_t)tok;
-        tn[i] = (uint8_t)nb;
-        tb[i] = bits;
-      }
-      jxo_ans_write_stream(s, ans, n, th, ts, tn, tb);
-      free(th);
-      free(ts);
-      free(tn);
-      free(tb);
-    }
-  }
-  free(ans);
+/* ------------------------- encode from given maps ------------------------- */
+static int is_emitted(int t) {
+  return (t >= 0 && t <= 7) || (t >= 10 && t <= 13) || (t >= 18 && t <= 26);
+}
 
-  /* ---- assemble ---- */
-  jxo_bw o;
-  jxo_bw_init(&o);
-  put_headers(&o, w, h, jxo_lf_code(p->filters, p->distance));
-  jxo_bw_put(&o, 1, 0); /* TOC not permuted */
-  jxo_bw_pad(&o);
-  if (nsec == 1) {
-    jxo_bw all;
-    jxo_bw_init(&all);
-    for (int i = 0; i < nparts; i++) jxo_bw_append(&all, &sec[i]);
-    put_toc_entry(&o, (uint32_t)((all.nbits + 7) / 8));
-    jxo_bw_pad(&o);
-    jxo_bw_pad(&all);
-    jxo_bw_append(&o, &all);
-    jxo_bw_free(&all);
-  } else {
-    for (int i = 0; i < nparts; i++) put_toc_entry(&o, (uint32_t)((sec[i].nbits + 7) / 8));
-    jxo_bw_pad(&o);
-    for (int i = 0; i < nparts; i++) {
-      jxo_bw_pad(&sec[i]);
-      jxo_bw_append(&o, &sec[i]);
+int jxo_encode_maps(uint32_t w, uint32_t h, const jxo_params* p, const uint8_t* acs,
+                    const uint8_t* qf, const int32_t* dc, const int32_t* ac, const int8_t* cmap,
+                    jxo_result* out) {
+  memset(out, 0, sizeof(*out));
+  if (!acs || !qf || !dc || !ac || !cmap || w == 0 || h == 0 || w > (1u << 18) || h > (1u << 18))
+    return JXO_MAPS_BAD_ARG;
+  if (!(p->distance > 0.0f) || p->distance > 25.0f) return -2;
+  if (p->coder != 0 && p->coder != 1) return -3;
+  if (p->filters & ~(JXO_FILTER_GAB | JXO_FILTER_EPF | JXO_OPT_AQ_MASKING)) return -4;
+  jxo_frame f;
+  jxo_frame_init(&f, w, h, p);
+  const size_t nb = (size_t)f.bxs * f.bys;
+  /* the maps describe one consistent frame */
+  for (size_t i = 0; i < 3 * nb; i++)
+    if (dc[i] < JXO_MAPS_DC_MIN || dc[i] > JXO_MAPS_DC_MAX) return JXO_MAPS_DC_RANGE;
+  uint8_t* seen = (uint8_t*)calloc(nb, 1);
+  int st = 0;
+  for (uint32_t by = 0; by < f.bys && !st; by++)
+    for (uint32_t bx = 0; bx < f.bxs && !st; bx++) {
+      const size_t b = (size_t)by * f.bxs + bx;
+      if (seen[b]) continue;
+      const int t = acs[b];
+      if (t & 0x80) { /* a cover flag no head accounts for */
+        st = JXO_MAPS_COVER;
+        break;
+      }
+      if (!is_emitted(t)) {
+        st = JXO_MAPS_ID;
+        break;
+      }
+      const int si = jxo_shape_of(t);
+      const uint32_t cy = si < 0 ? 1 : jxo_shapes[si].cy, cx = si < 0 ? 1 : jxo_shapes[si].cx;
+      if (by + cy > f.bys || bx + cx > f.bxs) {
+        st = JXO_MAPS_FIT;
+        break;
+      }
+      for (uint32_t iy = 0; iy < cy && !st; iy++)
+        for (uint32_t ix = 0; ix < cx && !st; ix++) {
+          const size_t bi = (size_t)(by + iy) * f.bxs + bx + ix;
+          if (seen[bi] || ((iy | ix) && acs[bi] != (t | 0x80))) st = JXO_MAPS_COVER;
+          else if (qf[bi] != qf[b]) st = JXO_MAPS_QF;
+          seen[bi] = 1;
+        }
+      /* the slots the DC image carries: natural-order positions 0 .. cy cx - 1 */
+      const uint32_t cb = cy * cx;
+      for (uint32_t k = 0; k < cb && !st; k++) {
+        const size_t bi = (size_t)(by + (k >> 6) / cx) * f.bxs + bx + (k >> 6) % cx;
+        for (int c = 0; c < 3; c++)
+          if (ac[(bi * 3 + c) * 64 + (k & 63)] != 0) st = JXO_MAPS_LLF;
+      }
     }
-  }
-  out->nbytes = (o.nbits + 7) / 8;
-  out->bytes = (uint8_t*)malloc(out->nbytes);
-  memcpy(out->bytes, o.buf, out->nbytes);
-  jxo_bw_free(&o);
-  for (int i = 0; i < nparts; i++) jxo_bw_free(&sec[i]);
-  free(sec);
-  for (uint32_t g = 0; g < f.ngroups; g++) free(gt[g]);
-  free(gt);
-  free(gn);
-  free(ctxmap);
-  free(codes);
-  return 0;
+  free(seen);
+  if (st) return st;
+  out->xsize = w;
+  out->ysize = h;
+  out->bxs = f.bxs;
+  out->bys = f.bys;
+  out->global_scale = f.G;
+  out->quant_dc = f.qdc;
+  out->tiles_x = (f.bxs + 7) / 8;
+  out->tiles_y = (f.bys + 7) / 8;
+  const size_t ntiles = (size_t)out->tiles_x * out->tiles_y;
+  out->acs = (uint8_t*)malloc(nb);
+  out->qf = (uint8_t*)malloc(nb);
+  out->dc = (int32_t*)malloc(sizeof(int32_t) * nb * 3);
+  out->ac = (int32_t*)malloc(sizeof(int32_t) * nb * 192);
+  out->cmap = (int8_t*)malloc(2 * ntiles);
+  out->ac_tokens = (uint32_t*)calloc((size_t)f.ngroups * 3, sizeof(uint32_t));
+  memcpy(out->acs, acs, nb);
+  memcpy(out->qf, qf, nb);
+  memcpy(out->dc, dc, sizeof(int32_t) * nb * 3);
+  memcpy(out->ac, ac, sizeof(int32_t) * nb * 192);
+  memcpy(out->cmap, cmap, 2 * ntiles);
+  return encode_from_maps(&f, p, out);
 }
 
 #ifdef _OPENMP

@@ -100,6 +100,28 @@ typedef struct {
 
 int jxo_encode_rgb8(const uint8_t* rgb, uint32_t w, uint32_t h,
                     size_t row_stride, const jxo_params* p, jxo_result* out);
+/* The codestream of given maps (tests: streams no image produces).  Arrays in
+ * jxo_result's layout; global_scale and quant_dc follow from p->distance as in
+ * jxo_encode_rgb8, p->effort and p->proposals play no part.  ac is int32: a
+ * value outside int16 is written as it stands.  The maps must describe one
+ * consistent frame, or a JXO_MAPS_* code comes back and out stays empty; where a
+ * decoder may place a varblock (its tile / pass-group rule) is not checked. */
+enum {
+  JXO_MAPS_BAD_ARG = -1,   /* null array, empty or oversized frame (-2 .. -4: as jxo_encode_rgb8) */
+  JXO_MAPS_ID = -10,       /* a head's id is not one of the 21 the encoder emits */
+  JXO_MAPS_FIT = -11,      /* a varblock reaches past the frame's blocks */
+  JXO_MAPS_COVER = -12,    /* cover flags (0x80 | id) differ from the head's shape, or overlap */
+  JXO_MAPS_QF = -13,       /* qf varies inside a varblock */
+  JXO_MAPS_LLF = -14,      /* a non-zero coefficient in a slot the DC image carries */
+  JXO_MAPS_DC_RANGE = -15, /* dc outside [JXO_MAPS_DC_MIN, JXO_MAPS_DC_MAX] */
+};
+/* every residual of the DC image's predictors then packs into less than 2^31,
+ * which is what the hybrid-integer writer (entropy.c) takes */
+#define JXO_MAPS_DC_MIN (-(1 << 29))
+#define JXO_MAPS_DC_MAX ((1 << 29) - 1)
+int jxo_encode_maps(uint32_t w, uint32_t h, const jxo_params* p, const uint8_t* acs,
+                    const uint8_t* qf, const int32_t* dc, const int32_t* ac, const int8_t* cmap,
+                    jxo_result* out);
 void jxo_result_free(jxo_result* r);
 /* synthetic RGB8 frame (jxg/synth.py synth_rgb8), out: h*w*3 bytes */
 void jxo_synth_rgb8(uint32_t w, uint32_t h, uint64_t seed, uint8_t* out);

@@ -60,6 +60,9 @@ def lib():
         _lib = ctypes.CDLL(LIB)
         _lib.jxo_encode_rgb8.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                          ctypes.c_size_t, ctypes.POINTER(_Params), ctypes.POINTER(_Result)]
+        _lib.jxo_encode_maps.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_Params),
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_Result)]
         _lib.jxo_result_free.argtypes = [ctypes.POINTER(_Result)]
         _lib.jxo_homog_map.argtypes = [ctypes.POINTER(_Xyb), ctypes.c_float, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p]
@@ -112,6 +115,11 @@ def encode(rgb: np.ndarray, distance=1.0, effort=7, proposals=0, coder=0,
     st = lib().jxo_encode_rgb8(rgb.ctypes.data, w, h, w * 3, ctypes.byref(p), ctypes.byref(r))
     if st != 0:
         raise RuntimeError("oracle encode failed: %d" % st)
+    return _take(r, w, h)
+
+
+def _take(r, w, h) -> OracleResult:
+    """copy a filled jxo_result into numpy arrays and free it"""
     try:
         o = OracleResult()
         nb = r.bxs * r.bys
@@ -131,6 +139,42 @@ def encode(rgb: np.ndarray, distance=1.0, effort=7, proposals=0, coder=0,
         return o
     finally:
         lib().jxo_result_free(ctypes.byref(r))
+
+
+# jxo.h JXO_MAPS_*: what jxo_encode_maps refuses
+MAPS_BAD_ARG, MAPS_ID, MAPS_FIT, MAPS_COVER, MAPS_QF, MAPS_LLF, MAPS_DC_RANGE = (
+    -1, -10, -11, -12, -13, -14, -15)
+MAPS_DC_MIN, MAPS_DC_MAX = -(1 << 29), (1 << 29) - 1
+
+
+class MapsError(RuntimeError):
+    def __init__(self, code):
+        RuntimeError.__init__(self, "oracle encode_maps refused the maps: %d" % code)
+        self.code = code
+
+
+def encode_maps(w: int, h: int, acs, qf, dc, ac, cmap, distance=1.0, coder=0,
+                filters=0) -> OracleResult:
+    """The codestream of given maps (jxo_encode_maps): acs, qf (bys, bxs) uint8, dc
+    (3, bys, bxs) int32, ac (bys, bxs, 3, 64) int32, cmap (2, tiles down, tiles
+    across) int8 -- the layout of :func:`encode`'s result.  Raises MapsError
+    with the JXO_MAPS_* code when the maps are not one consistent frame."""
+    bxs, bys = (w + 7) // 8, (h + 7) // 8
+    arrs = []
+    for a, dt, shape in ((acs, np.uint8, (bys, bxs)), (qf, np.uint8, (bys, bxs)),
+                         (dc, np.int32, (3, bys, bxs)), (ac, np.int32, (bys, bxs, 3, 64)),
+                         (cmap, np.int8, (2, (bys + 7) // 8, (bxs + 7) // 8))):
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.shape != shape:
+            raise ValueError("expected shape %r, got %r" % (shape, a.shape))
+        arrs.append(a)
+    p = _Params(distance, 4, 0, coder, filters)
+    r = _Result()
+    st = lib().jxo_encode_maps(w, h, ctypes.byref(p), *[a.ctypes.data for a in arrs],
+                               ctypes.byref(r))
+    if st != 0:
+        raise MapsError(st)
+    return _take(r, w, h)
 
 
 def _xyb_struct(planes: np.ndarray):

@@ -192,18 +192,36 @@ def decode_mutate_bin(tmp_path_factory):
     return str(exe), bool(san)
 
 
-@pytest.mark.parametrize("name", ["natural_d12_all", "gradient_e8"])
-def test_corrupted_streams_never_leave_their_buffers(decode_mutate_bin, oracle, tmp_path, name):
+def _crafted_stream(which):
+    import crafted
+
+    case = crafted.most_unaligned_s1() if which == "crafted_s1" else next(
+        c for c in crafted.families()["S4"] if c.name == "s4_dense64")
+    return crafted.stream(case)
+
+
+@pytest.mark.parametrize("name,changes,cuts", [("natural_d12_all", "2000", "200"),
+                                               ("gradient_e8", "2000", "200"),
+                                               ("crafted_s1", "500", "50"),
+                                               ("crafted_dense64", "500", "50")],
+                         ids=["natural_d12_all", "gradient_e8", "crafted_s1", "crafted_dense64"])
+def test_corrupted_streams_never_leave_their_buffers(decode_mutate_bin, oracle, tmp_path, name,
+                                                     changes, cuts):
     """2000 single-byte changes spread over every section and 200 truncations
     of the 333x222 d12 and the 768x520 effort-8 streams, decoded on the host
-    path under ASan + UBSan: every call returns a status, no report"""
+    path under ASan + UBSan: every call returns a status, no report.  And 500 /
+    50 of two crafted streams (tests/crafted.py): the 512x512 frame with the
+    most placements off their shape's grid, and the 64x64 px varblock whose
+    4032 coefficients are all non-zero -- the walk runs on such placements
+    under the sanitizers before they go near a GPU"""
     exe, sanitized = decode_mutate_bin
-    ref = _oracle_encode(oracle, _by_name(name))
+    data = (_crafted_stream(name) if name.startswith("crafted")
+            else _oracle_encode(oracle, _by_name(name)).bytes)
     path = tmp_path / (name + ".jxl")
-    path.write_bytes(ref.bytes)
+    path.write_bytes(data)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
                UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, str(path), "2000", "200"], capture_output=True, text=True,
+    r = subprocess.run([exe, str(path), changes, cuts], capture_output=True, text=True,
                        timeout=600, env=env)
     print(r.stdout.strip(), "(sanitizers: %s)" % ("on" if sanitized else "NOT available"))
     assert r.returncode == 0, r.stdout + r.stderr
