@@ -25,8 +25,10 @@
 
 #include "../../include/jxg.h"
 #include "jxg_bitstream.h"
+#include "jxg_codes.h"
 #include "jxg_device.h"
 #include "jxg_kernels.h"
+#include "jxg_layout.h"
 #include "jxg_plan.h"
 
 #pragma GCC visibility push(hidden)
@@ -65,19 +67,6 @@ struct DevBuf {
   }
 };
 
-// A typed window into an arena (Ctx::stat / up and their host mirrors): the
-// arena is laid out per frame by stage_alloc, so ensure() only checks.
-template <class T>
-struct View {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t count) const { return count <= n ? hipSuccess : hipErrorInvalidValue; }
-  void set(void* base, size_t byte_off, size_t count) {
-    p = reinterpret_cast<T*>(static_cast<uint8_t*>(base) + byte_off);
-    n = count;
-  }
-};
-
 template <class T>
 struct PinBuf {
   T* p = nullptr;
@@ -102,6 +91,21 @@ inline float ms_since(Clock::time_point t0) {
   return std::chrono::duration<float, std::milli>(Clock::now() - t0).count();
 }
 
+// the encoder's events of one frame (Ctx::ev), in the order they are recorded
+enum EncEvent : int {
+  kEvStart = 0,       // frame start
+  kEvFrontStart = 9,  // masking quant field done / front kernel start
+  kEvFrontDone = 5,   // front kernel done
+  kEvMerged = 1,      // transform and merge done
+  kEvAcStats = 6,     // AC statistics on the host (stage_download_ac)
+  kEvLfStats = 2,     // LF statistics downloaded (stage_download_lf)
+  kEvAcEmitted = 7,   // AC emission done and its bit counts on the host
+  kEvEmitted = 3,     // emission done
+  kEvAcBlock = 8,     // AC block in host memory (stage_concat_split)
+  kEvAssembled = 4,   // codestream assembled
+  kNumEncEvents = 10
+};
+
 struct Ctx;
 struct Job;
 struct Pipe;
@@ -114,16 +118,13 @@ struct CtxDeleter {
 struct PipeDeleter {  // (Pipe is private to jxg_pipe.cpp)
   void operator()(Pipe* p) const;
 };
-struct Ctx {
+struct Ctx : EncArenas {
   jxg_params params{};
   std::vector<std::unique_ptr<Ctx, CtxDeleter>> lanes;
   PinBuf<uint8_t> h_stage;  // pinned staging of one host frame (pipeline lanes)
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // AC-block concat + D2H (stage_concat_split)
-  // ev[6]: AC statistics downloaded (stage_download_ac); ev[7]: AC emission
-  // done and its bit counts on the host; ev[8]: AC block in host memory;
-  // ev[9]: masking quant field done (front kernel start)
-  hipEvent_t ev[10] = {};
+  hipEvent_t ev[kNumEncEvents] = {};  // by EncEvent
   bool constants_ready = false;
   // device
   DevBuf<uint8_t> rgb, acs, qf, aqf;  // aqf: masking quant field (JXG_FLAG_AQ_MASKING)
@@ -145,26 +146,10 @@ struct Ctx {
   DevBuf<uint8_t> type;
   DevBuf<uint32_t> stream_chunks, scratch, scratch_lf, out;
   DevBuf<uint64_t> lfstatus;  // [nchunks] lf_code look-back words
-  // Per-frame statistics, zeroed by the front kernel and downloaded by two copies
-  // (AC part, LF part): [hist_ac | bound | ntok | bandtok | bigcount][lfhist | sbound | vcount]
-  DevBuf<uint8_t> stat;
-  PinBuf<uint8_t> h_stat;
-  View<uint32_t> hist_ac, bound, ntok, bandtok, bigcount, lfhist, sbound, vcount;
-  View<uint32_t> h_hist_ac, h_bound, h_ntok, h_bigcount, h_lfhist, h_sbound, h_vcount;
-  size_t stat_lf = 0, stat_bytes = 0;  // byte offset of the LF part, total
-  // Per-frame code tables, uploaded by one copy (ANS) or two (prefix codes:
-  // the AC part ahead of the AC emission): [codes_ac | gbase | ans_order |
-  // ans_tab][lfcodes | stream_base]
-  DevBuf<uint8_t> up;
-  PinBuf<uint8_t> h_up;
-  View<uint32_t> codes_ac, ans_order, lfcodes, h_codes_ac, h_ans_order, h_lfcodes;
-  View<uint64_t> gbase, stream_base, h_gbase, h_sbase;
-  View<uint8_t> ans_tab, h_ans_tab;
-  size_t up_gbase = 0, up_ac = 0, up_lf = 0, up_bytes = 0;
-  // emitted bit counts, one download: [gbits | stream_bits]
-  DevBuf<uint32_t> bits;
-  PinBuf<uint32_t> h_bits;
-  View<uint32_t> gbits, stream_bits, h_gbits, h_sbits;
+  // the per-frame statistics, code-table and bit-count arenas (EncArenas:
+  // the sections and partial-copy boundaries) and their pinned mirrors
+  DevBuf<uint8_t> stat, up, bits;
+  PinBuf<uint8_t> h_stat, h_up, h_bits;
   uint32_t* lf_scratch = nullptr;  // LF-stream bit arena (scratch_lf, or in scratch)
   DevBuf<uint32_t> tile_list, glist;  // shard: tile ids, pass groups (non-contiguous plans)
   DevBuf<uint32_t> tokens, tval, ans_state, csum;  // ANS coder
@@ -232,10 +217,7 @@ struct Ctx {
   std::vector<LfRow> rows_h_cache;
   std::vector<LfChunk> chunks_h_cache;
   std::vector<uint32_t> schunks_cache;
-  // serialised AC context map of the previous frame (reused when equal)
-  std::vector<uint8_t> cm_last;
-  int cm_nhist = -1;
-  BitWriter cm_bits;
+  CtxMapCache ctxmap_cache;  // serialised AC context map of the previous frame
   std::vector<uint8_t> m_acs, m_qf;
   std::vector<int32_t> m_dc, m_ac;
   std::vector<uint32_t> m_ntok;

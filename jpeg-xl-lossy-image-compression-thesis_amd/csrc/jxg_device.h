@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jxg_acmodel.h"
+
 namespace jxg {
 
 // raw AcStrategy ids returned by the thesis selector
@@ -134,34 +136,7 @@ __device__ __constant__ static const uint16_t kNnzCtx[64] = {
     180, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206,
     206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206};
 
-constexpr int kBlockCtx = 15, kNzBuckets = 37, kZdCtx = 458;
-constexpr int kAcCtx = kBlockCtx * (kNzBuckets + kZdCtx);  // 7425
-constexpr int kMaxClusters = 132;
-constexpr int kAlpha = 128;
-
-__host__ __device__ __forceinline__ int bclass(int bctx) {
-  if (bctx < 7) return bctx == 0 ? 0 : (bctx == 1 ? 1 : 2);
-  return bctx == 7 ? 3 : (bctx == 8 ? 4 : 5);
-}
-// static clustering of the 7425 AC contexts (the map is transmitted)
-__host__ __device__ __forceinline__ int ac_cluster(int ctx) {
-  if (ctx < kBlockCtx * kNzBuckets) {
-    int bucket = ctx / kBlockCtx, bctx = ctx % kBlockCtx;
-    int nb = bucket == 0 ? 0 : (bucket <= 2 ? 1 : (bucket <= 8 ? 2 : 3));
-    return bclass(bctx) * 4 + nb;
-  }
-  int z = ctx - kBlockCtx * kNzBuckets;
-  int bctx = z / kZdCtx, zz = z % kZdCtx;
-  int prev = zz & 1, base = zz >> 1;
-  int bi = base >= 206 ? 7 : base >= 180 ? 6 : base >= 152 ? 5 : base >= 123 ? 4
-         : base >= 93 ? 3 : base >= 62 ? 2 : base >= 31 ? 1 : 0;
-  const int nzb_base = bi == 7 ? 206 : bi == 6 ? 180 : bi == 5 ? 152 : bi == 4 ? 123
-                     : bi == 3 ? 93 : bi == 2 ? 62 : bi == 1 ? 31 : 0;
-  int fc = base - nzb_base;
-  int nzg = bi < 2 ? 0 : (bi < 4 ? 1 : 2);
-  int fg = fc < 4 ? 0 : (fc < 12 ? 1 : 2);
-  return 24 + ((bclass(bctx) * 3 + nzg) * 3 + fg) * 2 + prev;
-}
+// (the context model's sizes, bclass and ac_cluster: jxg_acmodel.h)
 
 __host__ __device__ __forceinline__ uint32_t pack_signed(int32_t v) {
   return v >= 0 ? (uint32_t)v * 2u : (uint32_t)(-(int64_t)v) * 2u - 1u;

@@ -1,13 +1,17 @@
 // jxg_encode.cpp -- the encoder's stages A-H and the phases of one frame
 // (jxg_ctx.h has the pipeline's outline); the one-at-a-time entry points'
-// bodies.  The streaming pipeline (jxg_pipe.cpp) and the sharded encode
+// bodies.  What a stage does on the GPU is here: buffers, launches, copies,
+// events.  What the host computes for it is host-only code next door: the
+// frame plan (jxg_plan.cpp), the codes and arena layouts of stage F
+// (jxg_codes.cpp), the codestream layout of stage H (jxg_layout.cpp).  The
+// streaming pipeline (jxg_pipe.cpp) and the sharded encode
 // (jxg_shard_host.cpp) run the same stages.
 #include "jxg_ctx.h"
 
 #include <cstdlib>
 #include <cstring>
 
-#include "jxg_layout.h"
+#include "jxg_codes.h"
 #include "jxg_tables.h"
 
 namespace jxg {
@@ -87,7 +91,7 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
     JXG_HIP(c->mwork.ensure(1 + (size_t)ntiles * kNumShapes));
   }
   // the plan's tile, LF-group and pass-group lists: uploaded when the plan
-  // changes (the same key as the LF row cache below)
+  // changes (one key for them and the LF row cache below)
   const bool new_plan = c->rows_w != J.w || c->rows_h != J.h || c->rows_rank != J.plan.rank ||
                         c->rows_world != J.plan.world;
   if (!J.plan.tiles.empty()) {
@@ -105,88 +109,20 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
   JXG_HIP(c->vb.ensure((size_t)f.nlf * 65536));
   J.nstreams = f.nlf * 2;
   {
-    // the statistics, code-table and bit-count arenas of this frame
-    const uint32_t ns = J.nstreams;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_hist = o;
-    o = al(o + (size_t)kMaxClusters * kAlpha * 4);
-    const size_t o_bound = o;
-    o = al(o + (size_t)f.ngroups * 4);
-    const size_t o_ntok = o;
-    o = al(o + (size_t)f.ngroups * 12);
-    const size_t o_bandtok = o;
-    o = al(o + (size_t)f.ngroups * 16);
-    const size_t o_bigcount = o;  // varblocks per big kind (big_list_kernel)
-    o = al(o + 16);
-    const size_t o_lfhist = o;
-    o = al(o + (size_t)ns * 4 * kAlpha * 4);
-    const size_t o_sbound = o;
-    o = al(o + (size_t)ns * 4);
-    const size_t o_vcount = o;
-    o = al(o + (size_t)f.nlf * 4);
-    JXG_HIP(c->stat.ensure(o));
-    JXG_HIP(c->h_stat.ensure(o));
-    c->stat_lf = o_lfhist;
-    c->stat_bytes = o;
-    c->hist_ac.set(c->stat.p, o_hist, (size_t)kMaxClusters * kAlpha);
-    c->bound.set(c->stat.p, o_bound, f.ngroups);
-    c->ntok.set(c->stat.p, o_ntok, (size_t)f.ngroups * 3);
-    c->bandtok.set(c->stat.p, o_bandtok, (size_t)f.ngroups * 4);
-    c->bigcount.set(c->stat.p, o_bigcount, 4);
-    c->h_bigcount.set(c->h_stat.p, o_bigcount, 4);
-    c->lfhist.set(c->stat.p, o_lfhist, (size_t)ns * 4 * kAlpha);
-    c->sbound.set(c->stat.p, o_sbound, ns);
-    c->vcount.set(c->stat.p, o_vcount, f.nlf);
-    c->h_hist_ac.set(c->h_stat.p, o_hist, (size_t)kMaxClusters * kAlpha);
-    c->h_bound.set(c->h_stat.p, o_bound, f.ngroups);
-    c->h_ntok.set(c->h_stat.p, o_ntok, (size_t)f.ngroups * 3);
-    c->h_lfhist.set(c->h_stat.p, o_lfhist, (size_t)ns * 4 * kAlpha);
-    c->h_sbound.set(c->h_stat.p, o_sbound, ns);
-    c->h_vcount.set(c->h_stat.p, o_vcount, f.nlf);
-    const uint32_t ng = std::max(1u, J.plan.ng());
-    o = 0;
-    const size_t o_codes = o;
-    o = al(o + (size_t)kMaxClusters * kAlpha * 4);
-    const size_t o_gbase = o;
-    o = al(o + (size_t)f.ngroups * 8);
-    const size_t o_order = o;
-    o = al(o + (size_t)ng * 4);
-    const size_t o_tab = o;
-    o = al(o + kAnsTabBytes);
-    const size_t o_lfcodes = o;
-    o = al(o + (size_t)ns * 4 * kAlpha * 4);
-    const size_t o_sbase = o;
-    o = al(o + (size_t)ns * 8);
-    JXG_HIP(c->up.ensure(o));
-    JXG_HIP(c->h_up.ensure(o));
-    c->up_gbase = o_gbase;
-    c->up_ac = o_order;
-    c->up_lf = o_lfcodes;
-    c->up_bytes = o;
-    c->codes_ac.set(c->up.p, o_codes, (size_t)kMaxClusters * kAlpha);
-    c->gbase.set(c->up.p, o_gbase, f.ngroups);
-    c->ans_order.set(c->up.p, o_order, ng);
-    c->ans_tab.set(c->up.p, o_tab, kAnsTabBytes);
-    c->lfcodes.set(c->up.p, o_lfcodes, (size_t)ns * 4 * kAlpha);
-    c->stream_base.set(c->up.p, o_sbase, ns);
-    c->h_codes_ac.set(c->h_up.p, o_codes, (size_t)kMaxClusters * kAlpha);
-    c->h_gbase.set(c->h_up.p, o_gbase, f.ngroups);
-    c->h_ans_order.set(c->h_up.p, o_order, ng);
-    c->h_ans_tab.set(c->h_up.p, o_tab, kAnsTabBytes);
-    c->h_lfcodes.set(c->h_up.p, o_lfcodes, (size_t)ns * 4 * kAlpha);
-    c->h_sbase.set(c->h_up.p, o_sbase, ns);
-    const size_t nbits = (size_t)f.ngroups + ns;
-    JXG_HIP(c->bits.ensure(nbits));
-    JXG_HIP(c->h_bits.ensure(nbits));
-    c->gbits.set(c->bits.p, 0, f.ngroups);
-    c->stream_bits.set(c->bits.p, (size_t)f.ngroups * 4, ns);
-    c->h_gbits.set(c->h_bits.p, 0, f.ngroups);
-    c->h_sbits.set(c->h_bits.p, (size_t)f.ngroups * 4, ns);
+    // the statistics, code-table and bit-count arenas of this frame, device
+    // and pinned side from one layout
+    const EncArenas::Layouts L = c->declare(f, J.plan.ng());
+    JXG_HIP(c->stat.ensure(c->stat_bytes));
+    JXG_HIP(c->h_stat.ensure(c->stat_bytes));
+    JXG_HIP(c->up.ensure(c->up_bytes));
+    JXG_HIP(c->h_up.ensure(c->up_bytes));
+    JXG_HIP(c->bits.ensure(c->bits_bytes));
+    JXG_HIP(c->h_bits.ensure(c->bits_bytes));
+    L.stat.commit(c->stat.p, c->h_stat.p);
+    L.up.commit(c->up.p, c->h_up.p);
+    L.bits.commit(c->bits.p, c->h_bits.p);
   }
-  const bool new_rows = c->rows_w != J.w || c->rows_h != J.h || c->rows_rank != J.plan.rank ||
-                        c->rows_world != J.plan.world;
-  if (new_rows) {
+  if (new_plan) {
     build_rows(f, J.plan, c->rows_h_cache, c->chunks_h_cache, c->schunks_cache);
     c->rows_w = J.w;
     c->rows_h = J.h;
@@ -200,7 +136,7 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
   JXG_HIP(c->lfchunks.ensure(J.nchunks));
   JXG_HIP(c->lfstatus.ensure(J.nchunks));
   JXG_HIP(c->stream_chunks.ensure(nstreams + 1));
-  if (new_rows) {
+  if (new_plan) {
     if (J.nrows)
       JXG_HIP(hipMemcpyAsync(c->rows.p, c->rows_h_cache.data(), J.nrows * sizeof(LfRow),
                              hipMemcpyHostToDevice, s));
@@ -227,13 +163,13 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
                              hipMemcpyHostToDevice, s));
     aa.glist = c->glist.p;
   }
-  aa.hist = c->hist_ac.p;
-  aa.bound = c->bound.p;
-  aa.ntok = c->ntok.p;
-  aa.bandtok = c->bandtok.p;
-  aa.codes = c->codes_ac.p;
-  aa.base = c->gbase.p;
-  aa.bits = c->gbits.p;
+  aa.hist = c->hist_ac.d;
+  aa.bound = c->bound.d;
+  aa.ntok = c->ntok.d;
+  aa.bandtok = c->bandtok.d;
+  aa.codes = c->codes_ac.d;
+  aa.base = c->gbase.d;
+  aa.bits = c->gbits.d;
   JXG_HIP(c->tokens.ensure((uint64_t)std::max(1u, J.plan.ng()) * kGroupTokStride));
   aa.tokens = c->tokens.p;
   LfArgs& la = J.la;
@@ -244,20 +180,20 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
   la.acs = c->acs.p;
   la.qf = c->qf.p;
   la.vb = c->vb.p;
-  la.vcount = c->vcount.p;
+  la.vcount = c->vcount.d;
   la.bxs = f.bxs;
   la.bys = f.bys;
   la.lfxs = f.lfxs;
   la.cmap = c->cmap.p;
   la.tiles_x = f.tiles_x;
   la.ntiles_all = f.tiles_x * f.tiles_y;
-  la.hist = c->lfhist.p;
-  la.sbound = c->sbound.p;
-  la.codes = c->lfcodes.p;
+  la.hist = c->lfhist.d;
+  la.sbound = c->sbound.d;
+  la.codes = c->lfcodes.d;
   la.status = c->lfstatus.p;
   la.stream_chunks = c->stream_chunks.p;
-  la.stream_base = c->stream_base.p;
-  la.stream_bits = c->stream_bits.p;
+  la.stream_base = c->stream_base.d;
+  la.stream_bits = c->stream_bits.d;
   return JXG_OK;
 }
 
@@ -398,14 +334,14 @@ jxg_status build_front(Ctx* c, Job& J) {
     ba.slots = slots;
     ba.cost = c->big_cost.p;
     ba.work = c->big_work.p;
-    ba.kinds = c->bigcount.p;
+    ba.kinds = c->bigcount.d;
     ba.glist = J.plan.contiguous ? nullptr : c->glist.p;
     ba.g0 = J.plan.g0();
     ba.ng = J.plan.ng();
     ba.gxs = f.gxs;
   }
   J.va = VbArgs{c->acs.p, f.bxs, f.bys, f.lfxs, J.plan.world > 1 ? c->lf_mine.p : nullptr, c->vb.p,
-                c->vcount.p};
+                c->vcount.d};
   return JXG_OK;
 }
 
@@ -424,17 +360,17 @@ uint32_t big_mask(const uint32_t* count) {
 jxg_status stage_download_ac(Ctx* c, Job& J, const uint32_t* hist) {
   (void)J;
   hipStream_t s = c->stream;
-  if (hist == c->hist_ac.p) {  // [hist_ac | bound | ntok]: one copy
+  if (hist == c->hist_ac.d) {  // [hist_ac | bound | ntok]: one copy
     JXG_HIP(hipMemcpyAsync(c->h_stat.p, c->stat.p, c->stat_lf, hipMemcpyDeviceToHost, s));
   } else {  // a caller's (all-reduced) histogram
-    const size_t hb = (size_t)kMaxClusters * kAlpha * 4, ob = (uint8_t*)c->bound.p - c->stat.p;
-    JXG_HIP(hipMemcpyAsync(c->h_hist_ac.p, hist, hb, hipMemcpyDeviceToHost, s));
+    const size_t hb = (size_t)kMaxClusters * kAlpha * 4, ob = (uint8_t*)c->bound.d - c->stat.p;
+    JXG_HIP(hipMemcpyAsync(c->hist_ac.h, hist, hb, hipMemcpyDeviceToHost, s));
     JXG_HIP(hipMemcpyAsync(c->h_stat.p + ob, c->stat.p + ob, c->stat_lf - ob, hipMemcpyDeviceToHost, s));
     // the big-kind counts summed with it (jxg_shard_sizes: after the histogram)
-    JXG_HIP(hipMemcpyAsync(c->h_bigcount.p, hist + (size_t)kMaxClusters * kAlpha, 16,
+    JXG_HIP(hipMemcpyAsync(c->bigcount.h, hist + (size_t)kMaxClusters * kAlpha, 16,
                            hipMemcpyDeviceToHost, s));
   }
-  JXG_HIP(hipEventRecord(c->ev[6], s));
+  JXG_HIP(hipEventRecord(c->ev[kEvAcStats], s));
   return JXG_OK;
 }
 static jxg_status stage_download_lf(Ctx* c, Job& J) {
@@ -443,7 +379,7 @@ static jxg_status stage_download_lf(Ctx* c, Job& J) {
   // [lfhist | sbound | vcount]: one copy
   JXG_HIP(hipMemcpyAsync(c->h_stat.p + c->stat_lf, c->stat.p + c->stat_lf, c->stat_bytes - c->stat_lf,
                          hipMemcpyDeviceToHost, s));
-  JXG_HIP(hipEventRecord(c->ev[2], s));
+  JXG_HIP(hipEventRecord(c->ev[kEvLfStats], s));
   return JXG_OK;
 }
 
@@ -478,19 +414,19 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
   const Frame& f = J.f;
   const bool listed = !J.plan.tiles.empty();
   const uint32_t ntiles = listed ? (uint32_t)J.plan.tiles.size() : f.tiles_x * f.tiles_y;
-  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[0], s));
+  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvStart], s));
   if (J.aq) {
     const auto q = gather<AqArgs>(js, k, [](Job& j) { return j.qa; });
     launch_aq(q.data(), k, ntiles, s);
   }
-  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[9], s));
+  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontStart], s));
   const auto fa = gather<FrontArgs>(js, k, [](Job& j) { return j.fa; });
   if (listed)
     launch_front_list(fa.data(), k, ntiles, s);
   else if (J.plan.world == 1)
     launch_front(fa.data(), k, f.tiles_x, f.tiles_y, s);
   JXG_HIP(hipGetLastError());
-  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[5], s));  // front kernel alone
+  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontDone], s));  // front kernel alone
   if (J.max_s) {
     const auto ma = gather<MergeArgs>(js, k, [](Job& j) { return j.ma; });
     JXG_HIP(launch_merge(ma.data(), k, s));
@@ -510,7 +446,7 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
       }
     }
   }
-  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[1], s));
+  for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvMerged], s));
   // (the statistics arenas were zeroed by the front kernel)
   const auto aa = gather<AcArgs>(js, k, [](Job& j) { return j.aa; });
   launch_ac_hist(aa.data(), k, J.plan.ng(), s, J.big);
@@ -536,226 +472,73 @@ jxg_status launch_lf_stats(Ctx* const* cs, Job* const* js, uint32_t k) {
 // all of stages B-E (each frame's own AC histogram)
 jxg_status launch_stats(Ctx* const* cs, Job* const* js, uint32_t k) {
   jxg_status st = launch_transform(cs, js, k);
-  for (uint32_t i = 0; i < k && !st; i++) st = stage_download_ac(cs[i], *js[i], cs[i]->hist_ac.p);
+  for (uint32_t i = 0; i < k && !st; i++) st = stage_download_ac(cs[i], *js[i], cs[i]->hist_ac.d);
   return st ? st : launch_lf_stats(cs, js, k);
 }
 
-// ---- stage F (host): prefix codes, LF preludes, LfGlobal / HfGlobal,
-// scratch layout for the plan's groups and streams ----
+// ---- stage F (host): the frame's codes, global sections and arena layouts
+// (built by jxg_codes.cpp straight into the pinned upload sections), their
+// uploads, and with prefix codes the AC emission ----
 jxg_status stage_codes(Ctx* c, Job& J) {
   hipStream_t s = c->stream;
   const Frame& f = J.f;
-  const uint32_t nstreams = J.nstreams;
-  JXG_HIP(hipEventSynchronize(c->ev[6]));  // AC statistics on the host; LF kernels may still run
+  JXG_HIP(hipEventSynchronize(c->ev[kEvAcStats]));  // LF kernels may still run
   const Clock::time_point t_codes = Clock::now();
-  // prefix codes: one histogram per (used) static cluster; ANS: the static
-  // clusters are clustered again into <= kAnsMaxHists groups (the alias
-  // inverses must fit the encoder's LDS).  Dense ids in order of first
-  // appearance over contexts (oracle/encode.c).
-  int group[kMaxClusters];
+  const AcCodes A = build_ac_codes(c->hist_ac.h, J.ans, c->ans_tab.h, c->codes_ac.h);
   if (J.ans) {
-    cluster_ans_histograms(c->h_hist_ac.p, kMaxClusters, group);
-  } else {
-    int ng = 0;
-    for (int cl = 0; cl < kMaxClusters; cl++) {
-      uint64_t tot = 0;
-      for (int k = 0; k < kAlpha; k++) tot += c->h_hist_ac.p[cl * kAlpha + k];
-      group[cl] = tot ? ng++ : -1;
-    }
-  }
-  int dense[kMaxClusters];
-  std::fill(dense, dense + kMaxClusters, -1);
-  int nhist = 0;
-  std::vector<uint8_t> ctxmap(kAcCtx);
-  for (int ctx = 0; ctx < kAcCtx; ctx++) {
-    const int gr = group[ac_cluster(ctx)];
-    if (gr >= 0 && dense[gr] < 0) dense[gr] = nhist++;
-    ctxmap[ctx] = (uint8_t)(gr < 0 ? 0 : dense[gr]);
-  }
-  std::vector<PrefixCode> codes(std::max(nhist, 1));
-  std::vector<AnsTable> ans_tables(J.ans ? std::max(nhist, 1) : 0);
-  std::vector<uint32_t> packed(kMaxClusters * kAlpha, 0);
-  if (J.ans) {
-    std::vector<uint32_t> dh((size_t)std::max(nhist, 1) * kAlpha, 0);
-    for (int cl = 0; cl < kMaxClusters; cl++)
-      if (group[cl] >= 0)
-        for (int k = 0; k < kAlpha; k++) dh[dense[group[cl]] * kAlpha + k] += c->h_hist_ac.p[cl * kAlpha + k];
-    // device table blob (AnsArgs::tab): freq | cum << 16, alias inverses,
-    // static cluster -> dense histogram
-    JXG_HIP(c->h_ans_tab.ensure(kAnsTabBytes));
-    uint8_t* blob = c->h_ans_tab.p;
-    std::memset(blob, 0, kAnsTabBytes);
-    uint32_t* sym = reinterpret_cast<uint32_t*>(blob);
-    uint16_t* inv = reinterpret_cast<uint16_t*>(blob + kAnsInvOff);
-    for (int h = 0; h < nhist; h++) {
-      AnsTable& t = ans_tables[h];
-      t = build_ans_table(dh.data() + h * kAlpha);
-      std::copy(t.inv.begin(), t.inv.end(), inv + (size_t)h * 4096);
-      for (int k = 0; k < 128; k++) {
-        const uint32_t f = t.freq[k];
-        if (!f) continue;
-        sym[h * 128 + k] = (f - 1) | (uint32_t)t.cum[k] << 12;
-      }
-    }
-    for (int cl = 0; cl < kMaxClusters; cl++)
-      blob[kAnsMapOff + cl] = (uint8_t)(group[cl] >= 0 ? dense[group[cl]] : 0);
-    J.nhist_ans = (uint32_t)nhist;
+    J.nhist_ans = (uint32_t)A.nhist;
     if (J.presets) {
-      J.pre_ctxmap = ctxmap;
-      J.pre_counts.assign(dh.begin(), dh.begin() + (size_t)nhist * kAlpha);
-    }
-  } else {
-    for (int cl = 0; cl < kMaxClusters; cl++) {
-      if (group[cl] < 0) continue;
-      const int h = dense[group[cl]];
-      codes[h] = build_prefix_code(c->h_hist_ac.p + cl * kAlpha, kAlpha);
-      for (int k = 0; k < kAlpha; k++) packed[cl * kAlpha + k] = codes[h].packed(k);
+      J.pre_ctxmap = A.ctxmap;
+      J.pre_counts.assign(A.counts.begin(), A.counts.begin() + (size_t)A.nhist * kAlpha);
     }
   }
   // LfGlobal / HfGlobal (rank 0): need the AC codes only
   J.lfglobal = BitWriter();
   J.hfglobal = BitWriter();
   if (J.plan.rank == 0) {
-    BitWriter& lfglobal = J.lfglobal;
-    BitWriter& hfglobal = J.hfglobal;
-    lfglobal.put(1, 1);  // LfChannelDequantization.all_default
-    if (f.G <= 2048)
-      write_u32_sel(lfglobal, 0, 11, f.G - 1);
-    else if (f.G <= 4096)
-      write_u32_sel(lfglobal, 1, 11, f.G - 2049);
-    else if (f.G <= 8192)
-      write_u32_sel(lfglobal, 2, 12, f.G - 4097);
-    else
-      write_u32_sel(lfglobal, 3, 16, f.G - 8193);
-    if (f.qdc == 16)
-      lfglobal.put(2, 0);
-    else if (f.qdc <= 32)
-      write_u32_sel(lfglobal, 1, 5, f.qdc - 1);
-    else if (f.qdc <= 256)
-      write_u32_sel(lfglobal, 2, 8, f.qdc - 1);
-    else
-      write_u32_sel(lfglobal, 3, 16, f.qdc - 1);
-    lfglobal.put(1, 1);  // BlockCtxMap default
-    lfglobal.put(1, 1);  // colour correlation default
-    lfglobal.put(1, 0);  // GlobalModular: no tree, no channels
+    write_lf_global(J.lfglobal, f.G, f.qdc);
     if (!J.presets) {  // (per-rank presets: HfGlobal at assembly, build_hf_presets)
-      // the quant tables of the 128 / 256 px kinds the frame uses (e >= 8)
-      write_dequant_matrices(hfglobal, J.big ? big_mask(c->h_bigcount.p) : 0u);
-      hfglobal.put(ceil_log2(f.ngroups), 0);  // num_hf_presets - 1
-      write_u32_sel(hfglobal, 2, 0, 0);        // used_orders = 0
-      if (nhist != c->cm_nhist || ctxmap != c->cm_last) {
-        c->cm_bits = BitWriter();
-        write_context_map(c->cm_bits, ctxmap, nhist);
-        c->cm_last = ctxmap;
-        c->cm_nhist = nhist;
-      }
+      const uint32_t mask = J.big ? big_mask(c->bigcount.h) : 0u;
+      const BitWriter* cm = &c->ctxmap_cache.get(A.ctxmap, A.nhist);
       if (J.ans)
-        write_ans_histograms(hfglobal, ctxmap, nhist, ans_tables, kCfg420, &c->cm_bits);
+        write_hf_global(J.hfglobal, mask, f.ngroups, 1, A.ctxmap, A.nhist, A.tables, cm);
       else
-        write_histograms(hfglobal, ctxmap, nhist, codes, kCfg420, &c->cm_bits);
+        write_hf_global(J.hfglobal, mask, f.ngroups, 1, A.ctxmap, A.nhist, A.codes, cm);
     }
   }
-  // AC layout: the plan's groups in the scratch arena (32-bit aligned); the AC
-  // emission is launched at once and runs while the host builds the LF-group
-  // codes below
+  // AC layout; the pinned upload sources stay valid until the next frame's
+  // stage_codes, which runs after this frame's emission has completed
   J.gbase.assign(f.ngroups, 0);
-  uint64_t cursor = 0;
-  for (uint32_t g : J.plan.groups) {
-    J.gbase[g] = cursor;
-    const uint64_t nt = (uint64_t)c->h_ntok.p[g * 3] + c->h_ntok.p[g * 3 + 1] + c->h_ntok.p[g * 3 + 2];
-    // ANS: <= 16 + raw bits per token (prefix: <= 15 + raw) and the 32-bit state
-    const uint64_t bound = (uint64_t)c->h_bound.p[g] + (J.ans ? nt + 32 : 0);
-    cursor += (bound + 63) & ~31ull;
-  }
-  const uint64_t ac_words = (cursor / 32 + 2 + 63) & ~63ull;
+  const uint64_t ac_words = layout_ac(J.plan.groups, c->ntok.h, c->bound.h, J.ans, J.gbase.data());
   if (!J.ans) JXG_HIP(c->scratch.ensure(ac_words));  // (ANS: with the LF arena below)
-  // pinned upload sources: valid until the next frame's stage_codes, which
-  // runs after this frame's emission has completed
-  JXG_HIP(c->h_codes_ac.ensure(packed.size()));
-  std::copy(packed.begin(), packed.end(), c->h_codes_ac.p);
-  JXG_HIP(c->h_gbase.ensure(J.gbase.size()));
-  std::copy(J.gbase.begin(), J.gbase.end(), c->h_gbase.p);
+  std::copy(J.gbase.begin(), J.gbase.end(), c->gbase.h);
   if (J.ans) {
     const uint64_t nrec = (uint64_t)std::max(1u, J.plan.ng()) * kGroupTokStride;
     JXG_HIP(c->tval.ensure(nrec));
     JXG_HIP(c->tlen.ensure(nrec));
     JXG_HIP(c->ans_state.ensure(f.ngroups));
     JXG_HIP(c->csum.ensure((uint64_t)std::max(1u, J.plan.ng()) * kAnsMaxChunks));
-    JXG_HIP(c->ans_tab.ensure(kAnsTabBytes));
-    // chain order: the plan's groups by token count, longest first, so the
-    // 64 lanes of a chain workgroup hold groups of similar length and the
-    // workgroups of short groups give their CUs (and their LDS, 139.5 KB each
-    // in the streamed form, 68 KB in the one-frame form) back
-    // early -- the kernel still lasts as long as the longest group
-    const uint32_t ng = J.plan.ng();
-    JXG_HIP(c->h_ans_order.ensure(ng));
-    JXG_HIP(c->ans_order.ensure(ng));
-    uint32_t* ord = c->h_ans_order.p;
-    for (uint32_t i = 0; i < ng; i++) ord[i] = i;  // launch slots
-    const uint32_t* nt = c->h_ntok.p;
-    const uint32_t* gl = J.plan.groups.data();
-    std::stable_sort(ord, ord + ng, [nt, gl](uint32_t x, uint32_t y) {
-      const uint32_t gx = gl[x], gy = gl[y];
-      return nt[gx * 3] + nt[gx * 3 + 1] + nt[gx * 3 + 2] > nt[gy * 3] + nt[gy * 3 + 1] + nt[gy * 3 + 2];
-    });
-    J.max_tokens = 0;
-    for (uint32_t g : J.plan.groups)
-      J.max_tokens = std::max(J.max_tokens, nt[g * 3] + nt[g * 3 + 1] + nt[g * 3 + 2]);
+    J.max_tokens = ans_chain_order(J.plan, c->ntok.h, c->ans_order.h);
   }
   const float ms_ac_codes = ms_since(t_codes);
   if (!J.ans) {
     // prefix codes: the AC code tables now, so the AC emission runs while the
-    // host builds the LF-group codes (ANS: every table in one upload below)
+    // host builds the LF-group codes (ANS: every table in one upload below; the
+    // rANS coder -- a long latency-bound chain that hides the LF-code
+    // construction anyway -- is launched by stage_emit)
     JXG_HIP(hipMemcpyAsync(c->up.p, c->h_up.p, c->up_ac, hipMemcpyHostToDevice, s));
     J.aa.scratch = c->scratch.p;
     launch_ac_emit(J.aa, J.plan.ng(), s);
     JXG_HIP(hipGetLastError());
-    JXG_HIP(hipMemcpyAsync(c->h_gbits.p, c->gbits.p, f.ngroups * 4, hipMemcpyDeviceToHost, s));
-    JXG_HIP(hipEventRecord(c->ev[7], s));
+    JXG_HIP(hipMemcpyAsync(c->gbits.h, c->gbits.d, f.ngroups * 4, hipMemcpyDeviceToHost, s));
+    JXG_HIP(hipEventRecord(c->ev[kEvAcEmitted], s));
   }
-  // (the rANS coder -- a long latency-bound chain that hides the LF-code
-  // construction anyway -- is launched by stage_emit)
-
-  // LF-group stream codes and preludes (the plan's LF groups)
-  JXG_HIP(hipEventSynchronize(c->ev[2]));  // LF statistics (stage_download_lf)
+  JXG_HIP(hipEventSynchronize(c->ev[kEvLfStats]));  // (stage_download_lf)
   const Clock::time_point t_lf = Clock::now();
-  const size_t nlfcodes = (size_t)nstreams * 4 * kAlpha;
-  JXG_HIP(c->h_lfcodes.ensure(nlfcodes));
-  uint32_t* lfpacked = c->h_lfcodes.p;
-  std::fill(lfpacked, lfpacked + nlfcodes, 0u);
-  J.preA.assign(f.nlf, BitWriter());
-  J.preB.assign(f.nlf, BitWriter());
-  for (uint32_t lg = 0; lg < f.nlf; lg++) {
-    if (!J.plan.owns_lf(lg)) continue;
-    const uint32_t bx0 = (lg % f.lfxs) * 256, by0 = (lg / f.lfxs) * 256;
-    const uint32_t bw = std::min(256u, f.bxs - bx0), bh = std::min(256u, f.bys - by0);
-    for (int sidx = 0; sidx < 2; sidx++) {
-      const uint32_t sid = lg * 2 + sidx;
-      const int nleaves = sidx == 0 ? 3 : 4;
-      std::vector<PrefixCode> lc(nleaves);
-      for (int l = 0; l < nleaves; l++) {
-        lc[l] = build_prefix_code(c->h_lfhist.p + ((size_t)sid * 4 + l) * kAlpha, kAlpha);
-        for (int k = 0; k < kAlpha; k++) lfpacked[((size_t)sid * 4 + l) * kAlpha + k] = lc[l].packed(k);
-      }
-      if (sidx == 0) {
-        J.preA[lg].put(2, 0);  // extra_precision
-        write_modular_prelude(J.preA[lg], kDcTree, 5, 3, lc);
-      } else {
-        J.preB[lg].put(ceil_log2(bw * bh), c->h_vcount.p[lg] - 1);  // varblock count - 1
-        write_modular_prelude(J.preB[lg], (J.lf >> 1) ? kMetaTreeEpf : kMetaTree, 7, 4, lc);
-      }
-    }
-  }
-  // LF layout: the plan's LF streams in their own arena (32-bit aligned)
-  J.sbase.assign(nstreams, 0);
-  cursor = 0;
-  for (uint32_t i = 0; i < nstreams; i++) {
-    J.sbase[i] = cursor;
-    if (J.plan.owns_lf(i / 2)) cursor += ((uint64_t)c->h_sbound.p[i] + 63) & ~31ull;
-  }
-  const uint64_t lf_words = cursor / 32 + 2;
-  JXG_HIP(c->h_sbase.ensure(J.sbase.size()));
-  std::copy(J.sbase.begin(), J.sbase.end(), c->h_sbase.p);
+  build_lf_codes(f, J.plan, c->lfhist.h, c->vcount.h, J.lf, c->lfcodes.h, J.preA, J.preB);
+  J.sbase.assign(J.nstreams, 0);
+  const uint64_t lf_words = layout_lf(f, J.plan, c->sbound.h, J.sbase.data());
+  std::copy(J.sbase.begin(), J.sbase.end(), c->stream_base.h);
   if (J.ans) {
     // one arena for the AC and LF bits (no fill: the chains clear their
     // ranges, lf_code stores whole words) and every table in one upload
@@ -784,18 +567,18 @@ static void build_emit(Ctx* c, Job& J) {
   na.tokens = c->tokens.p;
   na.val = c->tval.p;
   na.len = c->tlen.p;
-  na.ntok = c->ntok.p;
-  na.bandtok = c->bandtok.p;
-  na.tab = c->ans_tab.p;
+  na.ntok = c->ntok.d;
+  na.bandtok = c->bandtok.d;
+  na.tab = c->ans_tab.d;
   na.nhist = J.nhist_ans;
   na.state = c->ans_state.p;
-  na.base = c->gbase.p;
+  na.base = c->gbase.d;
   na.scratch = c->scratch.p;
-  na.bits = c->gbits.p;
+  na.bits = c->gbits.d;
   na.g0 = J.plan.g0();
   na.n = J.plan.ng();
   na.glist = J.aa.glist;
-  na.order = c->ans_order.p;
+  na.order = c->ans_order.d;
   na.csum = c->csum.p;
   na.max_tokens = J.max_tokens;
 }
@@ -818,16 +601,14 @@ jxg_status launch_emit(Ctx* const* cs, Job* const* js, uint32_t k, bool streamed
   JXG_HIP(hipGetLastError());
   for (uint32_t i = 0; i < k; i++) {
     Ctx* c = cs[i];
-    const Frame& f = js[i]->f;
     if (J.ans) {  // [gbits | stream_bits]: one copy
-      JXG_HIP(hipMemcpyAsync(c->h_bits.p, c->bits.p, ((size_t)f.ngroups + js[i]->nstreams) * 4,
-                             hipMemcpyDeviceToHost, s));
-      JXG_HIP(hipEventRecord(c->ev[7], s));
+      JXG_HIP(hipMemcpyAsync(c->h_bits.p, c->bits.p, c->bits_bytes, hipMemcpyDeviceToHost, s));
+      JXG_HIP(hipEventRecord(c->ev[kEvAcEmitted], s));
     } else {
-      JXG_HIP(hipMemcpyAsync(c->h_sbits.p, c->stream_bits.p, js[i]->nstreams * 4,
+      JXG_HIP(hipMemcpyAsync(c->stream_bits.h, c->stream_bits.d, js[i]->nstreams * 4,
                              hipMemcpyDeviceToHost, s));
     }
-    JXG_HIP(hipEventRecord(c->ev[3], s));
+    JXG_HIP(hipEventRecord(c->ev[kEvEmitted], s));
   }
   return JXG_OK;
 }
@@ -855,9 +636,9 @@ static JobSections job_sections(const Ctx* c, const Job& J) {
   j.preA = J.preA.data();
   j.preB = J.preB.data();
   j.sbase = J.sbase.data();
-  j.sbits = c->h_sbits.p;
+  j.sbits = c->stream_bits.h;
   j.gbase = J.gbase.data();
-  j.gbits = c->h_gbits.p;
+  j.gbits = c->gbits.h;
   return j;
 }
 static_assert(sizeof(PlacedPiece) == sizeof(ConcatPiece), "PlacedPiece is what the concat kernel reads");
@@ -904,7 +685,7 @@ jxg_status stage_concat(Ctx* c, Job& J, bool full, std::vector<uint32_t>* sectio
     out_release(ho);
     return JXG_ERR_HIP;
   }
-  JXG_HIP(hipEventRecord(c->ev[4], s));
+  JXG_HIP(hipEventRecord(c->ev[kEvAssembled], s));
   if (host_out) *host_out = ho;
   *out_bytes = nbytes;
   if (section_ids) *section_ids = L.ids();
@@ -924,7 +705,7 @@ static jxg_status stage_concat_split(Ctx* c, Job& J, uint8_t** host_out, size_t*
     return JXG_ERR_HIP;  // created on first use: only lone contexts take this path
   hipStream_t s = c->stream, s2 = c->stream2;
   const Frame& f = J.f;
-  JXG_HIP(hipEventSynchronize(c->ev[7]));  // AC emission done, its bit counts on the host
+  JXG_HIP(hipEventSynchronize(c->ev[kEvAcEmitted]));  // AC emission done, its bit counts on the host
   const JobSections js = job_sections(c, J);  // (one context: all groups)
   PieceList A;
   A.add_groups(js);
@@ -938,8 +719,8 @@ static jxg_status stage_concat_split(Ctx* c, Job& J, uint8_t** host_out, size_t*
   uint64_t pbits = J.lfglobal.bits() + J.hfglobal.bits() + 16;
   for (uint32_t lg = 0; lg < f.nlf; lg++)
     if (J.plan.owns_lf(lg))
-      pbits += J.preA[lg].bits() + J.preB[lg].bits() + c->h_sbound.p[lg * 2] +
-               c->h_sbound.p[lg * 2 + 1] + 8;
+      pbits += J.preA[lg].bits() + J.preB[lg].bits() + c->sbound.h[lg * 2] +
+               c->sbound.h[lg * 2 + 1] + 8;
   const size_t nsec = 2 + (size_t)f.nlf + f.ngroups;
   size_t pmax = (size_t)(pbits / 8) + 256 + 4 * nsec + 16 + kOutHdr;
   pmax = (pmax + 63) & ~(size_t)63;
@@ -955,7 +736,7 @@ static jxg_status stage_concat_split(Ctx* c, Job& J, uint8_t** host_out, size_t*
   if (c->cat.out_ac.ensure(ac_words) != hipSuccess ||
       c->cat.pieces_ac.ensure(std::max<uint32_t>(np, 1)) != hipSuccess)
     return fail(JXG_ERR_HIP);
-  if (hipStreamWaitEvent(s2, c->ev[7], 0) != hipSuccess ||
+  if (hipStreamWaitEvent(s2, c->ev[kEvAcEmitted], 0) != hipSuccess ||
       (np && hipMemcpyAsync(c->cat.pieces_ac.p, c->cat.h_pieces_ac.p, np * sizeof(ConcatPiece),
                             hipMemcpyHostToDevice, s2) != hipSuccess))
     return fail(JXG_ERR_HIP);
@@ -964,7 +745,7 @@ static jxg_status stage_concat_split(Ctx* c, Job& J, uint8_t** host_out, size_t*
   if (hipGetLastError() != hipSuccess ||
       (ac_bytes && hipMemcpyAsync(ho + pmax, c->cat.out_ac.p, ac_bytes, hipMemcpyDeviceToHost, s2) !=
                        hipSuccess) ||
-      hipEventRecord(c->ev[8], s2) != hipSuccess)
+      hipEventRecord(c->ev[kEvAcBlock], s2) != hipSuccess)
     return fail(JXG_ERR_HIP);
 
   // prefix, after the LF emission (stage_emit without its sync)
@@ -1002,8 +783,8 @@ static jxg_status stage_concat_split(Ctx* c, Job& J, uint8_t** host_out, size_t*
                 c->lf_scratch, c->out.p, s);
   if (hipGetLastError() != hipSuccess ||
       hipMemcpyAsync(data, c->out.p, pbytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamWaitEvent(s, c->ev[8], 0) != hipSuccess ||
-      hipEventRecord(c->ev[4], s) != hipSuccess)
+      hipStreamWaitEvent(s, c->ev[kEvAcBlock], 0) != hipSuccess ||
+      hipEventRecord(c->ev[kEvAssembled], s) != hipSuccess)
     return fail(JXG_ERR_HIP);
   J.ms_layout = ms_since(t_layout);
   out_set_backref(data, ho);
@@ -1070,7 +851,7 @@ jxg_status enc_finish_start(Ctx* c, Job& J, bool split) {
   return JXG_OK;
 }
 // the frame's stats (the lane's jxg_stats); `assembled`: the assembly has
-// completed (ev[4]), else its time is left out
+// completed (kEvAssembled), else its time is left out
 void enc_stats(Ctx* c, Job& J, size_t out_bytes, float ms_layout, bool assembled,
                       const std::vector<int16_t>* m_ac16, Clock::time_point t_call) {
   const jxg_params& P = c->params;
@@ -1087,7 +868,7 @@ void enc_stats(Ctx* c, Job& J, size_t out_bytes, float ms_layout, bool assembled
   S.global_scale = f.G;
   S.quant_dc = f.qdc;
   S.bytes = out_bytes;
-  c->m_ntok.assign(c->h_ntok.p, c->h_ntok.p + f.ngroups * 3);
+  c->m_ntok.assign(c->ntok.h, c->ntok.h + f.ngroups * 3);
   S.ac_tokens = c->m_ntok.data();
   if ((P.flags & JXG_FLAG_KEEP_MAPS) && m_ac16) {
     // coefficients in natural-order slices, widened to int32 for the caller
@@ -1098,13 +879,13 @@ void enc_stats(Ctx* c, Job& J, size_t out_bytes, float ms_layout, bool assembled
     S.ac = c->m_ac.data();
     S.homogeneity = J.homog ? c->m_homog.data() : nullptr;
   }
-  S.ms_front = elapsed(c->ev[0], c->ev[1]);
-  S.ms_front_kernel = elapsed(c->ev[9], c->ev[5]);
-  S.ms_aq = elapsed(c->ev[0], c->ev[9]);
-  S.ms_histogram = elapsed(c->ev[1], c->ev[2]);
-  S.ms_emit = elapsed(c->ev[2], c->ev[3]);
-  S.ms_assemble = assembled ? elapsed(c->ev[3], c->ev[4]) : 0.0f;
-  S.ms_total = elapsed(c->ev[0], assembled ? c->ev[4] : c->ev[3]);
+  S.ms_front = elapsed(c->ev[kEvStart], c->ev[kEvMerged]);
+  S.ms_front_kernel = elapsed(c->ev[kEvFrontStart], c->ev[kEvFrontDone]);
+  S.ms_aq = elapsed(c->ev[kEvStart], c->ev[kEvFrontStart]);
+  S.ms_histogram = elapsed(c->ev[kEvMerged], c->ev[kEvLfStats]);
+  S.ms_emit = elapsed(c->ev[kEvLfStats], c->ev[kEvEmitted]);
+  S.ms_assemble = assembled ? elapsed(c->ev[kEvEmitted], c->ev[kEvAssembled]) : 0.0f;
+  S.ms_total = elapsed(c->ev[kEvStart], assembled ? c->ev[kEvAssembled] : c->ev[kEvEmitted]);
   S.ms_host_codes = J.ms_codes;
   S.ms_host_layout = ms_layout;
   S.ms_host_call = ms_since(t_call);

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "jxg_acmodel.h"
 #include "jxg_decode_core.h"
 
 namespace jxg {
@@ -174,13 +175,8 @@ constexpr uint64_t kGroupTokStride = 1024ull * 3 * 64;
 constexpr uint64_t kBandTokStride = 256ull * 3 * 64;
 
 // ANS coding of the pass groups' token records (jxg_ac.hip)
-#ifndef JXG_ANS_HISTS  // (jxg_bitstream.h kAnsMaxHists; experiment builds override it)
-#define JXG_ANS_HISTS 8
-#endif
-constexpr uint32_t kAnsHists = JXG_ANS_HISTS;  // == kAnsMaxHists (jxg_bitstream.h)
-constexpr uint32_t kAnsInvOff = kAnsHists * 128 * 4;
-constexpr uint32_t kAnsMapOff = kAnsInvOff + kAnsHists * 4096 * 2;
-constexpr uint32_t kAnsTabBytes = kAnsMapOff + 136;
+// (the table blob's layout, kAnsHists / kAnsInvOff / kAnsMapOff / kAnsTabBytes:
+// jxg_acmodel.h)
 struct AnsArgs {
   const uint32_t* tokens;  // token records of ac_hist_kernel (kGroupTokStride per group)
   uint32_t* val;           // [records] emitted bits: 16-bit chunk (if any) then raw bits

@@ -79,5 +79,48 @@ class PieceList {
   std::vector<PlacedPiece> placed_;
 };
 
+// One section of an arena that exists twice, in device memory and in its
+// pinned host mirror, at the same byte offset of both: d / h point at the two
+// copies of n elements.  A section read on one side only leaves the other
+// pointer unused.
+template <class T>
+struct Mirror {
+  T* d = nullptr;
+  T* h = nullptr;
+  size_t n = 0;
+};
+// The layout of such an arena, declared once per frame: sections in order,
+// each on a 256-byte boundary; commit() points every section's mirror into
+// the two allocations, so the two sides cannot disagree.
+class ArenaLayout {
+ public:
+  static constexpr size_t kAlign = 256;
+  template <class T>
+  void add(Mirror<T>& m, size_t count) {
+    m.n = count;
+    slots_.push_back({&m, off_, [](void* mp, uint8_t* dev, uint8_t* host) {
+                        Mirror<T>* mm = static_cast<Mirror<T>*>(mp);
+                        mm->d = reinterpret_cast<T*>(dev);
+                        mm->h = reinterpret_cast<T*>(host);
+                      }});
+    off_ = (off_ + count * sizeof(T) + kAlign - 1) & ~(kAlign - 1);
+  }
+  size_t mark() const { return off_; }   // byte offset of the next section
+  size_t bytes() const { return off_; }  // of the whole arena
+  void commit(void* dev_base, void* host_base) const {
+    for (const Slot& s : slots_)
+      s.set(s.mirror, static_cast<uint8_t*>(dev_base) + s.off, static_cast<uint8_t*>(host_base) + s.off);
+  }
+
+ private:
+  struct Slot {
+    void* mirror;
+    size_t off;
+    void (*set)(void*, uint8_t*, uint8_t*);
+  };
+  std::vector<Slot> slots_;
+  size_t off_ = 0;
+};
+
 }  // namespace jxg
 #pragma GCC visibility pop

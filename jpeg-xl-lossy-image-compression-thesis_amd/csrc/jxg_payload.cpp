@@ -3,9 +3,7 @@
 
 #include <cstring>
 
-#include "jxg_bitstream.h"
-#include "jxg_device.h"
-#include "jxg_tables.h"
+#include "jxg_codes.h"
 
 namespace jxg {
 
@@ -46,10 +44,7 @@ static jxg_status build_hf_presets(const std::vector<std::vector<uint32_t>>& hea
     off += nh;
   }
   if (off > 255 || n - 1 >= (1u << ceil_log2(ngroups))) return JXG_ERR_INVALID_ARG;
-  write_dequant_matrices(hf, big);         // DequantMatrices
-  hf.put(ceil_log2(ngroups), n - 1);     // num_hf_presets - 1
-  write_u32_sel(hf, 2, 0, 0);              // used_orders = 0
-  write_ans_histograms(hf, ctxmap, (int)off, tables, kCfg420, nullptr);
+  write_hf_global(hf, big, ngroups, n, ctxmap, (int)off, tables, nullptr);
   return JXG_OK;
 }
 

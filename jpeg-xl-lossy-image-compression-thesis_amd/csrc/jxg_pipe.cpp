@@ -199,9 +199,9 @@ static void shard_frame_stats(PipeFrame& fr, size_t bytes) {
   S.num_groups = fr.J.f.ngroups;
   S.num_lf_groups = fr.J.f.nlf;
   S.bytes = bytes;
-  S.ms_front_kernel = elapsed(fr.lane->ev[9], fr.lane->ev[5]);
-  S.ms_aq = elapsed(fr.lane->ev[0], fr.lane->ev[9]);
-  S.ms_front = elapsed(fr.lane->ev[0], fr.lane->ev[1]);
+  S.ms_front_kernel = elapsed(fr.lane->ev[kEvFrontStart], fr.lane->ev[kEvFrontDone]);
+  S.ms_aq = elapsed(fr.lane->ev[kEvStart], fr.lane->ev[kEvFrontStart]);
+  S.ms_front = elapsed(fr.lane->ev[kEvStart], fr.lane->ev[kEvMerged]);
   S.ms_host_codes = fr.J.ms_codes;
   S.ms_host_call = ms_since(fr.t0);
 }

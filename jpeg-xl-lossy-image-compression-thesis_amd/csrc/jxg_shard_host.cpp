@@ -35,8 +35,8 @@ jxg_status shard_begin(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h, siz
   if ((st = build_front(c, J))) return st;
   Job* jp = &J;
   if ((st = launch_transform(&c, &jp, 1))) return st;
-  JXG_HIP(hipMemcpyAsync(d_hist, c->hist_ac.p, kMaxClusters * kAlpha * 4, hipMemcpyDeviceToDevice, s));
-  JXG_HIP(hipMemcpyAsync(d_hist + (size_t)kMaxClusters * kAlpha, c->bigcount.p, 16,
+  JXG_HIP(hipMemcpyAsync(d_hist, c->hist_ac.d, kMaxClusters * kAlpha * 4, hipMemcpyDeviceToDevice, s));
+  JXG_HIP(hipMemcpyAsync(d_hist + (size_t)kMaxClusters * kAlpha, c->bigcount.d, 16,
                          hipMemcpyDeviceToDevice, s));
   // the send list (then the receive list) of the record exchange
   const Exchange& X = J.plan.x;
@@ -50,7 +50,7 @@ jxg_status shard_begin(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h, siz
               J.f.tiles_y, d_xbuf, c->xlist.p, (uint32_t)X.send.size()};
   launch_pack(pa, s);
   JXG_HIP(hipGetLastError());
-  JXG_HIP(hipEventRecord(c->ev[1], s));
+  JXG_HIP(hipEventRecord(c->ev[kEvMerged], s));
   JXG_HIP(hipStreamSynchronize(s));
   return JXG_OK;
 }
@@ -79,10 +79,10 @@ jxg_status shard_end(Ctx* c, const uint32_t* d_hist, const uint8_t* d_xbuf, size
   c->stats.num_groups = J.f.ngroups;
   c->stats.num_lf_groups = J.f.nlf;
   c->stats.bytes = *payload_bytes;
-  c->stats.ms_front = elapsed(c->ev[0], c->ev[1]);
-  c->stats.ms_front_kernel = elapsed(c->ev[9], c->ev[5]);
-  c->stats.ms_aq = elapsed(c->ev[0], c->ev[9]);
-  c->stats.ms_total = elapsed(c->ev[0], c->ev[4]);
+  c->stats.ms_front = elapsed(c->ev[kEvStart], c->ev[kEvMerged]);
+  c->stats.ms_front_kernel = elapsed(c->ev[kEvFrontStart], c->ev[kEvFrontDone]);
+  c->stats.ms_aq = elapsed(c->ev[kEvStart], c->ev[kEvFrontStart]);
+  c->stats.ms_total = elapsed(c->ev[kEvStart], c->ev[kEvAssembled]);
   c->stats.ms_host_call = ms_since(t_call);
   c->job.reset();
   return JXG_OK;
@@ -108,7 +108,7 @@ jxg_status shard_finish(Ctx* c, Job& J, size_t* payload_bytes, bool sync) {
   hw[1] = J.presets ? 2 : 1;
   // the rank, the frame's loop-filter code, the 128 / 256 px kinds the rank's
   // groups use (their quant tables go into HfGlobal, effort >= 8)
-  hw[2] = J.plan.rank | J.lf << 16 | (J.big ? big_mask(c->h_bigcount.p) : 0u) << 24;
+  hw[2] = J.plan.rank | J.lf << 16 | (J.big ? big_mask(c->bigcount.h) : 0u) << 24;
   hw[3] = J.plan.world;
   hw[4] = J.w;
   hw[5] = J.h;

@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "jxg_dequant.h"
+
 namespace jxg {
 
 struct MergeTables {
@@ -38,20 +40,6 @@ struct ReconTables {
 };
 ReconTables build_recon_tables(uint32_t global_scale);
 
-// DequantMatrices of HfGlobal [ext quant_weights.cc]: all_default when mask is
-// 0, else Library for every table but those of the big kinds in mask (bit 0
-// 128X64, 1 128X128, 2 256X128, 3 256X256: the kinds the frame uses, effort
-// >= 8), which are written in mode DCT with the binary16 parameters
-// build_big_tables quantizes with (== oracle/encode.c put_dequant_matrices),
-// so no decoder default is involved for them
-class BitWriter;
-void write_dequant_matrices(BitWriter& w, uint32_t mask);
-// whether bits[channel][band] (binary16 words of a DCT-mode table as the
-// stream carries them) are the parameters write_dequant_matrices writes for
-// big kind k -- the ones build_recon_tables reconstructs with (the decoder)
-bool dequant_params_match(int k, const uint16_t* bits /* [3][8] */);
-// the binary16 value nearest v (ties to even) and its bits (== oracle/merge.c)
-double f16_round(double v);
-uint32_t f16_bits(double v);
+// (DequantMatrices, the big kinds' binary16 parameters: jxg_dequant.h)
 
 }  // namespace jxg
