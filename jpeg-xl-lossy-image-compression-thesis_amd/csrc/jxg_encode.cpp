@@ -88,7 +88,7 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
     JXG_HIP(c->ent.ensure(nb));
     JXG_HIP(c->xyb_tiles.ensure((size_t)ntiles * 3 * 4096));
     JXG_HIP(c->mcost.ensure((size_t)ntiles * kNumShapes * 32));
-    JXG_HIP(c->mwork.ensure(1 + (size_t)ntiles * kNumShapes));
+    JXG_HIP(c->mwork.ensure(merge_work_words(ntiles)));
   }
   // the plan's tile, LF-group and pass-group lists: uploaded when the plan
   // changes (one key for them and the LF row cache below)

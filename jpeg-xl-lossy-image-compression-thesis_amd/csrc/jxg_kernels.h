@@ -76,8 +76,18 @@ constexpr int kNumKinds = 6;
 constexpr int kKindOff[kNumKinds + 1] = {0, 128, 384, 896, 1920, 3968, 8064};
 constexpr int kNumShapes = 9;
 constexpr int kShapeOff[kNumShapes + 1] = {0, 128, 256, 512, 1024, 1536, 2560, 4608, 6656, 10752};
+// merge_write's varblock lists (MergeArgs::work): a tile holds at most
+// 64 / (blocks of the shape) varblocks of a shape, so list si has room for
+// ntiles * kShapeSlots[si] entries (every block pair merged: 105 per tile)
+constexpr int kMergeWorkHead = 16;  // the nine counts, padded
+constexpr int kShapeSlots[kNumShapes] = {32, 32, 16, 8, 8, 4, 2, 2, 1};
+constexpr int kShapeSlotOff[kNumShapes + 1] = {0, 32, 64, 80, 88, 96, 100, 102, 104, 105};
+constexpr size_t merge_list_off(int si, uint32_t ntiles) {
+  return kMergeWorkHead + (size_t)ntiles * kShapeSlotOff[si];
+}
+constexpr size_t merge_work_words(uint32_t ntiles) { return merge_list_off(kNumShapes, ntiles); }
 struct MergeArgs {
-  const float* xyb;     // [tiles][3][64][64] XYB tiles (front kernel)
+  const float* xyb;    // [tiles][3][64][64] XYB tiles (front kernel)
   uint32_t bxs, bys, tiles_x, ntiles;  // ntiles: entries of tile_list (or all tiles)
   const uint32_t* tile_list;           // shard: tile ids, or null
   uint32_t proposals;
@@ -97,9 +107,10 @@ struct MergeArgs {
   const float* iwy;     // [kShapeOff[9]] 1 / Y weight
   const float* sdk;     // [3][kShapeOff[9]] distortion weights (dist_weight), same layout
   const uint16_t* nat;  // [kShapeOff[9]] natural-order position
-  uint32_t* work;       // [1 + tiles * 9]: count, then (tile << 4 | shape) of every
-                        //   (tile, shape) holding a chosen varblock (resolve -> write)
-  uint32_t nwrite;      // merge_write workgroups (persistent loop over work)
+  uint32_t* work;       // [merge_work_words(tiles)]: the nine shapes' counts, then per shape
+                        //   the (tile << 6 | first block) of every chosen varblock, list of
+                        //   shape si at merge_list_off(si, ntiles) (resolve -> write)
+  uint32_t nwrite;      // merge_write workgroups (persistent loop over the dense passes)
   const int8_t* cmap;   // [2][tiles_all] chroma from luma (front kernel)
   uint32_t ntiles_all;
 };

@@ -24,11 +24,20 @@
 //   merge_resolve one wave per tile: per level (16, 32, 64 px) and region,
 //                 keep / full / two tall / two wide halves with the
 //                 TryMergeAcs comparison (`candidate >= current` keeps: NaN
-//                 estimates are accepted, combined.diff:294 context).
-//   merge_write   one workgroup per (tile, shape) that holds chosen varblocks:
-//                 the same transform + quantization, coefficients scattered to
-//                 natural-order slices of the covered blocks, non-zero counts,
-//                 quant field, and the DC of each covered block from the LLF.
+//                 estimates are accepted, combined.diff:294 context).  Every
+//                 chosen varblock (tile, first block) is appended to the list
+//                 of its shape.
+//   merge_write   persistent workgroups over dense passes: a pass is one shape
+//                 and up to NV(shape) entries of its list, entry k in slot k
+//                 of the 64x64 LDS image whatever tile it comes from, so a
+//                 pass costs what the chosen area costs (one workgroup per
+//                 (tile, shape) ran 0.28 full at 8K).  The same transform +
+//                 quantization with the source tile, the block origin and the
+//                 chroma-from-luma factors per slot (WriteLds), coefficients
+//                 scattered to natural-order slices of the covered blocks,
+//                 non-zero counts, quant field, and the DC of each covered
+//                 block from the LLF.  A varblock's results depend on its own
+//                 pixels and blocks only, not on its slot or pass.
 // Float op order == oracle/merge.c (jxo_varblock, jxo_llf_dc, jxo_merge_tile).
 #include <float.h>
 
@@ -182,6 +191,16 @@ struct MergeLds {
   uint8_t braw[64];       // front-kernel quant field (raw) of the tile's blocks
   int any;
 };
+// merge_write: slot v of the image holds a varblock of any tile (a dense
+// pass), so what the eval kernel derives from (P.tile, P.by0(v), P.bx0(v)) is
+// per slot here; the image position of a slot stays P.off(v, plane)
+struct WriteLds : MergeLds {
+  uint32_t ssrc[32];  // a.xyb offset (floats) of the varblock's first pixel, channel 0
+  uint32_t sgb[32];   // frame block index of its first block
+  float skc[2][32];   // its tile's chroma-from-luma factors: X, B
+};
+template <class L>
+constexpr bool kIsWrite = std::is_same<L, WriteLds>::value;
 __device__ __forceinline__ float& llf_at(MergeLds& S, int c, int b) { return S.llf[c][b]; }
 // the two transform passes of a tile: pass 0 = Y (plane 0) and X (plane 1),
 // pass 1 = B (plane 1); local channel lc of a pass -> frame channel (X 0, Y 1,
@@ -265,8 +284,10 @@ __device__ __forceinline__ void load_row(const float* src, float* d) {
     d[4 * q + 3] = u.w;
   }
 }
-template <int C, int NCH>
-__device__ __forceinline__ void row_pass(const MergeArgs& a, const Pass& P, MergeLds& S, int pass) {
+// (write: the source row comes from the slot's own tile and origin)
+template <int C, int NCH, class L>
+__device__ __forceinline__ void row_pass(const MergeArgs& a, const Pass& P, L& S, int pass) {
+  constexpr bool WRITE = kIsWrite<L>;
   const float* tsrc = a.xyb + (size_t)P.tile * (3 * 4096);
   const int R = P.R(), lvr = P.lNV() + P.lR();
   if constexpr (C == 64) {
@@ -280,8 +301,10 @@ __device__ __forceinline__ void row_pass(const MergeArgs& a, const Pass& P, Merg
       if (pp >= npairs) continue;
       const int c = r >> lvr, v = (r >> P.lR()) & (P.NV() - 1), y = r & (R - 1);
       if (!S.valid[v]) continue;
-      const float4* s0 =
-          reinterpret_cast<const float4*>(tsrc + pass_src(pass, c) * 4096 + (P.by0(v) * 8 + y) * 64);
+      const float* src0;
+      if constexpr (WRITE) src0 = a.xyb + S.ssrc[v] + pass_src(pass, c) * 4096 + y * 64;
+      else src0 = tsrc + pass_src(pass, c) * 4096 + (P.by0(v) * 8 + y) * 64;
+      const float4* s0 = reinterpret_cast<const float4*>(src0);
       const float4* s1 = s0 + 16;  // row y + 1
       f2 t[32];
       // 16-byte loads of x[4q..4q+3] and of its mirror x[60-4q..63-4q]
@@ -321,8 +344,11 @@ __device__ __forceinline__ void row_pass(const MergeArgs& a, const Pass& P, Merg
       if (r < nrows) {
         int c, v, y;
         row_of(r, c, v, y);
-        load_row<C>(tsrc + pass_src(pass, c) * 4096 + (P.by0(v) * 8 + y) * 64 + P.bx0(v) * 8,
-                    buf[k]);
+        if constexpr (WRITE)  // (an empty slot reads tile 0: in bounds, never stored)
+          load_row<C>(a.xyb + S.ssrc[v] + pass_src(pass, c) * 4096 + y * 64, buf[k]);
+        else
+          load_row<C>(tsrc + pass_src(pass, c) * 4096 + (P.by0(v) * 8 + y) * 64 + P.bx0(v) * 8,
+                      buf[k]);
       } else {
 #pragma unroll
         for (int q = 0; q < C; q++) buf[k][q] = 0.0f;
@@ -525,13 +551,15 @@ __device__ __forceinline__ void group_all_reduce(float& cp, int& packed, int C) 
   if (C > 32) grp_step<32>(cp, packed);
 }
 
-template <int RPC, bool WRITE, int CH>
-__device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, MergeLds& S, const QTab<RPC>& T) {
+template <int RPC, bool WRITE, int CH, class L>
+__device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L& S, const QTab<RPC>& T) {
+  static_assert(WRITE == kIsWrite<L>, "the write kernel's LDS carries the per-slot arrays");
   constexpr int cidx = CH == 1 ? 0 : (CH == 0 ? 1 : 2);  // 0 Y, 1 X, 2 B
   const int C = P.C(), NV = P.NV();
   // chroma from luma of the tile (front kernel): X - kx Yd, B - kb Yd
+  // (write: of the slot's tile, from setup_slots)
   float kc = 0.0f;
-  if (CH != 1) {
+  if (!WRITE && CH != 1) {
     const float f = (float)a.cmap[(CH == 0 ? 0u : a.ntiles_all) + (uint32_t)P.tile];
     kc = CH == 0 ? f * (1.0f / 84.0f) : 1.0f + f * (1.0f / 84.0f);
   }
@@ -540,7 +568,8 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, Me
     const int j = threadIdx.x + it * kMThreads;
     const int ch = j >> (P.lNV() + P.lC()), v = (j >> P.lC()) & (NV - 1), x = j & (C - 1);
     if (!S.valid[v]) continue;  // the varblock's C lanes leave together
-    const int bx0 = P.bx0(v), by0 = P.by0(v);
+    const int bx0 = P.bx0(v), by0 = P.by0(v);  // image position (the LLF's index)
+    if constexpr (WRITE && CH != 1) kc = S.skc[CH == 0 ? 0 : 1][v];
     const float scale = (float)a.G * (float)S.vraw[v] / 65536.0f;
     float* cplane = S.co + P.off(v, chan_plane(CH)) + x;
     const float* yd = S.co + P.off(v, 0) + x;
@@ -624,9 +653,11 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, Me
           const int qq = (int)sqs[h];  // (vq < 0 ? -qa : qa)
           const int p = nat[kk + h];
           const int sl = p >> 6;
-          const int lbx = bx0 + (sl & (P.cx() - 1)), lby = by0 + (sl >> P.lcx);
-          const size_t gb = (size_t)(P.ty * 8 + lby) * a.bxs + P.tx * 8 + lbx;
-          a.ac[(gb * 3 + CH) * 64 + (p & 63)] = (int16_t)qq;
+          // covered block sl of the slot's varblock, from its first block
+          if constexpr (WRITE) {
+            const size_t gb = (size_t)S.sgb[v] + (size_t)(sl >> P.lcx) * a.bxs + (sl & (P.cx() - 1));
+            a.ac[(gb * 3 + CH) * 64 + (p & 63)] = (int16_t)qq;
+          }
         }
       }
       // error in steps times the distortion weight (oracle jxo_dist_weight);
@@ -655,8 +686,8 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, Me
 
 // transform + quantize every valid varblock of the pass; leaves per-varblock
 // bits / non-zeros and the chunk sums in LDS
-template <bool WRITE>
-__device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& P, MergeLds& S) {
+template <bool WRITE, class L>
+__device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& P, L& S) {
 #ifdef JXG_MERGE_PROFILE
   unsigned long long mprof_t0 = 0;
 #endif
@@ -727,11 +758,16 @@ __device__ __forceinline__ float varblock_dist(const Pass& P, const MergeLds& S,
   return (pc[0] + pc[1]) + pc[2];
 }
 
-// per-varblock setup, before the tile-load barrier: validity (eval: the
-// level region lies inside the frame's blocks; write: the resolved map holds
-// the shape there), hook-F indices, sums reset; the blocks' quant field goes
-// to LDS (the varblock maxima are taken after the barrier: vraw_pass)
-template <bool WRITE>
+// AdjustQuantBias of q: 0 -> 0, 1 -> 1 - 0.0700..., else q - 0.145 / q (the
+// per-coefficient expression, tabulated)
+__device__ __forceinline__ void fill_btab(MergeLds& S) {
+  for (int i = threadIdx.x; i < 256; i += kMThreads)
+    S.btab[i] = i == 0 ? 0.0f : (i == 1 ? 1.0f - 0.07005449891748593f : (float)i - 0.145f / (float)i);
+}
+// eval: per-varblock setup, before the tile-load barrier: validity (the
+// level region lies inside the frame's blocks), hook-F indices, sums reset;
+// the blocks' quant field goes to LDS (the varblock maxima are taken after
+// the barrier: vraw_pass)
 __device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& P, MergeLds& S,
                                                 int nbx, int nby) {
   const int t = threadIdx.x;
@@ -747,15 +783,11 @@ __device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& 
     if (v < P.NV()) {
       const int bx0 = P.bx0(v), by0 = P.by0(v);
       const size_t gb0 = (size_t)(P.ty * 8 + by0) * a.bxs + P.tx * 8 + bx0;
-      if (WRITE) {
-        ok = bx0 < nbx && by0 < nby && a.acs[gb0] == (uint8_t)P.type;
-      } else {
-        ok = (((bx0 >> P.ls) + 1) << P.ls) <= nbx && (((by0 >> P.ls) + 1) << P.ls) <= nby;
-        if (ok && (a.proposals & 2u)) {
-          S.vr3[v][0] = a.homog[gb0 * 3 + 0];
-          S.vr3[v][1] = a.homog[gb0 * 3 + 1];
-          S.vr3[v][2] = a.homog[gb0 * 3 + 2];
-        }
+      ok = (((bx0 >> P.ls) + 1) << P.ls) <= nbx && (((by0 >> P.ls) + 1) << P.ls) <= nby;
+      if (ok && (a.proposals & 2u)) {
+        S.vr3[v][0] = a.homog[gb0 * 3 + 0];
+        S.vr3[v][1] = a.homog[gb0 * 3 + 1];
+        S.vr3[v][2] = a.homog[gb0 * 3 + 2];
       }
     }
     S.valid[v] = ok;
@@ -763,10 +795,7 @@ __device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& 
     S.vbits[v] = 0;
     S.vnz[v][0] = S.vnz[v][1] = S.vnz[v][2] = 0;
   }
-  // AdjustQuantBias of q: 0 -> 0, 1 -> 1 - 0.0700..., else q - 0.145 / q (the
-  // per-coefficient expression, tabulated)
-  for (int i = t; i < 256; i += kMThreads)
-    S.btab[i] = i == 0 ? 0.0f : (i == 1 ? 1.0f - 0.07005449891748593f : (float)i - 0.145f / (float)i);
+  fill_btab(S);
 }
 // varblock quant field = max raw over its covered blocks (after a barrier):
 // one thread per block, an LDS atomic max into its varblock (round 6: one
@@ -782,6 +811,52 @@ __device__ __forceinline__ void vraw_pass(const MergeArgs& a, const Pass& P, Mer
     if (v < P.NV() && S.valid[v]) atomicMax(&S.vraw[v], (int)S.braw[b] + 1);
   }
 }
+// write: slot v takes entry first + v of the shape's list (n entries in this
+// pass; the empty slots of a shape's last pass are invalid): its tile's XYB
+// and chroma-from-luma factors, its first block in the frame; sums reset
+__device__ __forceinline__ void setup_slots(const MergeArgs& a, const Pass& P, WriteLds& S,
+                                            const uint32_t* list, uint32_t first, uint32_t n) {
+  (void)P;
+  const int v = threadIdx.x;
+  if (v < 32) {
+    const bool ok = (uint32_t)v < n;
+    uint32_t src = 0, gb0 = 0;
+    float kx = 0.0f, kb = 0.0f;
+    if (ok) {
+      const uint32_t e = list[first + v], tile = e >> 6, by = (e >> 3) & 7u, bx = e & 7u;
+      const uint32_t tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+      src = tile * (3u * 4096u) + by * (8u * 64u) + bx * 8u;
+      gb0 = (ty * 8u + by) * a.bxs + tx * 8u + bx;
+      // chroma from luma of the tile (front kernel): X - kx Yd, B - kb Yd
+      kx = (float)a.cmap[tile] * (1.0f / 84.0f);
+      kb = 1.0f + (float)a.cmap[a.ntiles_all + tile] * (1.0f / 84.0f);
+    }
+    S.ssrc[v] = src;
+    S.sgb[v] = gb0;
+    S.skc[0][v] = kx;
+    S.skc[1][v] = kb;
+    S.valid[v] = ok;
+    S.vraw[v] = 0;  // (vraw_slots: atomic max over the covered blocks)
+    S.vbits[v] = 0;
+    S.vnz[v][0] = S.vnz[v][1] = S.vnz[v][2] = 0;
+  }
+  fill_btab(S);
+}
+// write: the varblock quant field as in vraw_pass, one thread per image
+// block, the block's front-kernel value read from the slot's own varblock:
+// no other pass stores to those blocks (varblocks are disjoint), and this
+// slot stores them only after the maxima are taken
+__device__ __forceinline__ void vraw_slots(const MergeArgs& a, const Pass& P, WriteLds& S) {
+  const int b = threadIdx.x;
+  if (b < 64) {
+    const int lbx = b & 7, lby = b >> 3;
+    const int v = ((lby >> P.lcy) << P.lGX()) | (lbx >> P.lcx);
+    if (v < P.NV() && S.valid[v]) {
+      const size_t gb = (size_t)S.sgb[v] + (size_t)(lby & (P.cy() - 1)) * a.bxs + (lbx & (P.cx() - 1));
+      atomicMax(&S.vraw[v], (int)a.qf[gb] + 1);
+    }
+  }
+}
 
 __device__ __forceinline__ int max_level(const MergeArgs& a) {
   return a.max_s >= 8 ? 3 : (a.max_s >= 4 ? 2 : 1);
@@ -791,7 +866,7 @@ __global__ __launch_bounds__(kMThreads) __attribute__((amdgpu_waves_per_eu(JXG_M
 void merge_eval_kernel(Batch<MergeArgs> bt_) {
   const MergeArgs& a = bt_.a[blockIdx.z];  // the batch's frame
   __shared__ __attribute__((aligned(16))) MergeLds S;
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.work[0] = 0;  // merge_resolve's work-list count
+  if (blockIdx.x == 0 && threadIdx.x < kNumShapes) a.work[threadIdx.x] = 0;  // merge_resolve's list counts
   int tile, si;
   if (!decode_wg(a, tile, si)) return;
   const Pass P = make_pass(a, tile, si);
@@ -801,7 +876,7 @@ void merge_eval_kernel(Batch<MergeArgs> bt_) {
 #ifdef JXG_MERGE_PROFILE
   const unsigned long long t_setup = __builtin_readcyclecounter();
 #endif
-  setup_varblocks<false>(a, P, S, nbx, nby);
+  setup_varblocks(a, P, S, nbx, nby);
   __syncthreads();
   vraw_pass(a, P, S);
 #ifdef JXG_MERGE_PROFILE
@@ -820,8 +895,9 @@ void merge_eval_kernel(Batch<MergeArgs> bt_) {
 }
 
 // one wave per tile (16 tiles per workgroup): levels in order, one lane per
-// region; then the tile's chosen shapes go to the merge_write work list (one
-// global atomic per workgroup)
+// region; then every chosen varblock (tile << 6 | first block) goes to its
+// shape's merge_write list (one global atomic per workgroup and shape; list
+// order varies from run to run, what merge_write stores does not)
 constexpr int kResolveWaves = 16;
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -831,13 +907,12 @@ __global__ __launch_bounds__(64 * kResolveWaves) void merge_resolve_kernel(Batch
   const MergeArgs& a = bt_.a[blockIdx.z];
   __shared__ float sEntW[kResolveWaves][64];
   __shared__ uint8_t sAcsW[kResolveWaves][64];
-  __shared__ uint32_t sCnt[kResolveWaves];
-  __shared__ uint32_t sBase;
+  __shared__ uint32_t sCnt[kResolveWaves][kNumShapes];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   float* sEnt = sEntW[wv];
   uint8_t* sAcs = sAcsW[wv];
   const int idx = blockIdx.x * kResolveWaves + wv;
-  uint32_t has = 0;
+  int my = -1;  // shape of the chosen varblock whose first block is this lane's
   int tile = 0;
   if (idx < (int)a.ntiles) {
     tile = a.tile_list ? (int)a.tile_list[idx] : idx;
@@ -906,35 +981,46 @@ __global__ __launch_bounds__(64 * kResolveWaves) void merge_resolve_kernel(Batch
       a.acs[gb] = sAcs[t];
       a.ent[gb] = sEnt[t];  // the decisions' estimates: the 128 / 256 px levels' "current"
     }
-    // the shapes chosen somewhere in this tile
+    // the chosen varblock this block starts, if any
     if (in && !(sAcs[t] & 0x80)) {
 #pragma unroll
-      for (int si = 0; si < kNumShapes; si++) has |= sAcs[t] == kShapes[si].type ? 1u << si : 0u;
+      for (int si = 0; si < kNumShapes; si++) my = sAcs[t] == kShapes[si].type ? si : my;
     }
+  }
+  // per shape: the wave's varblocks counted, then one slot range per
+  // workgroup (one atomic per shape that has any), lanes in block order
+  uint32_t rank = 0;
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) has |= __shfl_xor(has, m, 64);
+  for (int si = 0; si < kNumShapes; si++) {
+    const uint64_t bal = __ballot(my == si);
+    if (t == 0) sCnt[wv][si] = (uint32_t)__popcll(bal);
+    if (my == si) rank = (uint32_t)__popcll(bal & ((1ull << t) - 1ull));
   }
-  if (t == 0) sCnt[wv] = (uint32_t)__popc(has);
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x < kNumShapes) {
+    const int si = threadIdx.x;
     uint32_t tot = 0;
-    for (int w = 0; w < kResolveWaves; w++) tot += sCnt[w];
-    sBase = tot ? atomicAdd(a.work, tot) : 0u;
+    for (int w = 0; w < kResolveWaves; w++) tot += sCnt[w][si];
+    uint32_t base = tot ? atomicAdd(a.work + si, tot) : 0u;
+    for (int w = 0; w < kResolveWaves; w++) {  // count -> the wave's first slot
+      const uint32_t n = sCnt[w][si];
+      sCnt[w][si] = base;
+      base += n;
+    }
   }
   __syncthreads();
-  uint32_t base = sBase;
-  for (int w = 0; w < wv; w++) base += sCnt[w];
-  if (t < kNumShapes && ((has >> t) & 1u))
-    a.work[1 + base + __popc(has & ((1u << t) - 1u))] = (uint32_t)tile << 4 | (uint32_t)t;
+  if (my >= 0)
+    a.work[merge_list_off(my, a.ntiles) + sCnt[wv][my] + rank] = (uint32_t)tile << 6 | (uint32_t)t;
 }
 
-// one (tile, shape) entry of the work list; returns after its last LDS use
-__device__ __forceinline__ void write_entry(const MergeArgs& a, int tile, int si, MergeLds& S) {
-  const Pass P = make_pass(a, tile, si);
-  const int nbx = min(8, (int)a.bxs - P.tx * 8), nby = min(8, (int)a.bys - P.ty * 8);
-  setup_varblocks<true>(a, P, S, nbx, nby);
+// one dense pass: entries first .. first + n - 1 of shape si's list, entry k
+// in slot k of the image; returns after its last LDS use
+__device__ __forceinline__ void write_pass(const MergeArgs& a, int si, uint32_t first, uint32_t n,
+                                           WriteLds& S) {
+  const Pass P = make_pass(a, 0, si);  // (tile, tx, ty: per slot, S.ssrc / S.sgb)
+  setup_slots(a, P, S, a.work + merge_list_off(si, a.ntiles), first, n);
   __syncthreads();
-  vraw_pass(a, P, S);
+  vraw_slots(a, P, S);
   transform_quant<true>(a, P, S);
   // per covered block: non-zero counts, quant field, LLF-derived DC
   const int cb = P.cy() * P.cx(), lcb = P.lcy + P.lcx;
@@ -944,8 +1030,8 @@ __device__ __forceinline__ void write_entry(const MergeArgs& a, int tile, int si
     const int v = i >> lcb, k = i & (cb - 1);
     if (!S.valid[v]) continue;
     const int iy = k >> P.lcx, ix = k & (P.cx() - 1);
-    const int bx0 = P.bx0(v), by0 = P.by0(v);
-    const size_t gb = (size_t)(P.ty * 8 + by0 + iy) * a.bxs + P.tx * 8 + bx0 + ix;
+    const int bx0 = P.bx0(v), by0 = P.by0(v);  // image position (the LLF's index)
+    const size_t gb = (size_t)S.sgb[v] + (size_t)iy * a.bxs + ix;
     for (int c = 0; c < 3; c++) {
       const int n = S.vnz[v][c];
       a.nz[c * nb + gb] = (uint16_t)(k == 0 ? n : (n + cb - 1) >> lcb);
@@ -990,17 +1076,36 @@ __device__ __forceinline__ void write_entry(const MergeArgs& a, int tile, int si
   }
 }
 
-// persistent workgroups over the (tile, shape) entries the resolve kernel
-// listed: only (tile, shape) pairs holding a chosen varblock cost anything
+// persistent workgroups over the dense passes of the nine lists the resolve
+// kernel filled: a pass is one shape and up to NV(shape) chosen varblocks, so
+// only the chosen area costs anything (the last pass of a shape is partly
+// filled).  Pass order: 64x64 first -- the longest passes, one varblock each
+// -- then the shapes by falling size.
 __global__ __launch_bounds__(kMThreads) __attribute__((amdgpu_waves_per_eu(JXG_MERGE_WRITE_WPE)))
 void merge_write_kernel(Batch<MergeArgs> bt_) {
   const MergeArgs& a = bt_.a[blockIdx.z];
-  __shared__ __attribute__((aligned(16))) MergeLds S;
-  const uint32_t n = __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)a.work);
-  for (uint32_t w = blockIdx.x; w < n; w += gridDim.x) {
-    const uint32_t e = a.work[1 + w];
-    write_entry(a, (int)(e >> 4), (int)(e & 15u), S);
-    __syncthreads();  // LDS reuse by the next entry
+  __shared__ __attribute__((aligned(16))) WriteLds S;
+  uint32_t cnt[kNumShapes], total = 0;
+#pragma unroll
+  for (int si = 0; si < kNumShapes; si++) {
+    cnt[si] = __builtin_amdgcn_readfirstlane(((volatile uint32_t*)a.work)[si]);
+    total += (cnt[si] + kShapeSlots[si] - 1) / kShapeSlots[si];
+  }
+  for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+    int si = 0;
+    uint32_t first = 0, n = 0, start = 0;
+#pragma unroll
+    for (int j = kNumShapes - 1; j >= 0; j--) {
+      const uint32_t np = (cnt[j] + kShapeSlots[j] - 1) / kShapeSlots[j];
+      if (w >= start && w - start < np) {
+        si = j;
+        first = (w - start) * kShapeSlots[j];
+        n = min((uint32_t)kShapeSlots[j], cnt[j] - first);
+      }
+      start += np;
+    }
+    write_pass(a, si, first, n, S);
+    __syncthreads();  // LDS reuse by the next pass
   }
 }
 
