@@ -467,6 +467,66 @@ typedef struct {
 } jxg_decode_batch_stats;
 jxg_status jxg_decode_batch_timings(jxg_ctx* ctx, jxg_decode_batch_stats* stats);
 
+/* ---- sweep: one image over many settings in one call ----
+ * The reference harness encodes every image at 10 distances x 5 efforts and
+ * measures each result (benchmark.rs:637-677).  A sweep uploads the image once
+ * (or reads the caller's device copy) and runs the n points through the
+ * streaming pipeline's lanes of this one context: a frame carries its point
+ * and the lane it lands on encodes with it (a lane's parameters are set at
+ * every submit; lanes grow whatever buffers a point needs).  outs[i] is
+ * byte-identical to jxg_encode_rgb8 of the image on a context created with
+ * points[i].  quality 1 / 2: after a frame's codestream is assembled, its
+ * lane runs the reconstruction chain of jxg_reconstruct_rgb8 on its own
+ * coefficients and stream, ending in a kernel that converts to sRGB8 and sums
+ * the squared error against the original in one pass (the decoded image is
+ * stored only when quality == 2, for the SSIM kernels); q[i] is bit-equal to
+ * jxg_compare_rgb8_device(original, jxg_reconstruct_rgb8_device) after a
+ * one-at-a-time encode with points[i] (ssim NaN with quality 1 or under
+ * 11 x 11).  The float planes (24 bytes per block-padded pixel and lane, plus
+ * 3 with quality 2) are allocated by the first quality sweep and released by
+ * jxg_destroy.  Small frames, which the pipeline batches four to a launch,
+ * go one point per launch (a change of point closes the open batch).
+ * The context's own distance / effort / proposals / flags play no part and
+ * are unchanged afterwards; like a batch encode the call ends what
+ * jxg_reconstruct_rgb8 could read.  A device image must stay unchanged until
+ * the call returns.
+ * Call-level errors, nothing touched: JXG_ERR_INVALID_ARG for a null ctx /
+ * rgb / points / outs, n == 0, a size jxg_encode_rgb8 refuses, a stride under
+ * 3 * xsize, quality outside 0..2, q non-NULL with quality 0 or NULL
+ * otherwise, or streamed frames pending.  Otherwise every point gets its
+ * status in statuses[i] (may be NULL): JXG_ERR_INVALID_ARG for a distance,
+ * effort or proposals jxg_create refuses, or JXG_FLAG_KEEP_MAPS; a refused
+ * point's output is {NULL, 0} (its q[i] zeroed) and the others complete.
+ * Returns the first non-OK status in index order.  JXG_ERR_HIP / JXG_ERR_OOM
+ * (and any other failure of the pipeline) are call-level: every output is
+ * released and every status filled. */
+typedef struct {
+  float distance;
+  int effort;
+  uint32_t proposals;
+  uint32_t flags;
+} jxg_sweep_point;
+jxg_status jxg_sweep_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t xsize, uint32_t ysize,
+                          size_t row_stride, const jxg_sweep_point* points, uint32_t n,
+                          int quality, jxg_buffer* outs /* [n] */,
+                          jxg_quality* q /* [n]; NULL iff quality == 0 */,
+                          jxg_status* statuses /* [n] or NULL */);
+jxg_status jxg_sweep_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsize, uint32_t ysize,
+                                 size_t row_stride, const jxg_sweep_point* points, uint32_t n,
+                                 int quality, jxg_buffer* outs, jxg_quality* q,
+                                 jxg_status* statuses);
+/* the context's last jxg_sweep_rgb8[_device] */
+typedef struct {
+  uint32_t points;   /* points encoded (refused ones not counted) */
+  uint32_t lanes;    /* pipeline lanes the frame size gets (jxg_pipeline_depth's lanes) */
+  float ms_call;     /* the whole call, host wall clock */
+  float ms_upload;   /* host variant: the image's upload (host wall clock) */
+  float ms_encode;   /* device time by events, summed over points: frame start -> emission */
+  float ms_recon;    /*   reconstruction chain incl. the fused colour + error kernel */
+  float ms_metrics;  /*   SSIM kernels and the results' download */
+} jxg_sweep_stats;
+jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats);
+
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result
  * discarded), which allocates the size's device buffers and loads every

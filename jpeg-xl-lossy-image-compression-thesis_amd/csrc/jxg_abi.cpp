@@ -389,6 +389,46 @@ jxg_status jxg_decode_batch_timings(jxg_ctx* ctx, jxg_decode_batch_stats* stats)
   return JXG_OK;
 }
 
+// the call-level checks of a sweep (everything that needs no device)
+static bool sweep_args_ok(jxg_ctx* ctx, const void* rgb, uint32_t w, uint32_t h, size_t stride,
+                          const jxg_sweep_point* points, uint32_t n, int quality,
+                          const jxg_buffer* outs, const jxg_quality* q) {
+  return ctx && rgb && points && outs && n != 0 && frame_args_ok(w, h, stride) && quality >= 0 &&
+         quality <= 2 && (quality != 0) == (q != nullptr);
+}
+
+jxg_status jxg_sweep_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride,
+                          const jxg_sweep_point* points, uint32_t n, int quality, jxg_buffer* outs,
+                          jxg_quality* q, jxg_status* statuses) {
+  if (!sweep_args_ok(ctx, rgb, w, h, stride, points, n, quality, outs, q))
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : guarded([&] {
+    return sweep(c, rgb, false, w, h, stride, points, n, quality, outs, q, statuses);
+  });
+}
+
+jxg_status jxg_sweep_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                 size_t stride, const jxg_sweep_point* points, uint32_t n,
+                                 int quality, jxg_buffer* outs, jxg_quality* q,
+                                 jxg_status* statuses) {
+  if (!sweep_args_ok(ctx, d_rgb, w, h, stride, points, n, quality, outs, q))
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : guarded([&] {
+    return sweep(c, static_cast<const uint8_t*>(d_rgb), true, w, h, stride, points, n, quality,
+                 outs, q, statuses);
+  });
+}
+
+jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats) {
+  if (!ctx || !stats) return JXG_ERR_INVALID_ARG;
+  *stats = reinterpret_cast<const Ctx*>(ctx)->sw.stats;
+  return JXG_OK;
+}
+
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
   Ctx* c;

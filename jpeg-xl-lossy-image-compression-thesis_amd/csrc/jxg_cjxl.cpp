@@ -7,13 +7,21 @@
 // (gray / gray+alpha / RGB / RGBA, non-interlaced; alpha dropped) or binary
 // PPM, encodes on the GPU and writes the codestream.  Exit 0 on success; a
 // message on stderr and exit 1 otherwise.
+//
+// `jxg_cjxl INPUT OUTDIR --sweep=LIST` encodes INPUT at every `distance effort`
+// line of the file LIST in one process and one jxg_sweep_rgb8 call (the other
+// flags apply to every point) and writes OUTDIR/<stem>-<distance>-<effort>.jxl,
+// the harness's names (benchmark.rs:644-650) -- its per-image loop without a
+// process start per setting.
 #include <zlib.h>
 
+#include <charconv>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <string>
 #include <thread>
 #include <vector>
@@ -180,6 +188,83 @@ bool decode_ppm(const std::vector<uint8_t>& d, std::vector<uint8_t>& rgb, uint32
   return true;
 }
 
+// Rust's `{}` of an f64 (the harness's file names): the shortest digits that
+// round-trip, never an exponent, "1" for 1.0
+std::string rust_f64(double v) {
+  char buf[400];
+  const auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::fixed);
+  return std::string(buf, r.ptr);
+}
+
+struct SweepLine {
+  double distance;
+  int effort;
+};
+bool read_sweep_list(const char* path, std::vector<SweepLine>& out) {
+  FILE* f = std::fopen(path, "r");
+  if (!f) return false;
+  char line[256];
+  bool ok = true;
+  while (ok && std::fgets(line, sizeof(line), f)) {
+    const char* s = line + std::strspn(line, " \t\r\n");
+    if (!*s || *s == '#') continue;
+    SweepLine l{};
+    ok = std::sscanf(s, "%lf %d", &l.distance, &l.effort) == 2;
+    if (ok) out.push_back(l);
+  }
+  std::fclose(f);
+  return ok && !out.empty();
+}
+
+// INPUT at every point of the list -> OUTDIR/<stem>-<distance>-<effort>.jxl
+int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* outdir,
+              const std::vector<SweepLine>& list, const std::vector<uint8_t>& rgb, uint32_t w,
+              uint32_t h) {
+  const size_t n = list.size();
+  std::vector<jxg_sweep_point> pts(n);
+  for (size_t i = 0; i < n; i++)
+    pts[i] = jxg_sweep_point{(float)list[i].distance, list[i].effort, p.proposals, p.flags};
+  std::vector<jxg_buffer> outs(n, jxg_buffer{nullptr, 0});
+  std::vector<jxg_status> sts(n, JXG_OK);
+  const auto t0 = std::chrono::steady_clock::now();
+  const jxg_status st = jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(),
+                                       (uint32_t)n, 0, outs.data(), nullptr, sts.data());
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  bool any = false;
+  for (size_t i = 0; i < n; i++) any = any || outs[i].data;
+  if (st != JXG_OK && !any) {
+    std::fprintf(stderr, "sweep failed: %s\n", jxg_status_str(st));
+    return 1;
+  }
+  std::error_code ec;
+  std::filesystem::create_directories(outdir, ec);
+  const std::string stem = std::filesystem::path(input).stem().string();
+  int rc = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!outs[i].data) {  // a refused point: the harness skips it
+      std::fprintf(stderr, "distance %s effort %d: %s\n", rust_f64(list[i].distance).c_str(),
+                   list[i].effort, jxg_status_str(sts[i]));
+      rc = 1;
+      continue;
+    }
+    const std::string path = (std::filesystem::path(outdir) /
+                              (stem + "-" + rust_f64(list[i].distance) + "-" +
+                               std::to_string(list[i].effort) + ".jxl")).string();
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(outs[i].data, 1, outs[i].size, f) != outs[i].size) {
+      std::fprintf(stderr, "cannot write %s\n", path.c_str());
+      rc = 1;
+    }
+    if (f) std::fclose(f);
+    std::printf("Encoding [VarDCT, d%.3f, effort: %d], %u x %u, %zu bytes, %.3f bpp\n",
+                pts[i].distance, pts[i].effort, w, h, outs[i].size,
+                outs[i].size * 8.0 / ((double)w * h));
+  }
+  std::printf("Sweep of %zu points, %u x %u, %.2f MP/s\n", n, w, h,
+              (double)n * w * h / 1e6 / sec);
+  return rc;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -188,8 +273,10 @@ int main(int argc, char** argv) {
                  "usage: %s INPUT OUTPUT [--distance=D] [--effort=E] "
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
                  "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH]\n"
+                 "       %s INPUT OUTDIR --sweep=LIST [the same flags]   "
+                 "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
-                 argv[0]);
+                 argv[0], argv[0]);
     return 1;
   }
   // `cjxl IN OUT --distance=D --effort=E` with no other flag (the harness's
@@ -199,6 +286,7 @@ int main(int argc, char** argv) {
   // --jxg_recon=PATH (not a cjxl option): also write the decoded image of the
   // codestream, reconstructed on the GPU (jxg_reconstruct_rgb8), as a binary PPM
   const char* recon_path = nullptr;
+  const char* sweep_path = nullptr;  // --sweep=LIST: OUTPUT is a directory
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -240,6 +328,8 @@ int main(int argc, char** argv) {
       p.device = std::atoi(a + 9);
     else if (!std::strncmp(a, "--jxg_recon=", 12))
       recon_path = a + 12;
+    else if (!std::strncmp(a, "--sweep=", 8))
+      sweep_path = a + 8;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -265,6 +355,13 @@ int main(int argc, char** argv) {
   // JXG_CJXL_DECODE_ONLY=1 (tests, no GPU): write the decoded image as a
   // binary PPM to OUTPUT instead of encoding it
   const bool decode_only = std::getenv("JXG_CJXL_DECODE_ONLY") != nullptr;
+  std::vector<SweepLine> sweep_list;
+  if (sweep_path && (recon_path || decode_only || !read_sweep_list(sweep_path, sweep_list))) {
+    std::fprintf(stderr, "--sweep: %s\n",
+                 recon_path || decode_only ? "not with --jxg_recon / decode only"
+                                           : "cannot read the list (`distance effort` lines)");
+    return 1;
+  }
   std::thread maker;
   auto fail = [&](int code) {
     if (maker.joinable()) maker.join();
@@ -313,6 +410,11 @@ int main(int argc, char** argv) {
   if (st != JXG_OK) {
     std::fprintf(stderr, "jxg_create: %s\n", jxg_status_str(st));
     return 1;
+  }
+  if (sweep_path) {
+    const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h);
+    std::fflush(nullptr);
+    std::_Exit(rc);  // (as below: no exit-time teardown)
   }
   jxg_buffer out{};
   const auto t0 = std::chrono::steady_clock::now();

@@ -243,6 +243,9 @@ void ctx_destroy(Ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->decb.ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->sw.ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->rc.ev_sigma) (void)hipEventDestroy(c->rc.ev_sigma);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_write) (void)hipEventDestroy(c->ev_write);
   if (c->stream && !c->shared_stream) (void)hipStreamDestroy(c->stream);

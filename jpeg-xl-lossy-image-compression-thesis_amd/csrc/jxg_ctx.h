@@ -172,6 +172,10 @@ struct Ctx : EncArenas {
     DevBuf<uint32_t> big;
     DevBuf<uint8_t> rgb;
     uint32_t tab_g = 0;  // global scale the EPF sigma table was built for
+    // a sweep's chains: pinned staging of the sigma table alone and the event
+    // of its last copy
+    PinBuf<float> h_sigma;
+    hipEvent_t ev_sigma = nullptr;
     // the last encode was jxg_encode_rgb8[_device] of a w x h frame, whose
     // coefficients and maps are still in this context's buffers
     bool ok = false;
@@ -201,6 +205,14 @@ struct Ctx : EncArenas {
     size_t budget = 0;      // jxg_set_decode_batch_bytes (0: kDecBatchDefaultBytes)
     jxg_decode_batch_stats stats{};
   } decb;
+  // sweep (jxg_sweep_rgb8; jxg_sweep.cpp): the host variant's device image,
+  // the points' pinned results [n][2] and events [n][3], the last call's stats
+  struct Sweep {
+    DevBuf<uint8_t> rgb;
+    PinBuf<uint64_t> h_q;
+    std::vector<hipEvent_t> ev;
+    jxg_sweep_stats stats{};
+  } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
   struct Concat {
@@ -334,9 +346,21 @@ bool pipe_busy(const Ctx* c);
 uint32_t pipe_pending(const Ctx* c);
 void pipe_abort(Ctx* c);
 void pipe_drop_done(Ctx* c);
+// a sweep's frame (jxg_sweep.cpp): the point its lane encodes with and, with
+// quality != 0, where its reconstruction chain and metrics leave their results
+struct SweepReq {
+  jxg_params params;
+  int quality = 0;         // 0 none, 1 sse, 2 also ssim
+  uint64_t* h_q = nullptr;  // pinned [2]: sse, the SSIM sum's bits
+  hipEvent_t* ev = nullptr;  // [3]: chain start, chain end, metrics end
+};
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
-                       size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false);
+                       size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
+                       const SweepReq* rq = nullptr);
 jxg_status pipe_receive(Ctx* c, jxg_buffer* out);
+// a completed frame is worth taking now: its codestream's copy has landed, or
+// more than two are waiting
+bool pipe_done_ready(Ctx* c);
 jxg_status pipe_depth(const Ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t world,
                       uint32_t* depth);
 jxg_status batch_encode(Ctx* c, const uint8_t* const* frames, bool on_device, uint32_t n,
@@ -345,6 +369,13 @@ jxg_status shard_next_head(Ctx* c, uint32_t* dst, size_t* nwords);
 jxg_status shard_write_next(Ctx* c, const uint32_t* const* heads, const size_t* head_words,
                             uint32_t n, uint8_t* dst, size_t dst_size, size_t* total);
 jxg_status shard_write_flush(Ctx* c);
+
+// ---- jxg_sweep.cpp: one image over many settings ----
+jxg_status sweep_quality_enqueue(Ctx* lane, const SweepReq& rq, const uint8_t* d_orig, size_t so,
+                                 uint32_t w, uint32_t h);
+jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h, size_t stride,
+                 const jxg_sweep_point* points, uint32_t n, int quality, jxg_buffer* outs,
+                 jxg_quality* q, jxg_status* statuses);
 
 // ---- jxg_shard_host.cpp: sharded encode and the shard assemblers ----
 jxg_status shard_begin(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h, size_t stride,
@@ -366,6 +397,7 @@ jxg_status homogeneity_map(Ctx* c, const float* xyb, uint32_t xsize, uint32_t ys
                            float distance, uint32_t flags, float* r3, uint8_t* type);
 jxg_status synth_device(Ctx* c, uint8_t* d_out, uint32_t w, uint32_t h, size_t stride,
                         uint64_t seed);
+jxg_status quality_gauss(Ctx* c);  // the SSIM window's constants, once per context
 jxg_status compare_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_t* d_comp,
                           size_t sc, uint32_t w, uint32_t h, int want_ssim, jxg_quality* out);
 jxg_status compare_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* comp, size_t sc,
@@ -390,8 +422,19 @@ struct ReconMaps {
   const int16_t* ac;
   const int8_t* cmap;
 };
+// q: a sweep's chain on a lane (jxg_sweep.cpp) -- every pass writes planes and
+// the fused colour + squared-error kernel ends it (RGB8 stored to d_rgb only
+// with q->store); everything is enqueued on c's stream, nothing waited for
+struct ReconSse {
+  const uint8_t* orig;  // the original, RGB8 rows of orig_stride bytes
+  size_t orig_stride;
+  uint64_t* sse;        // device, zeroed on the stream before
+  bool store;
+};
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
-                              size_t stride);
+                              size_t stride, const ReconSse* q = nullptr);
+// the frame constants of a w x h frame encoded with parameters P
+ReconFrame recon_frame_of_encode(uint32_t w, uint32_t h, const jxg_params& P);
 // the last one-at-a-time encode's decoded image, into device / host memory
 jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_device);
 

@@ -330,6 +330,7 @@ struct MetricArgs {
 uint32_t ssim_partials(uint32_t w, uint32_t h);
 hipError_t set_gauss_table(const double* g, hipStream_t s);
 void launch_metrics(const MetricArgs& a, hipStream_t s);
+void launch_ssim(const MetricArgs& a, hipStream_t s);  // the SSIM kernels of launch_metrics alone
 // decode-side reconstruction (jxg_recon.hip): the decoded
 // image from the context's quantized coefficients.  Table blob (floats, built
 // in double by build_recon_tables): inverse-DCT matrices [k][x] for n = 4 ..
@@ -380,6 +381,11 @@ hipError_t launch_recon_gab(const ReconArgs& a, const float* src, float* dst, bo
 hipError_t launch_recon_epf(const ReconArgs& a, int pass, const float* src, float* dst, bool last,
                             hipStream_t s);
 hipError_t launch_recon_colour(const ReconArgs& a, const float* src, hipStream_t s);
+// the same conversion fused with the squared error against the original
+// (orig: RGB8 rows of orig_stride bytes; *sse pre-zeroed, the exact integer sum
+// launch_metrics gives for the stored image); store: RGB8 also written to a.rgb
+hipError_t launch_recon_colour_sse(const ReconArgs& a, const float* src, const uint8_t* orig,
+                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s);
 // the decoder's pass groups (jxg_decode.hip): one wave per
 // group walks its section of the codestream with the decode core and writes
 // the non-zero coefficients into `ac` (it zeroes the group's area first)

@@ -160,14 +160,18 @@ hipError_t set_gauss_table(const double* g, hipStream_t s) {
                                 hipMemcpyHostToDevice, s);
 }
 
-void launch_metrics(const MetricArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(sse_kernel, dim3(a.h < 2048 ? a.h : 2048), dim3(256), 0, s, a);
+void launch_ssim(const MetricArgs& a, hipStream_t s) {
   if (a.ssim && a.w >= 11 && a.h >= 11) {
     const uint32_t tx = (a.w - 10 + kSsimT - 1) / kSsimT, ty = (a.h - 10 + kSsimT - 1) / kSsimT;
     hipLaunchKernelGGL(ssim_kernel, dim3(tx, ty, 3), dim3(256), 0, s, a);
     hipLaunchKernelGGL(ssim_reduce_kernel, dim3(1), dim3(256), 0, s, a.partials, tx * ty * 3,
                        a.ssim);
   }
+}
+
+void launch_metrics(const MetricArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(sse_kernel, dim3(a.h < 2048 ? a.h : 2048), dim3(256), 0, s, a);
+  launch_ssim(a, s);
 }
 
 }  // namespace jxg

@@ -54,6 +54,8 @@ struct PipeFrame {
   uint32_t w = 0, h = 0, rank = 0, world = 1;
   size_t stride = 0;
   std::future<jxg_status> codes;  // valid while a helper builds the codes
+  bool sweep = false;  // a sweep's frame: its point (the lane's parameters) and quality request
+  SweepReq rq;
 };
 // frames launched together on one lane; the last of their codes launches the
 // batch's emission
@@ -61,6 +63,7 @@ struct PipeBatch {
   Ctx* owner = nullptr;
   uint32_t w = 0, h = 0, rank = 0, world = 1;
   bool shard = false;
+  jxg_params params{};  // of every frame of the batch (one distance / effort per launch)
   std::vector<PipeFrame*> frames;
   std::atomic<int> left{0};         // codes not yet built
   std::atomic<int> err{JXG_OK};     // a frame's codes or the emission failed
@@ -278,6 +281,10 @@ static jxg_status pipe_complete_oldest(Ctx* c) {
       p.evfree.push_back(e);
     }
     st = enc_finish_start(fr.lane, fr.J, false);
+    // a sweep's quality: the lane's reconstruction chain and metrics behind the
+    // codestream's copy, under the other lanes' chains; nothing waited for here
+    if (!st && fr.sweep && fr.rq.quality)
+      st = sweep_quality_enqueue(fr.lane, fr.rq, fr.J.d_rgb, fr.J.stride, fr.J.w, fr.J.h);
     if (!st && hipEventRecord(p.evfree.back(), fr.lane->stream) != hipSuccess) st = JXG_ERR_HIP;
     if (st) {
       (void)hipStreamSynchronize(fr.lane->stream);
@@ -302,14 +309,26 @@ static Ctx* pipe_lane(Ctx* c, uint32_t li) { return li == 0 ? c : c->lanes[li - 
 
 // submit one frame (world == 1) or this rank's shard of one frame
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
-                       size_t stride, uint32_t rank, uint32_t world, bool shard) {
+                       size_t stride, uint32_t rank, uint32_t world, bool shard,
+                       const SweepReq* rq) {
   c->rc.ok = false;  // the lanes' frames overwrite this context's buffers
   if (!c->pipe) c->pipe.reset(new (std::nothrow) Pipe());
   if (!c->pipe) return JXG_ERR_OOM;
   Pipe& p = *c->pipe;
   const int mode = shard ? 2 : 1;
   if (pipe_busy(c) && p.mode != mode) return JXG_ERR_INVALID_ARG;  // one kind at a time
-  const Frame f0 = make_frame(w, h, c->params.distance);
+  // the frame's parameters: the context's, or a sweep's point.  The slot the
+  // frame lands on is given them below, at every submit -- a slot is free by
+  // then, and a sweep (which also uses the context itself as lane 0) puts the
+  // context's own back when it ends
+  jxg_params prm = c->params;
+  if (rq) {
+    prm.distance = rq->params.distance;
+    prm.effort = rq->params.effort;
+    prm.proposals = rq->params.proposals;
+    prm.flags = rq->params.flags;
+  }
+  const Frame f0 = make_frame(w, h, prm.distance);
   uint32_t ngroups = f0.ngroups, ntiles = f0.tiles_x * f0.tiles_y;
   if (shard) {
     if (world < 1 || rank >= world || f0.ngroups < world || (world > 1 && f0.ngroups < 2))
@@ -318,7 +337,7 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
     // than one rank one HF preset per rank (ANS)
     const Plan P = make_plan(f0, rank, world);
     if (!P.x.send.empty() || !P.x.recv.empty() ||
-        (world > 1 && !(c->params.flags & JXG_FLAG_ANS)))
+        (world > 1 && !(prm.flags & JXG_FLAG_ANS)))
       return JXG_ERR_UNSUPPORTED;
     ngroups = P.ng();
     if (!P.tiles.empty()) ntiles = (uint32_t)P.tiles.size();
@@ -336,9 +355,15 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
     pipe_abort(c);
     return e;
   };
-  // an open batch of another size / plan, or a full one, goes out first
+  // an open batch of another size / plan / point, or a full one, goes out
+  // first (a batched launch carries one distance and one effort)
+  const auto same_point = [](const jxg_params& a, const jxg_params& b) {
+    return a.distance == b.distance && a.effort == b.effort && a.proposals == b.proposals &&
+           a.flags == b.flags;
+  };
   if (p.open && (p.open->w != w || p.open->h != h || p.open->rank != rank ||
-                 p.open->world != world || p.open->frames.size() >= shape.batch))
+                 p.open->world != world || !same_point(p.open->params, prm) ||
+                 p.open->frames.size() >= shape.batch))
     if ((st = pipe_launch_open(c))) return fail(st);
   if (!p.open) {
     // a free lane (no frame in flight or ready on it): complete the oldest
@@ -365,6 +390,7 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
     B.rank = rank;
     B.world = world;
     B.shard = shard;
+    B.params = prm;
   }
   PipeBatch& B = *p.open;
   std::unique_ptr<PipeFrame> fr(new (std::nothrow) PipeFrame());
@@ -380,6 +406,11 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
   fr->stride = stride;
   fr->rank = rank;
   fr->world = world;
+  if (rq) {
+    fr->sweep = true;
+    fr->rq = *rq;
+  }
+  S->params = prm;
   if (!on_device) {
     // the slot's previous frame has completed, so its staging is free
     const size_t bytes = stride * (h - 1) + (size_t)w * 3;
@@ -431,6 +462,12 @@ jxg_status pipe_receive(Ctx* c, jxg_buffer* out) {
   return JXG_OK;
 }
 
+bool pipe_done_ready(Ctx* c) {
+  const std::vector<PipeDone>& done = c->pipe->done;
+  return !done.empty() && (done.size() > 2 || !done.front().ev ||
+                           hipEventQuery(done.front().ev) == hipSuccess);
+}
+
 jxg_status pipe_depth(const Ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t world,
                       uint32_t* depth) {
   const Frame f = make_frame(w, h, c->params.distance);
@@ -457,10 +494,7 @@ jxg_status batch_encode(Ctx* c, const uint8_t* const* frames, bool on_device, ui
     st = pipe_submit(c, frames[i], on_device, w, h, stride);
     // take completed frames whose codestream copy has landed (or when more
     // than two are waiting), without waiting on the newest one's
-    while (!st && !c->pipe->done.empty() &&
-           (c->pipe->done.size() > 2 || !c->pipe->done.front().ev ||
-            hipEventQuery(c->pipe->done.front().ev) == hipSuccess))
-      st = pipe_receive(c, &outs[got++]);
+    while (!st && pipe_done_ready(c)) st = pipe_receive(c, &outs[got++]);
   }
   while (!st && got < n) st = pipe_receive(c, &outs[got++]);
   if (st) {  // the pipe is aborted by then; drop what it completed, and ours

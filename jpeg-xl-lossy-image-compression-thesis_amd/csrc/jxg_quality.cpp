@@ -19,18 +19,23 @@ static void gauss_window(double g[11]) {
   for (int k = 0; k < 11; k++) g[k] /= sum;
 }
 
+jxg_status quality_gauss(Ctx* c) {
+  if (c->q.gauss_ready) return JXG_OK;
+  std::lock_guard<std::mutex> lock(g_const_mu);
+  double g[11];
+  gauss_window(g);
+  JXG_HIP(set_gauss_table(g, c->stream));
+  JXG_HIP(hipGetLastError());
+  c->q.gauss_ready = true;
+  return JXG_OK;
+}
+
 jxg_status compare_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_t* d_comp,
                           size_t sc, uint32_t w, uint32_t h, int want_ssim, jxg_quality* out) {
   hipStream_t s = c->stream;
   Ctx::Quality& q = c->q;
-  if (!q.gauss_ready) {
-    std::lock_guard<std::mutex> lock(g_const_mu);
-    double g[11];
-    gauss_window(g);
-    JXG_HIP(set_gauss_table(g, s));
-    JXG_HIP(hipGetLastError());
-    q.gauss_ready = true;
-  }
+  const jxg_status gs = quality_gauss(c);
+  if (gs) return gs;
   const uint32_t np = ssim_partials(w, h);
   const bool ssim = want_ssim && np > 0;
   JXG_HIP(q.sse.ensure(1));

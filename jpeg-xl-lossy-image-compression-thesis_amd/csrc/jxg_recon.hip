@@ -24,7 +24,12 @@
 //   recon_gab_kernel     decoder Gaborish (3x3, edge-repeating).
 //   recon_epf_kernel     one EPF pass over a 64x16 tile with a 3 px halo in LDS.
 //   recon_colour_kernel  XYB -> sRGB8 alone (128 / 256 px varblocks, no filter).
+//   recon_colour_sse_kernel  the same conversion fused with the squared error
+//                        against the original (jxg_sweep_rgb8); stores RGB8
+//                        only for SSIM.
 // The last kernel of the chain writes RGB8 cropped to the image size.
+#include <algorithm>
+
 #include "jxg_kernels.h"
 
 namespace jxg {
@@ -55,20 +60,29 @@ __device__ __forceinline__ float rc_adjust(int q, float b1, float b3) {
   return (float)q - b3 / (float)q;
 }
 
-// XYB -> sRGB8 of one pixel (oracle/jxl_decode.py xyb_to_srgb8)
-__device__ __forceinline__ void rc_store_rgb(const ReconArgs& a, uint32_t gx, uint32_t gy, float X,
-                                             float Y, float B) {
+// XYB -> sRGB8 of one pixel (oracle/jxl_decode.py xyb_to_srgb8): the one
+// conversion of every kernel that ends a chain
+__device__ __forceinline__ void rc_xyb_to_rgb8(const ReconArgs& a, float X, float Y, float B,
+                                               uint8_t out[3]) {
   const float L = (Y + X) + a.cbias, M = (Y - X) + a.cbias, S = B + a.cbias;
   const float m0 = L * L * L - a.obias, m1 = M * M * M - a.obias, m2 = S * S * S - a.obias;
-  uint8_t* o = a.rgb + (size_t)gy * a.stride + (size_t)gx * 3;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
     float v = (m0 * a.cm[c * 3] + m1 * a.cm[c * 3 + 1]) + m2 * a.cm[c * 3 + 2];
     v = fminf(fmaxf(v, 0.0f), 1.0f);
     v = v <= 0.0031308f ? v * 12.92f : 1.055f * powf(v, 1.0f / 2.4f) - 0.055f;
     v = floorf(v * 255.0f + 0.5f);
-    o[c] = (uint8_t)fminf(fmaxf(v, 0.0f), 255.0f);
+    out[c] = (uint8_t)fminf(fmaxf(v, 0.0f), 255.0f);
   }
+}
+__device__ __forceinline__ void rc_store_rgb(const ReconArgs& a, uint32_t gx, uint32_t gy, float X,
+                                             float Y, float B) {
+  uint8_t v[3];
+  rc_xyb_to_rgb8(a, X, Y, B, v);
+  uint8_t* o = a.rgb + (size_t)gy * a.stride + (size_t)gx * 3;
+  o[0] = v[0];
+  o[1] = v[1];
+  o[2] = v[2];
 }
 
 template <bool kToRgb>
@@ -533,6 +547,59 @@ __global__ __launch_bounds__(256) void recon_colour_kernel(ReconArgs a, const fl
   if (x >= a.w || y >= a.h) return;
   const size_t plane = (size_t)a.xp * a.yp, g = (size_t)y * a.xp + x;
   rc_store_rgb(a, x, y, src[g], src[plane + g], src[2 * plane + g]);
+}
+
+// the fused last stage of a sweep's chain: XYB -> sRGB8 as
+// recon_colour_kernel, compared on the spot with the original's pixel -- the
+// exact integer sum of squared sample differences sse_kernel computes from the
+// stored image.  The RGB8 is stored (rows of a.stride bytes) only when SSIM
+// will read it (kStore).  Workgroup = 64 columns x 4 rows, striding down the
+// image; threads past the image add nothing and stay for the reduction; one
+// 64-bit atomic per workgroup.
+constexpr uint32_t kRcSseRows = 32;  // workgroups down the image, at most
+template <bool kStore>
+__global__ __launch_bounds__(256) void recon_colour_sse_kernel(ReconArgs a, const float* src,
+                                                               const uint8_t* orig, size_t so,
+                                                               unsigned long long* sse) {
+  __shared__ uint64_t sW[4];
+  const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const size_t plane = (size_t)a.xp * a.yp;
+  uint64_t acc = 0;
+  if (x < a.w)
+    for (uint32_t y = blockIdx.y * 4 + (threadIdx.x >> 6); y < a.h; y += gridDim.y * 4) {
+      const size_t g = (size_t)y * a.xp + x;
+      uint8_t v[3];
+      rc_xyb_to_rgb8(a, src[g], src[plane + g], src[2 * plane + g], v);
+      const uint8_t* p = orig + (size_t)y * so + (size_t)x * 3;
+      uint32_t d2 = 0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const int d = (int)p[c] - (int)v[c];
+        d2 += (uint32_t)(d * d);
+      }
+      acc += d2;
+      if (kStore) {
+        uint8_t* o = a.rgb + (size_t)y * a.stride + (size_t)x * 3;
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+      }
+    }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(sse, (unsigned long long)(sW[0] + sW[1] + sW[2] + sW[3]));
+}
+
+hipError_t launch_recon_colour_sse(const ReconArgs& a, const float* src, const uint8_t* orig,
+                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s) {
+  const dim3 grid((a.w + 63) / 64, std::min((a.h + 3) / 4, kRcSseRows));
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(sse);
+  if (store)
+    recon_colour_sse_kernel<true><<<grid, 256, 0, s>>>(a, src, orig, orig_stride, out);
+  else
+    recon_colour_sse_kernel<false><<<grid, 256, 0, s>>>(a, src, orig, orig_stride, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_recon_tiles(const ReconArgs& a, bool to_rgb, hipStream_t s) {

@@ -11,11 +11,9 @@
 
 namespace jxg {
 
-static ReconFrame recon_frame_of_encode(const Ctx* c) {
-  const jxg_params& P = c->params;
-  const Frame f = make_frame(c->rc.w, c->rc.h, P.distance);
-  return ReconFrame{c->rc.w, c->rc.h, f.G, f.qdc, lf_code(P.flags, P.distance),
-                    1.0f, 1.0f, P.effort >= 8};
+ReconFrame recon_frame_of_encode(uint32_t w, uint32_t h, const jxg_params& P) {
+  const Frame f = make_frame(w, h, P.distance);
+  return ReconFrame{w, h, f.G, f.qdc, lf_code(P.flags, P.distance), 1.0f, 1.0f, P.effort >= 8};
 }
 
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride) {
@@ -24,11 +22,28 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_
 }
 
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
-                              size_t stride) {
+                              size_t stride, const ReconSse* q) {
   hipStream_t s = c->stream;
   Ctx::Recon& rc = c->rc;
   Frame f = make_frame(R.w, R.h, 1.0f);
   set_frame_scales(f, R.global_scale, R.quant_dc);
+  if (q && rc.tab.p && rc.tab_g != f.G) {
+    // a sweep changes the global scale with every point: only the EPF's sigma
+    // table depends on it.  It goes through the slot's pinned staging, so the
+    // copy is asynchronous whatever the runtime does with pageable sources;
+    // the staging's previous copy (the slot's previous chain, long queued) has
+    // been read before it is rewritten
+    JXG_HIP(rc.h_sigma.ensure(256));
+    if (!rc.ev_sigma)
+      JXG_HIP(make_event(&rc.ev_sigma, hipEventDisableTiming));
+    else
+      JXG_HIP(hipEventSynchronize(rc.ev_sigma));
+    recon_sigma_table(f.G, rc.h_sigma.p);
+    JXG_HIP(hipMemcpyAsync(rc.tab.p + kRcTabSigma, rc.h_sigma.p, 256 * sizeof(float),
+                           hipMemcpyHostToDevice, s));
+    JXG_HIP(hipEventRecord(rc.ev_sigma, s));
+    rc.tab_g = f.G;
+  }
   if (!rc.tab.p || rc.tab_g != f.G) {
     const ReconTables T = build_recon_tables(f.G);
     JXG_HIP(rc.tab.ensure(T.tab.size()));
@@ -49,7 +64,8 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, u
   if (epf >= 3) passes[np++] = 0;
   if (epf >= 1) passes[np++] = 1;
   if (epf >= 2) passes[np++] = 2;
-  const bool to_rgb = np == 0 && !big;
+  // q: every pass writes planes and the fused colour + error kernel ends the chain
+  const bool to_rgb = np == 0 && !big && !q;
   if (!to_rgb) JXG_HIP(rc.pa.ensure(3 * plane));
   if (np || big) JXG_HIP(rc.pb.ensure(3 * plane));
   const uint32_t bigcap = ntiles / 2 + 1;
@@ -103,21 +119,29 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, u
   a.xmul = R.xmul;
   a.bmul = R.bmul;
   JXG_HIP(launch_recon_tiles(a, to_rgb, s));
-  if (big) {
+  if (big && q) {
+    // no host round trip for the count: a workgroup per list slot, those past
+    // the count return at once
+    JXG_HIP(launch_recon_big(a, bigcap, s));
+  } else if (big) {
     uint32_t nbig = 0;
     JXG_HIP(hipMemcpyAsync(&nbig, rc.big.p, sizeof(nbig), hipMemcpyDeviceToHost, s));
     JXG_HIP(hipStreamSynchronize(s));
     JXG_HIP(launch_recon_big(a, std::min(nbig, bigcap), s));
   }
-  if (!to_rgb && np == 0) JXG_HIP(launch_recon_colour(a, a.pa, s));
+  if (!to_rgb && np == 0 && !q) JXG_HIP(launch_recon_colour(a, a.pa, s));
   float *src = a.pa, *dst = a.pb;
   for (int i = 0; i < np; i++) {
-    const bool last = i + 1 == np;
+    const bool last = i + 1 == np && !q;
     if (passes[i] < 0)
       JXG_HIP(launch_recon_gab(a, src, dst, last, s));
     else
       JXG_HIP(launch_recon_epf(a, passes[i], src, dst, last, s));
     std::swap(src, dst);
+  }
+  if (q) {  // (enqueued only: the caller orders itself after the stream)
+    JXG_HIP(launch_recon_colour_sse(a, src, q->orig, q->orig_stride, q->sse, q->store, s));
+    return JXG_OK;
   }
   JXG_HIP(hipStreamSynchronize(s));
   return JXG_OK;
@@ -128,11 +152,13 @@ jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_dev
   if (on_device) {
     const jxg_status st = order_input(c, c);  // the caller's earlier use of rgb
     if (st) return st;
-    return reconstruct_device(c, recon_frame_of_encode(c), rgb, row_stride);
+    return reconstruct_device(c, recon_frame_of_encode(c->rc.w, c->rc.h, c->params), rgb,
+                              row_stride);
   }
   const size_t row = (size_t)c->rc.w * 3;
   JXG_HIP(c->rc.rgb.ensure(row * c->rc.h));
-  const jxg_status st = reconstruct_device(c, recon_frame_of_encode(c), c->rc.rgb.p, row);
+  const jxg_status st =
+      reconstruct_device(c, recon_frame_of_encode(c->rc.w, c->rc.h, c->params), c->rc.rgb.p, row);
   if (st) return st;
   JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc.rgb.p, row, row, c->rc.h,
                            hipMemcpyDeviceToHost, c->stream));

@@ -1,0 +1,171 @@
+// jxg_sweep.cpp -- one image over many settings in one call (jxg_sweep_rgb8;
+// DESIGN.md §3.14).  The image is uploaded once; every point is a frame of
+// the streaming pipeline (jxg_pipe.cpp) that carries its parameters, so the
+// points' transform kernels, rANS chains, host-side codes and -- with quality
+// -- their reconstruction chains and metrics overlap over the context's lanes.
+// A frame's quality is enqueued on its lane's stream right behind its
+// codestream's copy (pipe_complete_oldest): the chain of jxg_reconstruct.cpp on
+// the lane's own coefficients, ending in the fused colour + squared-error
+// kernel, then the SSIM kernels on the stored image when asked for; the two
+// result words land in pinned memory before the frame's completion event.
+#include <cmath>
+#include <cstring>
+
+#include "jxg_ctx.h"
+
+namespace jxg {
+
+jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_orig, size_t so,
+                                 uint32_t w, uint32_t h) {
+  hipStream_t s = S->stream;
+  Ctx::Quality& q = S->q;
+  const uint32_t np = ssim_partials(w, h);
+  const bool ssim = rq.quality == 2 && np > 0;
+  const size_t row = (size_t)w * 3;
+  JXG_HIP(q.sse.ensure(1));
+  JXG_HIP(q.ssim.ensure(1));
+  if (ssim) {
+    const jxg_status st = quality_gauss(S);
+    if (st) return st;
+    JXG_HIP(q.part.ensure(np));
+    JXG_HIP(S->rc.rgb.ensure(row * h));
+  }
+  JXG_HIP(hipMemsetAsync(q.sse.p, 0, sizeof(uint64_t), s));
+  JXG_HIP(hipEventRecord(rq.ev[0], s));
+  const ReconSse e{d_orig, so, q.sse.p, ssim};
+  const jxg_status st = reconstruct_device(
+      S, recon_frame_of_encode(w, h, S->params),
+      ReconMaps{S->acs.p, S->qf.p, S->dc.p, S->ac.p, S->cmap.p}, ssim ? S->rc.rgb.p : nullptr, row,
+      &e);
+  if (st) return st;
+  JXG_HIP(hipEventRecord(rq.ev[1], s));
+  rq.h_q[1] = 0;
+  if (ssim) {
+    const MetricArgs a{d_orig, S->rc.rgb.p, so, row, w, h, q.sse.p, q.part.p, q.ssim.p};
+    launch_ssim(a, s);
+    JXG_HIP(hipGetLastError());
+    JXG_HIP(hipMemcpyAsync(rq.h_q + 1, q.ssim.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  JXG_HIP(hipEventRecord(rq.ev[2], s));
+  return JXG_OK;
+}
+
+static bool point_ok(const jxg_sweep_point& p) {  // as ctx_create checks its parameters
+  if (!(p.distance > 0.0f) || p.distance > 25.0f) return false;
+  if (p.effort < 1 || p.effort > 10) return false;
+  if (p.proposals & ~3u) return false;
+  return !(p.flags & JXG_FLAG_KEEP_MAPS);  // (maps are a one-at-a-time context's)
+}
+
+jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h, size_t stride,
+                 const jxg_sweep_point* points, uint32_t n, int quality, jxg_buffer* outs,
+                 jxg_quality* q, jxg_status* statuses) {
+  const Clock::time_point t0 = Clock::now();
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;  // (nothing touched)
+  std::vector<jxg_status> st(n, JXG_OK);
+  std::vector<uint32_t> valid;
+  jxg_status first = JXG_OK;
+  for (uint32_t i = 0; i < n; i++) {
+    outs[i] = jxg_buffer{nullptr, 0};
+    if (q) q[i] = jxg_quality{};
+    if (point_ok(points[i])) {
+      valid.push_back(i);
+    } else {
+      st[i] = JXG_ERR_INVALID_ARG;
+      if (!first) first = st[i];
+    }
+  }
+  const uint32_t nv = (uint32_t)valid.size();
+  Ctx::Sweep& sw = c->sw;
+  sw.stats = jxg_sweep_stats{};
+  // the context is lane 0 and encodes with its frames' points: its own
+  // parameters are put back however the call ends
+  const jxg_params saved = c->params;
+  struct Restore {
+    Ctx* c;
+    jxg_params p;
+    ~Restore() { c->params = p; }
+  } restore{c, saved};
+  // a failure of the call: the pipe is aborted by then; drop what it completed, and ours
+  auto fail = [&](jxg_status e) {
+    pipe_drop_done(c);
+    for (uint32_t i = 0; i < n; i++) {
+      out_release(outs[i].data);
+      outs[i] = jxg_buffer{nullptr, 0};
+      if (q) q[i] = jxg_quality{};
+      if (statuses) statuses[i] = e;
+    }
+    sw.stats.ms_call = ms_since(t0);
+    return e;
+  };
+  if (nv) {
+    const uint8_t* d = src;
+    if (!on_device) {  // the one upload every point reads
+      const Clock::time_point tu = Clock::now();
+      const size_t bytes = stride * (h - 1) + (size_t)w * 3;
+      if (sw.rgb.ensure(bytes) != hipSuccess) return fail(JXG_ERR_OOM);
+      if (hipMemcpyAsync(sw.rgb.p, src, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+          hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(JXG_ERR_HIP);
+      d = sw.rgb.p;
+      sw.stats.ms_upload = ms_since(tu);
+    }
+    if (quality) {
+      if (sw.h_q.ensure((size_t)nv * 2) != hipSuccess) return fail(JXG_ERR_OOM);
+      while (sw.ev.size() < (size_t)nv * 3) {
+        hipEvent_t e = nullptr;
+        if (make_event(&e, 0) != hipSuccess) return fail(JXG_ERR_HIP);
+        sw.ev.push_back(e);
+      }
+    }
+    uint32_t got = 0;
+    jxg_status e = JXG_OK;
+    // point valid[got]'s codestream (its completion event covers the quality
+    // results) and its share of the timings
+    auto take = [&]() {
+      const uint32_t k = got++, i = valid[k];
+      if ((e = pipe_receive(c, &outs[i]))) return;
+      sw.stats.ms_encode += c->stats.ms_total;
+      if (!quality) return;
+      const uint64_t sse = sw.h_q.p[2 * k];
+      double ssum;
+      std::memcpy(&ssum, &sw.h_q.p[2 * k + 1], sizeof(ssum));
+      const bool ssim = quality == 2 && ssim_partials(w, h) > 0;
+      jxg_quality& o = q[i];  // (the expressions of compare_device)
+      o.sse = sse;
+      o.samples = (uint64_t)w * h * 3;
+      o.mse = (double)sse / (double)o.samples;
+      o.psnr = 10.0 * std::log10((255.0 * 255.0) / o.mse);
+      o.ssim = ssim ? ssum / (3.0 * (double)(w - 10) * (double)(h - 10)) : NAN;
+      sw.stats.ms_recon += elapsed(sw.ev[3 * k], sw.ev[3 * k + 1]);
+      sw.stats.ms_metrics += elapsed(sw.ev[3 * k + 1], sw.ev[3 * k + 2]);
+    };
+    for (uint32_t k = 0; k < nv && !e; k++) {
+      SweepReq rq;
+      rq.params = saved;
+      rq.params.distance = points[valid[k]].distance;
+      rq.params.effort = points[valid[k]].effort;
+      rq.params.proposals = points[valid[k]].proposals;
+      rq.params.flags = points[valid[k]].flags;
+      rq.quality = quality;
+      if (quality) {
+        rq.h_q = sw.h_q.p + 2 * (size_t)k;
+        rq.ev = sw.ev.data() + 3 * (size_t)k;
+      }
+      e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
+      // completed points whose copies have landed (or when more than two wait)
+      while (!e && pipe_done_ready(c)) take();
+    }
+    while (!e && got < nv) take();
+    if (e) return fail(e);
+  }
+  const Frame f = make_frame(w, h, 1.0f);
+  sw.stats.points = nv;
+  sw.stats.lanes = pipe_shape(f.ngroups, f.tiles_x * f.tiles_y, c->lane_cap, hw_queues()).lanes;
+  if (statuses) std::copy(st.begin(), st.end(), statuses);
+  sw.stats.ms_call = ms_since(t0);
+  return first;
+}
+
+}  // namespace jxg

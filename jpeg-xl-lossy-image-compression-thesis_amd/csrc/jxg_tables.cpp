@@ -453,16 +453,21 @@ ReconTables build_recon_tables(uint32_t global_scale) {
       for (int p = 0; p < rows * cols; p++) iw[p] = (float)(1.0 / w[order[p]]);
     }
   }
-  // EPF: raw quant field - 1 -> inverse sigma; blocks below the minimum
-  // (not filtered) are marked with +1
+  recon_sigma_table(global_scale, &T.tab[kRcTabSigma]);
+  return T;
+}
+
+// EPF: raw quant field - 1 -> inverse sigma; blocks below the minimum
+// (not filtered) are marked with +1.  The blob's only part that depends on
+// the global scale.
+void recon_sigma_table(uint32_t global_scale, float* out) {
   for (int q = 0; q < 256; q++) {
     const double scale = (double)global_scale / 65536.0;
     double sigma = 0.46 / (scale * (double)(q + 1) * -1.1715728752538099) * ((double)kEpfSharpness / 7.0);
     if (sigma > -1e-4) sigma = -1e-4;
     const double inv = 1.0 / sigma;
-    T.tab[kRcTabSigma + q] = inv < -3.90625 ? 1.0f : (float)inv;
+    out[q] = inv < -3.90625 ? 1.0f : (float)inv;
   }
-  return T;
 }
 
 }  // namespace jxg

@@ -39,6 +39,8 @@ struct ReconTables {
   std::vector<uint16_t> pos;
 };
 ReconTables build_recon_tables(uint32_t global_scale);
+// the blob's kRcTabSigma part [256] alone (the rest does not depend on the scale)
+void recon_sigma_table(uint32_t global_scale, float* out);
 
 // (DequantMatrices, the big kinds' binary16 parameters: jxg_dequant.h)
 

@@ -95,6 +95,17 @@ class _Quality(ctypes.Structure):
                 ("psnr", ctypes.c_double), ("ssim", ctypes.c_double)]
 
 
+class _SweepPoint(ctypes.Structure):
+    _fields_ = [("distance", ctypes.c_float), ("effort", ctypes.c_int),
+                ("proposals", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _SweepStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("points", "lanes")] + [
+        (k, ctypes.c_float) for k in ("ms_call", "ms_upload", "ms_encode", "ms_recon",
+                                      "ms_metrics")]
+
+
 # every symbol declared in include/jxg.h
 EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_encode_rgb8_device", "jxg_encode_batch_rgb8", "jxg_get_stats",
@@ -111,6 +122,7 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_decode_info", "jxg_decode_rgb8", "jxg_decode_rgb8_device", "jxg_decode_maps",
            "jxg_decode_timings", "jxg_decode_batch_rgb8", "jxg_decode_batch_rgb8_device",
            "jxg_set_decode_batch_bytes", "jxg_decode_batch_timings",
+           "jxg_sweep_rgb8", "jxg_sweep_rgb8_device", "jxg_sweep_timings",
 )
 
 _lib = None
@@ -197,6 +209,12 @@ def load():
     lib.jxg_decode_batch_rgb8_device.argtypes = lib.jxg_decode_batch_rgb8.argtypes
     lib.jxg_set_decode_batch_bytes.argtypes = [vp, sz]
     lib.jxg_decode_batch_timings.argtypes = [vp, ctypes.POINTER(_DecodeBatchStats)]
+    lib.jxg_sweep_rgb8.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, sz,
+                                   ctypes.POINTER(_SweepPoint), ctypes.c_uint32, ctypes.c_int,
+                                   ctypes.POINTER(_Buffer), ctypes.POINTER(_Quality),
+                                   ctypes.POINTER(ctypes.c_int)]
+    lib.jxg_sweep_rgb8_device.argtypes = lib.jxg_sweep_rgb8.argtypes
+    lib.jxg_sweep_timings.argtypes = [vp, ctypes.POINTER(_SweepStats)]
     _lib = lib
     return lib
 
@@ -440,6 +458,89 @@ class Encoder:
                                              row_stride or width * 3, ctypes.byref(buf)))
         self._last_wh = (width, height)
         return self._take(buf) if copy else Codestream(buf)
+
+    # ---- sweep: one image over many settings (jxg_sweep_rgb8) ----
+    _QUALITY = {None: 0, "none": 0, "psnr": 1, "ssim": 2, 0: 0, 1: 1, 2: 2}
+
+    @staticmethod
+    def _sweep_points(points):
+        pts = []
+        for p in points:
+            if isinstance(p, dict):
+                pts.append(_SweepPoint(p["distance"], p["effort"], p.get("proposals", 0),
+                                       p.get("flags", 0)))
+            else:
+                p = tuple(p)
+                pts.append(_SweepPoint(p[0], p[1], *(tuple(p[2:4]) + (0, 0))[:2]))
+        return pts
+
+    def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict):
+        if quality not in self._QUALITY:
+            raise ValueError("quality: 'ssim', 'psnr' or None")
+        level = self._QUALITY[quality]
+        pts = self._sweep_points(points)
+        n = len(pts)
+        if n == 0:
+            return []
+        c_pts = (_SweepPoint * n)(*pts)
+        outs = (_Buffer * n)()
+        qs = (_Quality * n)() if level else None
+        st = (ctypes.c_int * n)()
+        ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
+        st = [int(v) for v in st]
+        if ret != 0 and (strict or self._batch_call_failed(ret, st)):
+            for i in range(n):
+                load().jxg_buffer_free(ctypes.byref(outs[i]))
+            _check(ret)
+        res = []
+        for i in range(n):
+            if st[i] != 0:
+                res.append((None, st[i]))
+                continue
+            q = None
+            if level:
+                q = {k: getattr(qs[i], k) for k in ("sse", "samples", "mse", "psnr", "ssim")}
+            res.append((self._take(outs[i]), q))
+        return res
+
+    def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True) -> list:
+        """One host (H, W, 3) uint8 image encoded at every point of ``points``
+        in one call (jxg_sweep_rgb8): the image is uploaded once and the points
+        run through the streaming pipeline's lanes of this context, whose own
+        distance / effort / proposals / flags play no part.  A point is a dict
+        with ``distance``, ``effort`` and optionally ``proposals`` / ``flags``
+        (the keywords of :class:`Encoder`), or a tuple in that order.
+        ``quality``: ``"ssim"`` (sse, mse, psnr and ssim of each point's
+        decoded image against ``rgb``), ``"psnr"`` (the decoded image is never
+        written; ssim NaN) or ``None``.  Returns ``[(bytes, dict | None), ...]``
+        in point order, each equal to a fresh ``Encoder(**point)``'s
+        ``encode`` / ``reconstruct_device`` / ``compare_device``.  Raises
+        JxgError on the first refused point; with ``strict=False`` a refused
+        point comes back as ``(None, status)``.  Afterwards :meth:`reconstruct`
+        raises until the next :meth:`encode`."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("expected (H, W, 3) uint8")
+        h, w = rgb.shape[:2]
+        return self._sweep_call(load().jxg_sweep_rgb8, rgb.ctypes.data, w, h, w * 3, points,
+                                quality, strict)
+
+    def sweep_device(self, ptr: int, width: int, height: int, points, quality="ssim",
+                     strict: bool = True, row_stride: int | None = None) -> list:
+        """:meth:`sweep` of a device-resident RGB8 image (rows of ``row_stride``
+        bytes, default 3 * width), which must stay unchanged until the call
+        returns (jxg_sweep_rgb8_device)."""
+        return self._sweep_call(load().jxg_sweep_rgb8_device, ctypes.c_void_p(ptr), width, height,
+                                row_stride or width * 3, points, quality, strict)
+
+    def sweep_timings(self) -> dict:
+        """The last :meth:`sweep` (jxg_sweep_timings): points encoded, lanes,
+        the call's host wall time, the upload, and device time by events summed
+        over the points -- encode, reconstruction chain, metrics."""
+        s = _SweepStats()
+        _check(load().jxg_sweep_timings(self._ctx, ctypes.byref(s)))
+        return {k: (int if t is ctypes.c_uint32 else float)(getattr(s, k))
+                for k, t in _SweepStats._fields_}
 
     # streaming encode (jxg_submit_rgb8[_device] / jxg_receive): a software
     # pipeline inside the library, driven by this thread

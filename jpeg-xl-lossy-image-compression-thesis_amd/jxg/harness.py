@@ -20,6 +20,8 @@ Mirrors pscoro/JPEG-XL-Lossy-Image-Compression-Thesis benchmark-jpegxl:
   SSIM on the GPU; MS-SSIM is 0.0 as in the reference (benchmark.rs:933);
   Butteraugli and SSIMULACRA2 need libjxl's tools (Docker) and are 0.0 here.
 * ``file_size_ratio`` -- metrics.rs:15-26.
+* ``sweep_and_compare`` -- the per-image loop of benchmark.rs:637-677 (every
+  distance x effort: encode, decode, compare) as one Encoder.sweep call.
 """
 import csv
 import os
@@ -27,7 +29,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from . import rust_f32, rust_f64
+from . import comp_image_name, rust_f32, rust_f64
 
 RESULT_HEADER = [
     "Original Image Name", "Compressed Image Name", "Distance", "Effort",
@@ -246,3 +248,31 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
     raw = w * h * 3
     return data, _record(orig_name, comp_name, distance, effort, orig_file_size, len(data), raw, q,
                          ssim, result_file)
+
+
+def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
+                      result_file: str | None = None, ssim: bool = True):
+    """The harness's per-image loop (benchmark.rs:637-677) in one call: the
+    image is encoded at every point (dicts with ``distance`` / ``effort`` and
+    optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
+    the points overlapped over the pipeline's lanes, each point's decoded
+    quality computed on its lane -- and one record per point is built, named
+    ``comp_image_name(stem of orig_name, distance, effort)`` (benchmark.rs:
+    644-650).  ``encoder``'s own parameters play no part.  Returns
+    (codestreams, records); the records, and the CSV rows in point order, equal
+    per-point :func:`encode_and_compare` on an encoder of those parameters."""
+    o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
+    if o.ndim != 3 or o.shape[2] != 3:
+        raise ValueError("orig_rgb must be (H, W, 3) uint8")
+    h, w = o.shape[:2]
+    points = list(points)
+    res = encoder.sweep(o, points, quality="ssim" if ssim else "psnr")
+    stem = os.path.splitext(orig_name)[0]
+    raw = w * h * 3
+    datas, records = [], []
+    for p, (data, q) in zip(points, res):
+        d, e = (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
+        datas.append(data)
+        records.append(_record(orig_name, comp_image_name(stem, d, e), d, e, orig_file_size,
+                               len(data), raw, q, ssim, result_file))
+    return datas, records

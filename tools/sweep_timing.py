@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""Times of jxg_sweep_rgb8 on the reference harness's grid
+-- 10 distances x 5 efforts (benchmark.rs:637-642), cjxl's default flags --
+against the loop it replaces on the same build: one cached context per point,
+each doing encode + reconstruct_device + compare_device.
+
+    python tools/sweep_timing.py [--reps 5] [--sizes 8k,768] [--queues N] [--cli]
+
+Per frame size (the 8K synthetic frame and a 768 x 512 one), input (host /
+device) and quality level (0 none, 1 sse/psnr, 2 also ssim): warm contexts,
+`--reps` repetitions with sweep and loop alternating, median and min..max of
+the host wall time, the jxg_sweep_timings split of the median sweep, and the
+device memory one sweeping context holds next to the 50 cached ones.  --queues
+sets GPU_MAX_HW_QUEUES before HIP starts (the pipeline has queues - 1 lanes).
+--cli: `jxg_cjxl IN OUTDIR --sweep=LIST` of the grid against 50 plain jxg_cjxl
+processes.  Prints one JSON line per measurement; the outputs of sweep and loop
+are compared before anything is timed."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "jpeg-xl-lossy-image-compression-thesis_amd"))
+
+DISTANCES = [0.5, 1.0, 1.5, 3.0, 4.0, 6.0, 8.0, 10.0, 12.0, 14.0]
+EFFORTS = [5, 6, 7, 8, 9]
+SIZES = {"8k": (7680, 4320, 2), "768": (768, 512, 5)}
+QUALITY = {0: None, 1: "psnr", 2: "ssim"}
+
+
+def spread(v):
+    return {"median": round(statistics.median(v), 3), "min": round(min(v), 3),
+            "max": round(max(v), 3)}
+
+
+def used_mib(torch):
+    free, total = torch.cuda.mem_get_info()
+    return (total - free) / 2.0 ** 20
+
+
+def library(args):
+    import torch
+
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8_device
+
+    points = [dict(distance=d, effort=e, proposals=0, flags=jxg.FLAGS_CJXL_DEFAULTS)
+              for d in DISTANCES for e in EFFORTS]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        d_img = synth_rgb8_device(w, h, SEED_BASE + seed, 0)
+        d_rec = torch.empty_like(d_img)
+        torch.cuda.synchronize()
+        img = d_img.cpu().numpy()
+        base = used_mib(torch)
+        sweeper = jxg.Encoder()
+        sweeper.sweep_device(d_img.data_ptr(), w, h, points, quality="ssim")  # warm, all buffers
+        sweeper.sweep(img, points[:1], quality=None)                          # (the upload buffer)
+        mem_sweep = used_mib(torch) - base
+        cached = [jxg.Encoder(**p) for p in points]
+
+        def loop(host, level):
+            out = []
+            for enc in cached:
+                data = enc.encode(img) if host else enc.encode_device(d_img.data_ptr(), w, h)
+                q = None
+                if level:
+                    enc.reconstruct_device(d_rec.data_ptr())
+                    q = enc.compare_device(d_img.data_ptr(), d_rec.data_ptr(), w, h,
+                                           ssim=level == 2)
+                out.append((data, q))
+            return out
+
+        def sweep(host, level):
+            if host:
+                return sweeper.sweep(img, points, quality=QUALITY[level])
+            return sweeper.sweep_device(d_img.data_ptr(), w, h, points, quality=QUALITY[level])
+
+        want = loop(False, 2)  # warm every cached context, and the reference results
+        mem_loop = used_mib(torch) - base - mem_sweep
+        got = sweep(False, 2)
+        assert [g[0] for g in got] == [r[0] for r in want], "sweep bytes differ from the loop's"
+        assert all(repr(g[1]) == repr(r[1]) for g, r in zip(got, want)), "quality differs"
+        print(json.dumps({"frame": "%s %dx%d synth_rgb8" % (name, w, h), "points": len(points),
+                          "queues": os.environ.get("GPU_MAX_HW_QUEUES", "default"),
+                          "lanes": sweeper.sweep_timings()["lanes"],
+                          "bytes_total": sum(len(g[0]) for g in got),
+                          "mib_one_sweeping_context": round(mem_sweep, 1),
+                          "mib_50_cached_contexts": round(mem_loop, 1)}), flush=True)
+        for host in (False, True):
+            for level in (0, 1, 2):
+                t_sweep, t_loop, split = [], [], []
+                for rep in range(args.reps + 1):
+                    t0 = time.perf_counter()
+                    sweep(host, level)
+                    t1 = time.perf_counter()
+                    tm = sweeper.sweep_timings()
+                    t2 = time.perf_counter()
+                    loop(host, level)
+                    t3 = time.perf_counter()
+                    if rep:
+                        t_sweep.append((t1 - t0) * 1e3)
+                        t_loop.append((t3 - t2) * 1e3)
+                        split.append(tm)
+                mid = sorted(range(len(t_sweep)), key=lambda i: t_sweep[i])[len(t_sweep) // 2]
+                res = {"frame": name, "input": "host" if host else "device", "quality": level,
+                       "reps": args.reps, "ms_sweep_wall": spread(t_sweep),
+                       "ms_loop_wall": spread(t_loop),
+                       "loop_over_sweep": round(statistics.median(t_loop) /
+                                                statistics.median(t_sweep), 2),
+                       "ms_sweep_per_point": round(statistics.median(t_sweep) / len(points), 3),
+                       "ms_loop_per_point": round(statistics.median(t_loop) / len(points), 3),
+                       "sweep_timings_of_median": {k: round(v, 3) if isinstance(v, float) else v
+                                                   for k, v in split[mid].items()}}
+                print(json.dumps(res), flush=True)
+        for enc in cached:
+            enc.close()
+        sweeper.close()
+        del cached, d_img, d_rec
+
+
+def cli(args):
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8
+
+    grid = [(d, e) for d in DISTANCES for e in EFFORTS]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        with tempfile.TemporaryDirectory() as tmp:
+            src = os.path.join(tmp, "frame.ppm")
+            with open(src, "wb") as f:
+                f.write(b"P6\n%d %d\n255\n" % (w, h) + synth_rgb8(w, h, SEED_BASE + seed).tobytes())
+            lst = os.path.join(tmp, "grid.txt")
+            with open(lst, "w") as f:
+                f.writelines("%s %d\n" % (jxg.rust_f64(d), e) for d, e in grid)
+            t_sweep, t_runs = [], []
+            for rep in range(args.cli_reps):
+                t0 = time.perf_counter()
+                subprocess.run([jxg.CLI_PATH, src, os.path.join(tmp, "s%d" % rep),
+                                "--sweep=" + lst], check=True, capture_output=True)
+                t1 = time.perf_counter()
+                for d, e in grid:
+                    ok, msg = jxg.execute_cjxl(src, os.path.join(tmp, "p%d" % rep,
+                                                                 jxg.comp_image_name("frame", d, e)),
+                                               d, e)
+                    assert ok, msg
+                t2 = time.perf_counter()
+                t_sweep.append((t1 - t0) * 1e3)
+                t_runs.append((t2 - t1) * 1e3)
+                for d, e in grid:
+                    n = jxg.comp_image_name("frame", d, e)
+                    a = open(os.path.join(tmp, "s%d" % rep, n), "rb").read()
+                    assert a == open(os.path.join(tmp, "p%d" % rep, n), "rb").read(), n
+            print(json.dumps({"frame": name, "cli": True, "points": len(grid),
+                              "reps": args.cli_reps, "ms_sweep_process": spread(t_sweep),
+                              "ms_50_processes": spread(t_runs)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cli-reps", type=int, default=2)
+    ap.add_argument("--sizes", default="8k,768")
+    ap.add_argument("--queues", type=int, default=0)
+    ap.add_argument("--cli", action="store_true")
+    args = ap.parse_args()
+    if not 0 <= args.queues <= 32:
+        ap.error("--queues: at most 32 hardware queues (0: leave the environment's)")
+    if args.queues:
+        os.environ["GPU_MAX_HW_QUEUES"] = str(args.queues)
+    if args.cli:
+        return cli(args)
+    import torch  # noqa: F401  (one HIP runtime in the process: DESIGN.md §6)
+
+    library(args)
+
+
+if __name__ == "__main__":
+    main()
