@@ -16,9 +16,10 @@
  * allocated by the library and released with jxg_buffer_free.
  *
  * Device inputs (jxg_encode_rgb8_device, jxg_submit_rgb8_device,
- * jxg_shard_submit_device, jxg_shard_begin, jxg_compare_rgb8_device) are
- * read on the library's own HIP streams.  Either the caller's writes to them
- * are complete before the call (e.g. hipStreamSynchronize of the producing
+ * jxg_shard_submit_device, jxg_shard_begin, jxg_compare_rgb8_device,
+ * jxg_msssim_rgb8_device) are read on the library's own HIP streams.  Either
+ * the caller's writes to them are complete before the call (e.g.
+ * hipStreamSynchronize of the producing
  * stream), or the caller names its producing stream with
  * jxg_set_input_stream: every later device-input call then orders its reads
  * after all work submitted to that stream so far (an event recorded on it,
@@ -26,8 +27,8 @@
  *
  * A context with streamed frames pending (jxg_pending > 0) serves them as a
  * pipeline lane: the one-at-a-time, batch, sharded-begin/end, homogeneity,
- * compare, reconstruct and decode entry points return JXG_ERR_INVALID_ARG until
- * they are received.
+ * compare, MS-SSIM (jxg_msssim_rgb8, jxg_set_sweep_msssim), reconstruct and
+ * decode entry points return JXG_ERR_INVALID_ARG until they are received.
  */
 #ifndef JXG_H_
 #define JXG_H_
@@ -335,6 +336,32 @@ jxg_status jxg_compare_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig
                                    const void* d_comp, size_t comp_stride, uint32_t xsize,
                                    uint32_t ysize, int want_ssim, jxg_quality* out);
 
+/* ---- MS-SSIM (Wang, Simoncelli, Bovik 2003) on the GPU ----
+ * The harness's column 13, which the reference leaves at 0.0
+ * (benchmark.rs:932-933).  Five scales; scale 0 is the two RGB8 images, each
+ * channel on its own, and scale j + 1 is the 2 x 2 box mean of scale j (an odd
+ * last row or column dropped), so scale j has (xsize >> j) x (ysize >> j)
+ * samples, held as exact f32 planes.  At every scale the window, constants and
+ * expressions are jxg_quality.ssim's, plus cs = (2 cov + C2) / (var_a + var_b +
+ * C2); cs[j] / ssim[j] are the means over all windows and the three channels.
+ * ms_ssim = prod_{j<4} max(cs[j], 0)^W[j] * max(ssim[4], 0)^W[4] with W =
+ * {0.0448, 0.2856, 0.3001, 0.2363, 0.1333}: 0.0 when a mean is not positive.
+ * Deterministic: two calls on the same images give the same bits.
+ * JXG_ERR_INVALID_ARG as jxg_compare_rgb8: a null argument, a stride under
+ * 3 * xsize, or streamed frames pending.  The pyramid planes (about 8 bytes a
+ * pixel) are allocated by the first call and released by jxg_destroy. */
+typedef struct {
+  double ms_ssim;   /* NaN when min(xsize, ysize) < 176 (then cs / ssim are NaN too) */
+  double cs[5];     /* mean contrast-structure term per scale */
+  double ssim[5];   /* mean SSIM per scale; ssim[0] is bit-equal to jxg_quality.ssim */
+} jxg_msssim;
+jxg_status jxg_msssim_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
+                           const uint8_t* comp, size_t comp_stride, uint32_t xsize,
+                           uint32_t ysize, jxg_msssim* out);
+jxg_status jxg_msssim_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
+                                  const void* d_comp, size_t comp_stride, uint32_t xsize,
+                                  uint32_t ysize, jxg_msssim* out);
+
 /* ---- decode-side reconstruction: decoded pixels without a decoder ----
  * The decoded image of the frame this context encoded last with
  * jxg_encode_rgb8 / jxg_encode_rgb8_device: what a conforming decoder
@@ -523,9 +550,24 @@ typedef struct {
   float ms_upload;   /* host variant: the image's upload (host wall clock) */
   float ms_encode;   /* device time by events, summed over points: frame start -> emission */
   float ms_recon;    /*   reconstruction chain incl. the fused colour + error kernel */
-  float ms_metrics;  /*   SSIM kernels and the results' download */
+  float ms_metrics;  /*   SSIM (or MS-SSIM) kernels and the results' download */
 } jxg_sweep_stats;
 jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats);
+/* MS-SSIM in a sweep.  With the switch on (default 0; JXG_ERR_INVALID_ARG
+ * while streamed frames are pending) a quality-2 sweep also runs the MS-SSIM
+ * kernels for every point on its lane, where the SSIM kernels would run, on
+ * the decoded image that quality 2 stores (scale 0's SSIM sum is the SSIM
+ * kernels', bit for bit, and fills q[i].ssim); the original's pyramid is built
+ * once per sweep.
+ * Codestreams and q[] are unchanged, ms_metrics includes the added kernels,
+ * and sweeps of other quality levels, or with the switch off, are untouched.
+ * jxg_sweep_msssim copies the last sweep's results out in point order, each
+ * bit-equal to jxg_msssim_rgb8_device(original, jxg_reconstruct_rgb8_device)
+ * after a one-at-a-time encode with that point (NaN fields under 176 pixels,
+ * a refused point zero-filled); JXG_ERR_INVALID_ARG when the last sweep did
+ * not compute them or n is not that sweep's. */
+jxg_status jxg_set_sweep_msssim(jxg_ctx* ctx, int on);
+jxg_status jxg_sweep_msssim(jxg_ctx* ctx, jxg_msssim* out, uint32_t n);
 
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result

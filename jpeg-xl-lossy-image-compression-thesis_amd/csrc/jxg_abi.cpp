@@ -310,6 +310,31 @@ jxg_status jxg_compare_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_strid
             : compare_host(c, orig, orig_stride, comp, comp_stride, xsize, ysize, want_ssim, out);
 }
 
+jxg_status jxg_msssim_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
+                                  const void* d_comp, size_t comp_stride, uint32_t xsize,
+                                  uint32_t ysize, jxg_msssim* out) {
+  if (!ctx || !d_orig || !d_comp || !out || xsize == 0 || ysize == 0 ||
+      orig_stride < (size_t)xsize * 3 || comp_stride < (size_t)xsize * 3)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  jxg_status st = ctx_enter(ctx, true, &c);
+  if (!st) st = order_input(c, c);
+  return st ? st
+            : msssim_device(c, static_cast<const uint8_t*>(d_orig), orig_stride,
+                            static_cast<const uint8_t*>(d_comp), comp_stride, xsize, ysize, out);
+}
+
+jxg_status jxg_msssim_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
+                           const uint8_t* comp, size_t comp_stride, uint32_t xsize,
+                           uint32_t ysize, jxg_msssim* out) {
+  if (!ctx || !orig || !comp || !out || xsize == 0 || ysize == 0 ||
+      orig_stride < (size_t)xsize * 3 || comp_stride < (size_t)xsize * 3)
+    return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : msssim_host(c, orig, orig_stride, comp, comp_stride, xsize, ysize, out);
+}
+
 jxg_status jxg_reconstruct_rgb8_device(jxg_ctx* ctx, void* d_rgb, size_t row_stride) {
   if (!ctx || !d_rgb) return JXG_ERR_INVALID_ARG;
   Ctx* c;
@@ -426,6 +451,22 @@ jxg_status jxg_sweep_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, ui
 jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats) {
   if (!ctx || !stats) return JXG_ERR_INVALID_ARG;
   *stats = reinterpret_cast<const Ctx*>(ctx)->sw.stats;
+  return JXG_OK;
+}
+
+jxg_status jxg_set_sweep_msssim(jxg_ctx* ctx, int on) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->sw.msssim = on != 0;
+  return JXG_OK;
+}
+
+jxg_status jxg_sweep_msssim(jxg_ctx* ctx, jxg_msssim* out, uint32_t n) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  const Ctx::Sweep& sw = reinterpret_cast<const Ctx*>(ctx)->sw;
+  if (!sw.ms_have || n != sw.ms.size()) return JXG_ERR_INVALID_ARG;
+  std::copy(sw.ms.begin(), sw.ms.end(), out);
   return JXG_OK;
 }
 

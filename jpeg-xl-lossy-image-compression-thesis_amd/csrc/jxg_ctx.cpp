@@ -245,6 +245,7 @@ void ctx_destroy(Ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->sw.ev)
     if (e) (void)hipEventDestroy(e);
+  if (c->sw.ev_pyr) (void)hipEventDestroy(c->sw.ev_pyr);
   if (c->rc.ev_sigma) (void)hipEventDestroy(c->rc.ev_sigma);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_write) (void)hipEventDestroy(c->ev_write);

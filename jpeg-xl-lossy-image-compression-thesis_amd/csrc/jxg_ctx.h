@@ -162,6 +162,11 @@ struct Ctx : EncArenas {
     DevBuf<uint64_t> sse;
     DevBuf<double> part, ssim;
     bool gauss_ready = false;
+    // MS-SSIM (jxg_msssim_rgb8, a sweep's lane): the pyramids of the two
+    // images (a sweep's lane fills only pyr_c), per-workgroup partials, the
+    // ten window sums; allocated by the first use
+    DevBuf<float> pyr_o, pyr_c;
+    DevBuf<double> ms_part, ms_out;
   } q;
   // decode-side reconstruction (jxg_reconstruct_rgb8; jxg_reconstruct.cpp),
   // allocated by its first call: tables, two sets of three block-padded f32
@@ -206,12 +211,21 @@ struct Ctx : EncArenas {
     jxg_decode_batch_stats stats{};
   } decb;
   // sweep (jxg_sweep_rgb8; jxg_sweep.cpp): the host variant's device image,
-  // the points' pinned results [n][2] and events [n][3], the last call's stats
+  // the points' pinned results [n][2] and events [n][3], the last call's stats.
+  // With jxg_set_sweep_msssim: the original's pyramid (built once per sweep on
+  // this context's stream, read by every lane after ev_pyr), the points' pinned
+  // window sums [n][10], the last sweep's results in point order
   struct Sweep {
     DevBuf<uint8_t> rgb;
     PinBuf<uint64_t> h_q;
     std::vector<hipEvent_t> ev;
     jxg_sweep_stats stats{};
+    bool msssim = false;  // the switch
+    DevBuf<float> pyr_o;
+    hipEvent_t ev_pyr = nullptr;
+    PinBuf<double> h_ms;
+    std::vector<jxg_msssim> ms;
+    bool ms_have = false;  // the last sweep computed `ms`
   } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
@@ -353,6 +367,12 @@ struct SweepReq {
   int quality = 0;         // 0 none, 1 sse, 2 also ssim
   uint64_t* h_q = nullptr;  // pinned [2]: sse, the SSIM sum's bits
   hipEvent_t* ev = nullptr;  // [3]: chain start, chain end, metrics end
+  // MS-SSIM behind the SSIM kernels (quality 2 with the switch on, frames of
+  // kMsMinEdge and more): pinned [10] window sums, the original's pyramid and
+  // the event it is complete after
+  double* h_ms = nullptr;
+  const float* pyr_o = nullptr;
+  hipEvent_t ev_pyr = nullptr;
 };
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                        size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
@@ -402,6 +422,14 @@ jxg_status compare_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_
                           size_t sc, uint32_t w, uint32_t h, int want_ssim, jxg_quality* out);
 jxg_status compare_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* comp, size_t sc,
                         uint32_t w, uint32_t h, int want_ssim, jxg_quality* out);
+// MS-SSIM: every field NaN (nothing launched) under kMsMinEdge
+jxg_status msssim_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_t* d_comp,
+                         size_t sc, uint32_t w, uint32_t h, jxg_msssim* out);
+jxg_status msssim_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* comp, size_t sc,
+                       uint32_t w, uint32_t h, jxg_msssim* out);
+// the result from the ten window sums (ssim[0 .. 4], cs[0 .. 4]) of a w x h pair
+void msssim_result(uint32_t w, uint32_t h, const double* sums, jxg_msssim* out);
+void msssim_nan(jxg_msssim* out);
 
 // ---- jxg_reconstruct.cpp ----
 // the frame constants of a reconstruction: the encoder fills them from its

@@ -331,6 +331,28 @@ uint32_t ssim_partials(uint32_t w, uint32_t h);
 hipError_t set_gauss_table(const double* g, hipStream_t s);
 void launch_metrics(const MetricArgs& a, hipStream_t s);
 void launch_ssim(const MetricArgs& a, hipStream_t s);  // the SSIM kernels of launch_metrics alone
+// MS-SSIM (jxg_metrics.hip): five scales, scale j of
+// (w >> j) x (h >> j).  Scale 0 is the RGB8 images; scales 1 .. 4 are exact
+// f32 planes [3][h_j][w_j] (2 x 2 box means), the four levels of one image back
+// to back in one buffer of ms_pyramid_floats(w, h).
+constexpr int kMsScales = 5;
+constexpr uint32_t kMsMinEdge = 176;  // scale 4 is at least 11 x 11
+size_t ms_pyramid_floats(uint32_t w, uint32_t h);
+size_t ms_level_offset(uint32_t w, uint32_t h, int j);  // j = 1 .. 4, in floats
+uint32_t ms_partials(uint32_t w, uint32_t h);  // doubles: [scale][ssim | cs][workgroup]
+void launch_ms_pyramid(const uint8_t* img, size_t stride, uint32_t w, uint32_t h, float* pyr,
+                       hipStream_t s);
+struct MsArgs {
+  const uint8_t* orig;
+  const uint8_t* comp;
+  size_t so, sc;  // row strides (bytes)
+  uint32_t w, h;  // min(w, h) >= kMsMinEdge
+  const float* pyr_o;  // the two images' pyramids (launch_ms_pyramid)
+  const float* pyr_c;
+  double* partials;    // [ms_partials(w, h)]
+  double* out;         // [10]: window sums of ssim[0 .. 4], then of cs[0 .. 4]
+};
+void launch_msssim(const MsArgs& a, hipStream_t s);
 // decode-side reconstruction (jxg_recon.hip): the decoded
 // image from the context's quantized coefficients.  Table blob (floats, built
 // in double by build_recon_tables): inverse-DCT matrices [k][x] for n = 4 ..

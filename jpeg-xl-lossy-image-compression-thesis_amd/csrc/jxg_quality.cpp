@@ -70,6 +70,70 @@ jxg_status compare_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* c
   return compare_device(c, c->q.orig.p, row, c->q.comp.p, row, w, h, want_ssim, out);
 }
 
+// MS-SSIM of Wang, Simoncelli, Bovik 2003: the per-scale
+// means pool like the SSIM above; the product runs in ascending scale from 1.0
+void msssim_result(uint32_t w, uint32_t h, const double* sums, jxg_msssim* out) {
+  static const double kW[kMsScales] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
+  for (int j = 0; j < kMsScales; j++) {
+    const double n = 3.0 * (double)((w >> j) - 10) * (double)((h >> j) - 10);
+    out->ssim[j] = sums[j] / n;
+    out->cs[j] = sums[kMsScales + j] / n;
+  }
+  double v = 1.0;
+  for (int j = 0; j < kMsScales; j++) {
+    const double m = j < kMsScales - 1 ? out->cs[j] : out->ssim[j];
+    v *= std::pow(m > 0.0 ? m : 0.0, kW[j]);
+  }
+  out->ms_ssim = v;
+}
+
+void msssim_nan(jxg_msssim* out) {
+  out->ms_ssim = NAN;
+  for (int j = 0; j < kMsScales; j++) out->cs[j] = out->ssim[j] = NAN;
+}
+
+jxg_status msssim_device(Ctx* c, const uint8_t* d_orig, size_t so, const uint8_t* d_comp,
+                         size_t sc, uint32_t w, uint32_t h, jxg_msssim* out) {
+  if (std::min(w, h) < kMsMinEdge) {
+    msssim_nan(out);
+    return JXG_OK;
+  }
+  hipStream_t s = c->stream;
+  Ctx::Quality& q = c->q;
+  const jxg_status gs = quality_gauss(c);
+  if (gs) return gs;
+  const size_t nf = ms_pyramid_floats(w, h);
+  JXG_HIP(q.pyr_o.ensure(nf));
+  JXG_HIP(q.pyr_c.ensure(nf));
+  JXG_HIP(q.ms_part.ensure(ms_partials(w, h)));
+  JXG_HIP(q.ms_out.ensure(2 * kMsScales));
+  launch_ms_pyramid(d_orig, so, w, h, q.pyr_o.p, s);
+  launch_ms_pyramid(d_comp, sc, w, h, q.pyr_c.p, s);
+  const MsArgs a{d_orig, d_comp, so, sc, w, h, q.pyr_o.p, q.pyr_c.p, q.ms_part.p, q.ms_out.p};
+  launch_msssim(a, s);
+  JXG_HIP(hipGetLastError());
+  double sums[2 * kMsScales];
+  JXG_HIP(hipMemcpyAsync(sums, q.ms_out.p, sizeof(sums), hipMemcpyDeviceToHost, s));
+  JXG_HIP(hipStreamSynchronize(s));
+  msssim_result(w, h, sums, out);
+  return JXG_OK;
+}
+
+jxg_status msssim_host(Ctx* c, const uint8_t* orig, size_t so, const uint8_t* comp, size_t sc,
+                       uint32_t w, uint32_t h, jxg_msssim* out) {
+  if (std::min(w, h) < kMsMinEdge) {
+    msssim_nan(out);
+    return JXG_OK;
+  }
+  const size_t row = (size_t)w * 3, n = row * h;
+  JXG_HIP(c->q.orig.ensure(n));
+  JXG_HIP(c->q.comp.ensure(n));
+  hipStream_t s = c->stream;
+  JXG_HIP(hipMemcpy2DAsync(c->q.orig.p, row, orig, so, row, h, hipMemcpyHostToDevice, s));
+  JXG_HIP(hipMemcpy2DAsync(c->q.comp.p, row, comp, sc, row, h, hipMemcpyHostToDevice, s));
+  return msssim_device(c, c->q.orig.p, row, c->q.comp.p, row, w, h, out);
+}
+
 jxg_status homogeneity_map(Ctx* c, const float* xyb, uint32_t xsize, uint32_t ysize,
                            float distance, uint32_t flags, float* r3, uint8_t* type) {
   const size_t plane = (size_t)xsize * ysize, nb = plane / 64;

@@ -8,6 +8,10 @@
 // the lane's own coefficients, ending in the fused colour + squared-error
 // kernel, then the SSIM kernels on the stored image when asked for; the two
 // result words land in pinned memory before the frame's completion event.
+// With jxg_set_sweep_msssim the lane runs, in the SSIM kernels' place, the
+// pyramid of its decoded image and the MS-SSIM kernels
+// against the original's pyramid, which the context built once on its own
+// stream; their scale 0 is the SSIM.
 #include <cmath>
 #include <cstring>
 
@@ -40,11 +44,29 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
   if (st) return st;
   JXG_HIP(hipEventRecord(rq.ev[1], s));
   rq.h_q[1] = 0;
-  if (ssim) {
+  const bool ms = ssim && rq.h_ms;
+  if (ssim && !ms) {
     const MetricArgs a{d_orig, S->rc.rgb.p, so, row, w, h, q.sse.p, q.part.p, q.ssim.p};
     launch_ssim(a, s);
     JXG_HIP(hipGetLastError());
     JXG_HIP(hipMemcpyAsync(rq.h_q + 1, q.ssim.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  // MS-SSIM's scale 0 is ssim_kernel's sum bit for bit (ssim_cs_kernel<false>
+  // and the reduction order; tests/test_gpu_msssim.py), so the SSIM kernels are
+  // not run a second time: the frame's SSIM word is the first of the ten sums
+  if (ms) {
+    JXG_HIP(q.pyr_c.ensure(ms_pyramid_floats(w, h)));
+    JXG_HIP(q.ms_part.ensure(ms_partials(w, h)));
+    JXG_HIP(q.ms_out.ensure(2 * kMsScales));
+    launch_ms_pyramid(S->rc.rgb.p, row, w, h, q.pyr_c.p, s);
+    JXG_HIP(hipStreamWaitEvent(s, rq.ev_pyr, 0));
+    const MsArgs a{d_orig, S->rc.rgb.p, so, row, w, h, rq.pyr_o, q.pyr_c.p, q.ms_part.p,
+                   q.ms_out.p};
+    launch_msssim(a, s);
+    JXG_HIP(hipGetLastError());
+    JXG_HIP(hipMemcpyAsync(rq.h_ms, q.ms_out.p, 2 * kMsScales * sizeof(double),
+                           hipMemcpyDeviceToHost, s));
+    JXG_HIP(hipMemcpyAsync(rq.h_q + 1, q.ms_out.p, sizeof(double), hipMemcpyDeviceToHost, s));
   }
   JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   JXG_HIP(hipEventRecord(rq.ev[2], s));
@@ -79,6 +101,13 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   const uint32_t nv = (uint32_t)valid.size();
   Ctx::Sweep& sw = c->sw;
   sw.stats = jxg_sweep_stats{};
+  // MS-SSIM rides on quality 2 (jxg_set_sweep_msssim); kernels only for frames
+  // it is defined for, NaN results otherwise
+  const bool ms = quality == 2 && sw.msssim;
+  const bool ms_run = ms && std::min(w, h) >= kMsMinEdge;
+  sw.ms_have = false;
+  sw.ms.clear();
+  if (ms) sw.ms.assign(n, jxg_msssim{});
   // the context is lane 0 and encodes with its frames' points: its own
   // parameters are put back however the call ends
   const jxg_params saved = c->params;
@@ -97,6 +126,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       if (statuses) statuses[i] = e;
     }
     sw.stats.ms_call = ms_since(t0);
+    sw.ms.clear();
     return e;
   };
   if (nv) {
@@ -119,6 +149,20 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         sw.ev.push_back(e);
       }
     }
+    if (ms_run) {  // the original's pyramid, once: every lane reads it after ev_pyr
+      if (sw.h_ms.ensure((size_t)nv * 2 * kMsScales) != hipSuccess ||
+          sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess)
+        return fail(JXG_ERR_OOM);
+      if (!sw.ev_pyr && make_event(&sw.ev_pyr, hipEventDisableTiming) != hipSuccess)
+        return fail(JXG_ERR_HIP);
+      if (on_device) {
+        const jxg_status so = order_input(c, c);
+        if (so) return fail(so);
+      }
+      launch_ms_pyramid(d, stride, w, h, sw.pyr_o.p, c->stream);
+      if (hipGetLastError() != hipSuccess || hipEventRecord(sw.ev_pyr, c->stream) != hipSuccess)
+        return fail(JXG_ERR_HIP);
+    }
     uint32_t got = 0;
     jxg_status e = JXG_OK;
     // point valid[got]'s codestream (its completion event covers the quality
@@ -138,6 +182,10 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       o.mse = (double)sse / (double)o.samples;
       o.psnr = 10.0 * std::log10((255.0 * 255.0) / o.mse);
       o.ssim = ssim ? ssum / (3.0 * (double)(w - 10) * (double)(h - 10)) : NAN;
+      if (ms_run)
+        msssim_result(w, h, sw.h_ms.p + (size_t)k * 2 * kMsScales, &sw.ms[i]);
+      else if (ms)
+        msssim_nan(&sw.ms[i]);
       sw.stats.ms_recon += elapsed(sw.ev[3 * k], sw.ev[3 * k + 1]);
       sw.stats.ms_metrics += elapsed(sw.ev[3 * k + 1], sw.ev[3 * k + 2]);
     };
@@ -153,6 +201,11 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.h_q = sw.h_q.p + 2 * (size_t)k;
         rq.ev = sw.ev.data() + 3 * (size_t)k;
       }
+      if (ms_run) {
+        rq.h_ms = sw.h_ms.p + (size_t)k * 2 * kMsScales;
+        rq.pyr_o = sw.pyr_o.p;
+        rq.ev_pyr = sw.ev_pyr;
+      }
       e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
       // completed points whose copies have landed (or when more than two wait)
       while (!e && pipe_done_ready(c)) take();
@@ -164,6 +217,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.stats.points = nv;
   sw.stats.lanes = pipe_shape(f.ngroups, f.tiles_x * f.tiles_y, c->lane_cap, hw_queues()).lanes;
   if (statuses) std::copy(st.begin(), st.end(), statuses);
+  sw.ms_have = ms;
   sw.stats.ms_call = ms_since(t0);
   return first;
 }

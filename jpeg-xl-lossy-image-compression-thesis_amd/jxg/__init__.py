@@ -95,6 +95,15 @@ class _Quality(ctypes.Structure):
                 ("psnr", ctypes.c_double), ("ssim", ctypes.c_double)]
 
 
+class _Msssim(ctypes.Structure):
+    _fields_ = [("ms_ssim", ctypes.c_double), ("cs", ctypes.c_double * 5),
+                ("ssim", ctypes.c_double * 5)]
+
+    def as_dict(self) -> dict:
+        return {"ms_ssim": float(self.ms_ssim), "cs": [float(v) for v in self.cs],
+                "ssim": [float(v) for v in self.ssim]}
+
+
 class _SweepPoint(ctypes.Structure):
     _fields_ = [("distance", ctypes.c_float), ("effort", ctypes.c_int),
                 ("proposals", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -123,6 +132,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_decode_timings", "jxg_decode_batch_rgb8", "jxg_decode_batch_rgb8_device",
            "jxg_set_decode_batch_bytes", "jxg_decode_batch_timings",
            "jxg_sweep_rgb8", "jxg_sweep_rgb8_device", "jxg_sweep_timings",
+           "jxg_msssim_rgb8", "jxg_msssim_rgb8_device", "jxg_set_sweep_msssim",
+           "jxg_sweep_msssim",
 )
 
 _lib = None
@@ -215,6 +226,11 @@ def load():
                                    ctypes.POINTER(ctypes.c_int)]
     lib.jxg_sweep_rgb8_device.argtypes = lib.jxg_sweep_rgb8.argtypes
     lib.jxg_sweep_timings.argtypes = [vp, ctypes.POINTER(_SweepStats)]
+    ms_args = [vp, vp, sz, vp, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_Msssim)]
+    lib.jxg_msssim_rgb8.argtypes = ms_args
+    lib.jxg_msssim_rgb8_device.argtypes = ms_args
+    lib.jxg_set_sweep_msssim.argtypes = [vp, ctypes.c_int]
+    lib.jxg_sweep_msssim.argtypes = [vp, ctypes.POINTER(_Msssim), ctypes.c_uint32]
     _lib = lib
     return lib
 
@@ -460,7 +476,8 @@ class Encoder:
         return self._take(buf) if copy else Codestream(buf)
 
     # ---- sweep: one image over many settings (jxg_sweep_rgb8) ----
-    _QUALITY = {None: 0, "none": 0, "psnr": 1, "ssim": 2, 0: 0, 1: 1, 2: 2}
+    # "msssim": a quality-2 sweep with jxg_set_sweep_msssim on for its duration
+    _QUALITY = {None: 0, "none": 0, "psnr": 1, "ssim": 2, "msssim": 2, 0: 0, 1: 1, 2: 2}
 
     @staticmethod
     def _sweep_points(points):
@@ -476,8 +493,9 @@ class Encoder:
 
     def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict):
         if quality not in self._QUALITY:
-            raise ValueError("quality: 'ssim', 'psnr' or None")
+            raise ValueError("quality: 'msssim', 'ssim', 'psnr' or None")
         level = self._QUALITY[quality]
+        ms = quality == "msssim"
         pts = self._sweep_points(points)
         n = len(pts)
         if n == 0:
@@ -486,7 +504,18 @@ class Encoder:
         outs = (_Buffer * n)()
         qs = (_Quality * n)() if level else None
         st = (ctypes.c_int * n)()
-        ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
+        mss = None
+        if ms:
+            _check(load().jxg_set_sweep_msssim(self._ctx, 1))
+        try:
+            ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
+            if ms:  # (a sweep that failed as a whole has none: ret is raised below)
+                m = (_Msssim * n)()
+                if load().jxg_sweep_msssim(self._ctx, m, n) == 0:
+                    mss = m
+        finally:
+            if ms:
+                load().jxg_set_sweep_msssim(self._ctx, 0)
         st = [int(v) for v in st]
         if ret != 0 and (strict or self._batch_call_failed(ret, st)):
             for i in range(n):
@@ -500,6 +529,9 @@ class Encoder:
             q = None
             if level:
                 q = {k: getattr(qs[i], k) for k in ("sse", "samples", "mse", "psnr", "ssim")}
+                if mss is not None:
+                    q["ms_ssim"] = float(mss[i].ms_ssim)
+                    q["cs"] = [float(v) for v in mss[i].cs]
             res.append((self._take(outs[i]), q))
         return res
 
@@ -511,8 +543,10 @@ class Encoder:
         with ``distance``, ``effort`` and optionally ``proposals`` / ``flags``
         (the keywords of :class:`Encoder`), or a tuple in that order.
         ``quality``: ``"ssim"`` (sse, mse, psnr and ssim of each point's
-        decoded image against ``rgb``), ``"psnr"`` (the decoded image is never
-        written; ssim NaN) or ``None``.  Returns ``[(bytes, dict | None), ...]``
+        decoded image against ``rgb``), ``"msssim"`` (the same plus ``ms_ssim``
+        and the per-scale ``cs`` of :meth:`msssim`, computed on the point's
+        lane), ``"psnr"`` (the decoded image is never written; ssim NaN) or
+        ``None``.  Returns ``[(bytes, dict | None), ...]``
         in point order, each equal to a fresh ``Encoder(**point)``'s
         ``encode`` / ``reconstruct_device`` / ``compare_device``.  Raises
         JxgError on the first refused point; with ``strict=False`` a refused
@@ -755,6 +789,32 @@ class Encoder:
             self._ctx, ctypes.c_void_p(d_orig), orig_stride or width * 3, ctypes.c_void_p(d_comp),
             comp_stride or width * 3, width, height, 1 if ssim else 0, ctypes.byref(q)))
         return {"sse": q.sse, "samples": q.samples, "mse": q.mse, "psnr": q.psnr, "ssim": q.ssim}
+
+    def msssim(self, orig: np.ndarray, comp: np.ndarray) -> dict:
+        """MS-SSIM on the GPU (jxg_msssim_rgb8; Wang, Simoncelli, Bovik 2003):
+        orig / comp are (H, W, 3) uint8.  Returns ``ms_ssim`` and the per-scale
+        means ``cs[5]`` / ``ssim[5]`` (``ssim[0]`` is :meth:`compare`'s ssim);
+        every field is NaN when min(H, W) < 176."""
+        o = np.asarray(orig)
+        c = np.asarray(comp)
+        if o.shape != c.shape or o.ndim != 3 or o.shape[2] != 3:
+            raise ValueError("orig / comp must both be (H, W, 3) uint8")
+        o = np.ascontiguousarray(o, dtype=np.uint8)
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        h, w = o.shape[:2]
+        m = _Msssim()
+        _check(load().jxg_msssim_rgb8(self._ctx, o.ctypes.data, w * 3, c.ctypes.data, w * 3, w, h,
+                                      ctypes.byref(m)))
+        return m.as_dict()
+
+    def msssim_device(self, d_orig: int, d_comp: int, width: int, height: int,
+                      orig_stride: int | None = None, comp_stride: int | None = None) -> dict:
+        """Same on device-resident RGB8 (jxg_msssim_rgb8_device)."""
+        m = _Msssim()
+        _check(load().jxg_msssim_rgb8_device(
+            self._ctx, ctypes.c_void_p(d_orig), orig_stride or width * 3, ctypes.c_void_p(d_comp),
+            comp_stride or width * 3, width, height, ctypes.byref(m)))
+        return m.as_dict()
 
 
 # ---------------------------------------------------------------------------

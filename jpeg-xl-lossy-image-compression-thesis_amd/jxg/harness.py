@@ -17,7 +17,9 @@ Mirrors pscoro/JPEG-XL-Lossy-Image-Compression-Thesis benchmark-jpegxl:
   written to ``comparison_diffs.csv`` and ``summary.csv`` next to results_1.
 * ``compare_to_orig`` -- JXLCompressionBenchmark::compare_to_orig
   (benchmark.rs:895-972): file-size ratios (metrics.rs:15-26), MSE / PSNR /
-  SSIM on the GPU; MS-SSIM is 0.0 as in the reference (benchmark.rs:933);
+  SSIM on the GPU; MS-SSIM is 0.0 by default as in the reference
+  (benchmark.rs:932-933 never fills it) and, with ``ms_ssim=True``, the GPU's
+  jxg_msssim_rgb8 (Wang, Simoncelli, Bovik 2003; NaN under 176 pixels);
   Butteraugli and SSIMULACRA2 need libjxl's tools (Docker) and are 0.0 here.
 * ``file_size_ratio`` -- metrics.rs:15-26.
 * ``sweep_and_compare`` -- the per-image loop of benchmark.rs:637-677 (every
@@ -173,7 +175,8 @@ def compare_results(results_1: str, results_2: str):
 def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int,
                     comp_name: str, comp_rgb, comp_file_size: int,
                     distance: float, effort: int, result_file: str | None = None,
-                    ssim: bool = True, decode_with=None) -> ComparisonResult:
+                    ssim: bool = True, decode_with=None,
+                    ms_ssim: bool = False) -> ComparisonResult:
     """benchmark.rs:895-972 with the metrics on the GPU.  ``encoder`` is a
     jxg.Encoder (its context runs jxg_compare_rgb8); ``comp_rgb`` is the
     decoded image (stock djxl where present, any decoder otherwise) -- or,
@@ -182,18 +185,21 @@ def compare_to_orig(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_siz
     GPU (Encoder.decode, jxg_decode_rgb8): the reference harnesses' step of
     decoding the file that was written (image_reader.rs:555-606 through
     jpegxl-rs; ``djxl IN.jxl OUT.png``).  Raw sizes are width * height * 3
-    (image_reader.rs:523-540, Rgb8)."""
+    (image_reader.rs:523-540, Rgb8).  ``ms_ssim``: fill the MS-SSIM column
+    (Encoder.msssim) instead of the reference's 0.0."""
     if decode_with is not None:
         comp_rgb = decode_with.decode(comp_rgb)
     h, w = orig_rgb.shape[:2]
     raw = w * h * 3
     q = encoder.compare(orig_rgb, comp_rgb, ssim=ssim)
+    if ms_ssim:
+        q["ms_ssim"] = encoder.msssim(orig_rgb, comp_rgb)["ms_ssim"]
     return _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_size, raw, q,
                    ssim, result_file)
 
 
 def compare_batch_to_orig(encoder, items, decode_with, result_file: str | None = None,
-                          ssim: bool = True):
+                          ssim: bool = True, ms_ssim: bool = False):
     """compare_to_orig(..., decode_with=) of many files with one decode: the
     harness decodes every compressed file it wrote (benchmark.rs:637-660), and
     one frame's pass-group kernel leaves the GPU almost idle, so all items'
@@ -205,7 +211,7 @@ def compare_batch_to_orig(encoder, items, decode_with, result_file: str | None =
     items = list(items)
     decoded = decode_with.decode_batch([it[4] for it in items])
     return [compare_to_orig(encoder, it[0], it[1], it[2], it[3], rgb, it[5], it[6], it[7],
-                            result_file=result_file, ssim=ssim)
+                            result_file=result_file, ssim=ssim, ms_ssim=ms_ssim)
             for it, rgb in zip(items, decoded)]
 
 
@@ -216,7 +222,7 @@ def _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_si
         int(comp_file_size), raw, raw,
         file_size_ratio(orig_file_size, comp_file_size, "comp"),
         file_size_ratio(raw, comp_file_size, "comp"),
-        q["mse"], q["psnr"], q["ssim"] if ssim else 0.0, 0.0, 0.0, 0.0, 0.0)
+        q["mse"], q["psnr"], q["ssim"] if ssim else 0.0, q.get("ms_ssim", 0.0), 0.0, 0.0, 0.0)
     if result_file:
         write_csv_header(result_file, RESULT_HEADER)
         write_csv([res], result_file)
@@ -225,7 +231,8 @@ def _record(orig_name, comp_name, distance, effort, orig_file_size, comp_file_si
 
 def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int,
                        comp_name: str, distance: float, effort: int,
-                       result_file: str | None = None, ssim: bool = True):
+                       result_file: str | None = None, ssim: bool = True,
+                       ms_ssim: bool = False):
     """Encode + compare_to_orig in one process with no decoder: the image is
     encoded from device memory, its decoded pixels are reconstructed on the
     device (Encoder.reconstruct_device, jxg_reconstruct_rgb8_device) and the
@@ -245,13 +252,15 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
     data = encoder.encode_device(d_orig.data_ptr(), w, h)
     encoder.reconstruct_device(d_comp.data_ptr())
     q = encoder.compare_device(d_orig.data_ptr(), d_comp.data_ptr(), w, h, ssim=ssim)
+    if ms_ssim:
+        q["ms_ssim"] = encoder.msssim_device(d_orig.data_ptr(), d_comp.data_ptr(), w, h)["ms_ssim"]
     raw = w * h * 3
     return data, _record(orig_name, comp_name, distance, effort, orig_file_size, len(data), raw, q,
                          ssim, result_file)
 
 
 def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
-                      result_file: str | None = None, ssim: bool = True):
+                      result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False):
     """The harness's per-image loop (benchmark.rs:637-677) in one call: the
     image is encoded at every point (dicts with ``distance`` / ``effort`` and
     optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
@@ -260,13 +269,17 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     ``comp_image_name(stem of orig_name, distance, effort)`` (benchmark.rs:
     644-650).  ``encoder``'s own parameters play no part.  Returns
     (codestreams, records); the records, and the CSV rows in point order, equal
-    per-point :func:`encode_and_compare` on an encoder of those parameters."""
+    per-point :func:`encode_and_compare` on an encoder of those parameters.
+    ``ms_ssim`` (needs ``ssim``): the MS-SSIM column from the points' lanes
+    (``quality="msssim"``)."""
+    if ms_ssim and not ssim:
+        raise ValueError("ms_ssim rides on the quality-2 sweep: it needs ssim=True")
     o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
     if o.ndim != 3 or o.shape[2] != 3:
         raise ValueError("orig_rgb must be (H, W, 3) uint8")
     h, w = o.shape[:2]
     points = list(points)
-    res = encoder.sweep(o, points, quality="ssim" if ssim else "psnr")
+    res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr")
     stem = os.path.splitext(orig_name)[0]
     raw = w * h * 3
     datas, records = [], []
