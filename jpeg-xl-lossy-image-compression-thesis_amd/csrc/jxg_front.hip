@@ -36,6 +36,23 @@ __constant__ float c_sdperm[kNT * 3 * 64]; // [T][c][r][k] distortion weight at 
 __constant__ float c_btab[256];            // [q] = AdjustQuantBias of a magnitude q < 256 (host table: 0, 1 - 0.0700..., q - 0.145 / q)
 __constant__ uint8_t c_zz[kNT * 64];       // [T][r][k] = zigzag index of co_index(T,k,r)
 
+// quant_xb's zero votes, counted once per wave and vote in JXG_FRONT_PROFILE
+// builds ([0] votes, [1] all-zero), printed by dump_front_profile()
+#ifdef JXG_FRONT_PROFILE
+__device__ unsigned long long g_fzero[2];
+#define FZERO_COUNT(hit)                                                           \
+  do {                                                                             \
+    if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)__ballot(1)) - 1) { \
+      atomicAdd(&g_fzero[0], 1ull);                                                \
+      if (hit) atomicAdd(&g_fzero[1], 1ull);                                       \
+    }                                                                              \
+  } while (0)
+#else
+#define FZERO_COUNT(hit) \
+  do {                   \
+  } while (0)
+#endif
+
 constexpr int kTile = 64;
 constexpr int kRows = 66;           // 64 + halo above/below
 constexpr int kS = 75;              // LDS row stride (floats)
@@ -656,11 +673,26 @@ __device__ __forceinline__ void quant_xb(const GroupCtx& G, int ti, f2* v, float
   uint32_t ebx = 0, ebb = 0;  // exponent sums of X's and of B's eight values
   float eb[8];
   int sx[8], sb[8];
+  // the scaled values of all eight k first, then one wave vote per k over the
+  // wave's 8 blocks: where X and B quantize to 0 in every lane, sq = +-0, vq -
+  // sq == vq (a -0 becomes +0: e * e is +0 for either), no rate, no non-zeros
+  // (the negated compare: a NaN takes the full path, as its select does)
+  f2 vqs[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) vqs[k] = (v[k] - kxb * f2{A.yd[k], A.yd[k]}) * (wk[k] * sc2);
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    const f2 ws = wk[k] * sc2;
-    const f2 rv = v[k] - kxb * f2{A.yd[k], A.yd[k]};
-    const f2 vq = rv * ws;
+    const f2 vq = vqs[k];
+    const bool allz = !__any(!(fabsf(vq.x) < 0.58f) || !(fabsf(vq.y) < 0.58f));
+    FZERO_COUNT(allz);
+    if (allz) {
+      const f2 e = vq * f2{sxp[k], sbp[k]};
+      A.part = fmaf(e.x, e.x, A.part);
+      eb[k] = e.y;
+      sx[k] = 0;
+      sb[k] = 0;
+      continue;
+    }
     f2 qf;
     qf.x = fabsf(vq.x) < 0.58f ? 0.0f : floorf(fminf(fabsf(vq.x), 32767.0f) + 0.5f);
     qf.y = fabsf(vq.y) < 0.58f ? 0.0f : floorf(fminf(fabsf(vq.y), 32767.0f) + 0.5f);
@@ -1539,6 +1571,9 @@ void dump_front_profile() {
   std::fprintf(stderr, "front_kernel thread-0 shader cycles (Mcycles summed over workgroups):\n");
   for (int k = 0; k < 10; k++)
     std::fprintf(stderr, "  %-16s %12.3f\n", kNames[k], k ? h[k] / 1e6 : (double)h[0]);
+  unsigned long long z[2];
+  if (hipMemcpyFromSymbol(z, HIP_SYMBOL(g_fzero), sizeof(z)) != hipSuccess) return;
+  std::fprintf(stderr, "quant_xb zero votes: %llu of %llu (wave, k)\n", z[1], z[0]);
 }
 #else
 void dump_front_profile() {}

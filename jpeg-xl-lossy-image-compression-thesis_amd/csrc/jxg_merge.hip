@@ -159,6 +159,22 @@ __device__ unsigned long long g_mprof[16][8];
   do {                \
   } while (0)
 #endif
+// quant_pass's zero votes: counted once per wave and vote in profile builds
+// ([channel][0 votes, 1 all-zero]), printed with the cycle sums
+#ifdef JXG_MERGE_PROFILE
+__device__ unsigned long long g_mzero[3][2];
+#define MZERO_COUNT(ch, hit)                                                          \
+  do {                                                                                \
+    if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)__ballot(1)) - 1) {    \
+      atomicAdd(&g_mzero[(ch)][0], 1ull);                                             \
+      if (hit) atomicAdd(&g_mzero[(ch)][1], 1ull);                                    \
+    }                                                                                 \
+  } while (0)
+#else
+#define MZERO_COUNT(ch, hit) \
+  do {                       \
+  } while (0)
+#endif
 
 // merged shapes (== oracle jxo_shapes): raw id, blocks down / across (log2),
 // cost multiplier
@@ -555,6 +571,10 @@ template <int RPC, bool WRITE, int CH, class L>
 __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L& S, const QTab<RPC>& T) {
   static_assert(WRITE == kIsWrite<L>, "the write kernel's LDS carries the per-slot arrays");
   constexpr int cidx = CH == 1 ? 0 : (CH == 0 ? 1 : 2);  // 0 Y, 1 X, 2 B
+  // the wave-uniform zero path: the estimate's X and B passes (about 65 % and
+  // 63 % of their row pairs on the 8K bench frames).  Not Y (17 %: the vote
+  // costs more than it saves) and not the write pass.
+  constexpr bool ZERO = !WRITE && CH != 1;
   const int C = P.C(), NV = P.NV();
   // chroma from luma of the tile (front kernel): X - kx Yd, B - kb Yd
   // (write: of the slot's tile, from setup_slots)
@@ -601,8 +621,7 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L&
     // rows in pairs: the float multiplies / adds of the two rows are one
     // packed op each (f2, no contraction: each half is the scalar op order);
     // the distortion chain stays in row order
-#pragma unroll
-    for (int kk = 0; kk < RPC; kk += 2) {
+    auto scaled = [&](int kk) {
       const int ky = ch * RPC + kk;
       const f2 coef = f2{cplane[ky * kMS], cplane[(ky + 1) * kMS]};
       if (WRITE && llf_col) {
@@ -613,7 +632,37 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L&
       if (CH != 1) rv = rv - f2{kc, kc} * f2{yd[ky * kMS], yd[(ky + 1) * kMS]};
       // LLF positions carry weight 0 (host tables): vq = +-0 quantizes to 0
       // and contributes nothing
-      const f2 vq = rv * (f2{w[kk], w[kk + 1]} * f2{scale, scale});
+      return rv * (f2{w[kk], w[kk + 1]} * f2{scale, scale});
+    };
+    // ZERO: the scaled values of all the lane's rows first (the LDS reads stay
+    // one pipelined batch), then one wave vote per row pair (a vote per chunk,
+    // alone or ahead of these, and values formed inside the loop all measured
+    // slower: profiles/r09zero/variants.md)
+    f2 vqs[ZERO ? RPC / 2 : 1];
+    if constexpr (ZERO) {
+#pragma unroll
+      for (int kk = 0; kk < RPC; kk += 2) vqs[kk >> 1] = scaled(kk);
+    }
+#pragma unroll
+    for (int kk = 0; kk < RPC; kk += 2) {
+      const int ky = ch * RPC + kk;
+      f2 vq;
+      if constexpr (ZERO) vq = vqs[kk >> 1];
+      else vq = scaled(kk);
+      if constexpr (ZERO) {
+        // (the negated compare: a NaN takes the full path, as its select does)
+        const bool allz = !__any(!(fabsf(vq.x) < 0.58f) || !(fabsf(vq.y) < 0.58f));
+        MZERO_COUNT(CH, allz);
+        if (allz) {
+          // every active lane of the wave (an invalid varblock's lanes have
+          // left) quantizes both rows to 0: no rate, no non-zeros, sq = +-0
+          // and vq - sq == vq (a -0 becomes +0: e * e is +0 for either)
+          const f2 e = vq * f2{sd[kk], sd[kk + 1]};
+          cp = fmaf(e.x, e.x, cp);
+          cp = fmaf(e.y, e.y, cp);
+          continue;
+        }
+      }
       float sqs[2], qfs[2];
 #pragma unroll
       for (int h = 0; h < 2; h++) {
@@ -1194,6 +1243,11 @@ void dump_merge_profile() {
     std::fprintf(stderr, "  %dx%d %8.1f %8.1f %8.1f %8.1f %8.1f\n", 8 << kShapes[si].lcy,
                  8 << kShapes[si].lcx, h[si][5] / 1e6, h[si][1] / 1e6, h[si][2] / 1e6,
                  h[si][3] / 1e6, h[si][4] / 1e6);
+  unsigned long long z[3][2];
+  if (hipMemcpyFromSymbol(z, HIP_SYMBOL(g_mzero), sizeof(z)) != hipSuccess) return;
+  for (int c = 0; c < 3; c++)
+    std::fprintf(stderr, "quant_pass zero votes, channel %c: %llu of %llu row pairs\n", "XYB"[c],
+                 z[c][1], z[c][0]);
 }
 #else
 void dump_merge_profile() {}
