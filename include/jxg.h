@@ -550,7 +550,7 @@ typedef struct {
   float ms_upload;   /* host variant: the image's upload (host wall clock) */
   float ms_encode;   /* device time by events, summed over points: frame start -> emission */
   float ms_recon;    /*   reconstruction chain incl. the fused colour + error kernel */
-  float ms_metrics;  /*   SSIM (or MS-SSIM) kernels and the results' download */
+  float ms_metrics;  /*   SSIM (or MS-SSIM) kernels, the strategy reduction, the results' download */
 } jxg_sweep_stats;
 jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats);
 /* MS-SSIM in a sweep.  With the switch on (default 0; JXG_ERR_INVALID_ARG
@@ -568,6 +568,56 @@ jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats);
  * not compute them or n is not that sweep's. */
 jxg_status jxg_set_sweep_msssim(jxg_ctx* ctx, int on);
 jxg_status jxg_sweep_msssim(jxg_ctx* ctx, jxg_msssim* out, uint32_t n);
+
+/* ---- per-strategy statistics of an encode ----
+ * How the frame's area, surviving coefficients, quantizer and squared error
+ * split over the AC strategies the encoder chose: one row per raw AcStrategy
+ * id.  A block belongs to the strategy of the varblock that covers it (the
+ * low 7 bits of its ac_strategy byte; bit 7 marks a covered non-first block).
+ * Every field is an exact integer sum, reduced on the GPU from the buffers of
+ * the encode (csrc/jxg_report.hip): the rows add up to the frame's blocks,
+ * xsize * ysize pixels and jxg_compare_rgb8's sse. */
+#define JXG_NUM_STRATEGIES 27            /* raw AcStrategy ids 0..26; AFV 14..17 and
+                                            the ids the encoder never emits stay zero */
+typedef struct {
+  uint64_t varblocks;    /* varblocks of this strategy (first blocks) */
+  uint64_t blocks;       /* 8x8 blocks they cover */
+  uint64_t pixels;       /* image pixels inside those blocks (edge blocks cropped to xsize, ysize) */
+  uint64_t nonzeros[3];  /* non-zero quantized AC coefficients, X / Y / B (entries of jxg_stats' ac) */
+  uint64_t qf_sum;       /* sum over covered blocks of the raw quant field (stored value + 1) */
+  uint64_t sse;          /* sum of squared RGB8 sample differences, decoded vs original, over `pixels` */
+} jxg_strategy_row;      /* 64 bytes */
+typedef struct { jxg_strategy_row row[JXG_NUM_STRATEGIES]; } jxg_strategy_report;
+/* The report of the context's last one-at-a-time encode against orig / d_orig
+ * (xsize x ysize RGB8, rows of orig_stride bytes): the reconstruction chain of
+ * jxg_reconstruct_rgb8 runs into scratch and ends in a kernel that compares
+ * each decoded pixel -- exactly the pixels jxg_reconstruct_rgb8 returns --
+ * with the original's and keeps one sum per 8x8 block; one reduction over the
+ * blocks then fills the table.  block_sse (host memory; d_block_sse device
+ * memory; may be NULL) receives that map, [ysize_blocks][xsize_blocks] u32:
+ * the squared error of the block's image pixels over the three channels.
+ * Nothing the encoder reads is modified.  Both calls return when the results
+ * are complete.  JXG_ERR_INVALID_ARG where jxg_reconstruct_rgb8 gives it (no
+ * one-at-a-time encode was the context's last use of its buffers, streamed
+ * frames pending), for a null orig / out and for orig_stride < 3 * xsize. */
+jxg_status jxg_strategy_report_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
+                                    jxg_strategy_report* out, uint32_t* block_sse);
+jxg_status jxg_strategy_report_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
+                                           jxg_strategy_report* out, uint32_t* d_block_sse);
+/* Reports in a sweep.  With the switch on (default 0; JXG_ERR_INVALID_ARG
+ * while streamed frames are pending) every sweep of quality 1 or 2 also fills
+ * one report per point on its lane: the chain ends in the block-map form of
+ * the fused colour + error kernel and the reduction follows the metrics.
+ * Codestreams, q[] and the MS-SSIM results are unchanged, ms_metrics includes
+ * the reduction, and sweeps with the switch off launch what they launched
+ * before.  jxg_sweep_report copies the last sweep's reports out in point
+ * order, each bit-equal to jxg_strategy_report_rgb8_device after a
+ * one-at-a-time encode with that point (a refused point zero-filled; block
+ * maps are not kept); JXG_ERR_INVALID_ARG when the last sweep computed none
+ * (switch off, or quality 0), when n is not that sweep's, or while streamed
+ * frames are pending. */
+jxg_status jxg_set_sweep_report(jxg_ctx* ctx, int on);
+jxg_status jxg_sweep_report(jxg_ctx* ctx, jxg_strategy_report* out, uint32_t n);
 
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result

@@ -470,6 +470,41 @@ jxg_status jxg_sweep_msssim(jxg_ctx* ctx, jxg_msssim* out, uint32_t n) {
   return JXG_OK;
 }
 
+jxg_status jxg_set_sweep_report(jxg_ctx* ctx, int on) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->sw.report = on != 0;
+  return JXG_OK;
+}
+
+jxg_status jxg_sweep_report(jxg_ctx* ctx, jxg_strategy_report* out, uint32_t n) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+  const Ctx::Sweep& sw = c->sw;
+  if (pipe_busy(c) || !sw.rep_have || n != sw.rep.size()) return JXG_ERR_INVALID_ARG;
+  std::copy(sw.rep.begin(), sw.rep.end(), out);
+  return JXG_OK;
+}
+
+jxg_status jxg_strategy_report_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
+                                    jxg_strategy_report* out, uint32_t* block_sse) {
+  if (!ctx || !orig || !out) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : strategy_report_last(c, orig, orig_stride, false, out, block_sse);
+}
+
+jxg_status jxg_strategy_report_rgb8_device(jxg_ctx* ctx, const void* d_orig, size_t orig_stride,
+                                           jxg_strategy_report* out, uint32_t* d_block_sse) {
+  if (!ctx || !d_orig || !out) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st
+            : strategy_report_last(c, static_cast<const uint8_t*>(d_orig), orig_stride, true, out,
+                                   d_block_sse);
+}
+
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
   Ctx* c;

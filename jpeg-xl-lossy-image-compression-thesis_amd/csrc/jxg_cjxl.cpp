@@ -196,6 +196,59 @@ std::string rust_f64(double v) {
   return std::string(buf, r.ptr);
 }
 
+std::string rust_f32(float v) {
+  char buf[200];
+  const auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::fixed);
+  return std::string(buf, r.ptr);
+}
+
+// --jxg_report=FILE.csv: the rows of jxg/harness.py strategy_stats /
+// write_strategy_stats for one encode -- one per non-empty strategy of the
+// report, appended; the header goes only into a missing or empty file
+const char* const kStrategyNames[JXG_NUM_STRATEGIES] = {
+    "DCT8", "IDENTITY", "DCT2X2", "DCT4X4", "DCT16X16", "DCT32X32", "DCT16X8", "DCT8X16",
+    "DCT32X8", "DCT8X32", "DCT32X16", "DCT16X32", "DCT4X8", "DCT8X4", "AFV0", "AFV1", "AFV2",
+    "AFV3", "DCT64X64", "DCT64X32", "DCT32X64", "DCT128X128", "DCT128X64", "DCT64X128",
+    "DCT256X256", "DCT256X128", "DCT128X256"};
+std::string csv_field(const std::string& v) {  // (Python's csv module, minimal quoting)
+  if (v.find_first_of(",\"\r\n") == std::string::npos) return v;
+  std::string q = "\"";
+  for (char ch : v) {
+    if (ch == '"') q += '"';
+    q += ch;
+  }
+  return q + "\"";
+}
+bool write_report_rows(const char* path, const std::string& orig_name,
+                       const std::string& comp_name, float distance, int effort,
+                       const jxg_strategy_report& rep, uint32_t w, uint32_t h) {
+  std::error_code ec;
+  const auto size = std::filesystem::file_size(path, ec);
+  const bool header = ec || size == 0;
+  FILE* f = std::fopen(path, header ? "w" : "a");
+  if (!f) return false;
+  if (header)
+    std::fputs("Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
+               "Varblocks,Blocks,Pixels,Area Share,Nonzeros X,Nonzeros Y,Nonzeros B,"
+               "Mean Quant Field,SSE,MSE\n", f);
+  for (int i = 0; i < JXG_NUM_STRATEGIES; i++) {
+    const jxg_strategy_row& r = rep.row[i];
+    if (!r.blocks) continue;
+    std::fprintf(f, "%s,%s,%s,%d,%d,%s,%llu,%llu,%llu,%s,%llu,%llu,%llu,%s,%llu,%s\n",
+                 csv_field(orig_name).c_str(), csv_field(comp_name).c_str(),
+                 rust_f32(distance).c_str(), effort, i, kStrategyNames[i],
+                 (unsigned long long)r.varblocks, (unsigned long long)r.blocks,
+                 (unsigned long long)r.pixels,
+                 rust_f64((double)r.pixels / ((double)w * (double)h)).c_str(),
+                 (unsigned long long)r.nonzeros[0], (unsigned long long)r.nonzeros[1],
+                 (unsigned long long)r.nonzeros[2],
+                 rust_f64((double)r.qf_sum / (double)r.blocks).c_str(),
+                 (unsigned long long)r.sse,
+                 rust_f64((double)r.sse / (3.0 * (double)r.pixels)).c_str());
+  }
+  return std::fclose(f) == 0;
+}
+
 struct SweepLine {
   double distance;
   int effort;
@@ -219,21 +272,31 @@ bool read_sweep_list(const char* path, std::vector<SweepLine>& out) {
 // INPUT at every point of the list -> OUTDIR/<stem>-<distance>-<effort>.jxl
 int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* outdir,
               const std::vector<SweepLine>& list, const std::vector<uint8_t>& rgb, uint32_t w,
-              uint32_t h) {
+              uint32_t h, const char* report_path) {
   const size_t n = list.size();
   std::vector<jxg_sweep_point> pts(n);
   for (size_t i = 0; i < n; i++)
     pts[i] = jxg_sweep_point{(float)list[i].distance, list[i].effort, p.proposals, p.flags};
   std::vector<jxg_buffer> outs(n, jxg_buffer{nullptr, 0});
   std::vector<jxg_status> sts(n, JXG_OK);
+  // with a report the points' chains run (quality 1) and end in the reduction
+  std::vector<jxg_quality> qs(report_path ? n : 0);
+  std::vector<jxg_strategy_report> reps(report_path ? n : 0);
+  if (report_path && jxg_set_sweep_report(ctx, 1) != JXG_OK) return 1;
   const auto t0 = std::chrono::steady_clock::now();
-  const jxg_status st = jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(),
-                                       (uint32_t)n, 0, outs.data(), nullptr, sts.data());
+  const jxg_status st =
+      jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(), (uint32_t)n,
+                     report_path ? 1 : 0, outs.data(), report_path ? qs.data() : nullptr,
+                     sts.data());
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   bool any = false;
   for (size_t i = 0; i < n; i++) any = any || outs[i].data;
   if (st != JXG_OK && !any) {
     std::fprintf(stderr, "sweep failed: %s\n", jxg_status_str(st));
+    return 1;
+  }
+  if (report_path && jxg_sweep_report(ctx, reps.data(), (uint32_t)n) != JXG_OK) {
+    std::fprintf(stderr, "sweep report failed\n");
     return 1;
   }
   std::error_code ec;
@@ -247,9 +310,15 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
       rc = 1;
       continue;
     }
-    const std::string path = (std::filesystem::path(outdir) /
-                              (stem + "-" + rust_f64(list[i].distance) + "-" +
-                               std::to_string(list[i].effort) + ".jxl")).string();
+    const std::string name =
+        stem + "-" + rust_f64(list[i].distance) + "-" + std::to_string(list[i].effort) + ".jxl";
+    const std::string path = (std::filesystem::path(outdir) / name).string();
+    if (report_path &&
+        !write_report_rows(report_path, std::filesystem::path(input).filename().string(), name,
+                           pts[i].distance, pts[i].effort, reps[i], w, h)) {
+      std::fprintf(stderr, "cannot write %s\n", report_path);
+      rc = 1;
+    }
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f || std::fwrite(outs[i].data, 1, outs[i].size, f) != outs[i].size) {
       std::fprintf(stderr, "cannot write %s\n", path.c_str());
@@ -272,7 +341,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr,
                  "usage: %s INPUT OUTPUT [--distance=D] [--effort=E] "
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
-                 "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH]\n"
+                 "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH] "
+                 "[--jxg_report=FILE.csv]\n"
                  "       %s INPUT OUTDIR --sweep=LIST [the same flags]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
@@ -287,6 +357,9 @@ int main(int argc, char** argv) {
   // codestream, reconstructed on the GPU (jxg_reconstruct_rgb8), as a binary PPM
   const char* recon_path = nullptr;
   const char* sweep_path = nullptr;  // --sweep=LIST: OUTPUT is a directory
+  // --jxg_report=FILE.csv (not a cjxl option): append the per-strategy
+  // statistics of the encode, or of every point of --sweep= (jxg_strategy_report_rgb8)
+  const char* report_path = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -330,6 +403,8 @@ int main(int argc, char** argv) {
       recon_path = a + 12;
     else if (!std::strncmp(a, "--sweep=", 8))
       sweep_path = a + 8;
+    else if (!std::strncmp(a, "--jxg_report=", 13))
+      report_path = a + 13;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -412,7 +487,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (sweep_path) {
-    const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h);
+    const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h, report_path);
     std::fflush(nullptr);
     std::_Exit(rc);  // (as below: no exit-time teardown)
   }
@@ -448,6 +523,20 @@ int main(int argc, char** argv) {
     if (r) std::fclose(r);
     if (!wr) {
       std::fprintf(stderr, "cannot write %s\n", recon_path);
+      return fail(1);
+    }
+  }
+  if (report_path) {
+    jxg_strategy_report rep{};
+    st = jxg_strategy_report_rgb8(ctx, rgb.data(), (size_t)w * 3, &rep, nullptr);
+    if (st != JXG_OK) {
+      std::fprintf(stderr, "strategy report failed: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    if (!write_report_rows(report_path, std::filesystem::path(argv[1]).filename().string(),
+                           std::filesystem::path(argv[2]).filename().string(), p.distance,
+                           p.effort, rep, w, h)) {
+      std::fprintf(stderr, "cannot write %s\n", report_path);
       return fail(1);
     }
   }

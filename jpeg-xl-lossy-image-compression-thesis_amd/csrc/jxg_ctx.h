@@ -167,6 +167,10 @@ struct Ctx : EncArenas {
     // ten window sums; allocated by the first use
     DevBuf<float> pyr_o, pyr_c;
     DevBuf<double> ms_part, ms_out;
+    // strategy report (jxg_strategy_report_rgb8, a sweep's lane): the block
+    // error map of the chain's last kernel and the 27 x 8 table
+    DevBuf<uint32_t> bsse;
+    DevBuf<uint64_t> rep;
   } q;
   // decode-side reconstruction (jxg_reconstruct_rgb8; jxg_reconstruct.cpp),
   // allocated by its first call: tables, two sets of three block-padded f32
@@ -226,6 +230,12 @@ struct Ctx : EncArenas {
     PinBuf<double> h_ms;
     std::vector<jxg_msssim> ms;
     bool ms_have = false;  // the last sweep computed `ms`
+    // with jxg_set_sweep_report: the points' pinned tables [n][27 * 8], the
+    // last sweep's reports in point order
+    bool report = false;  // the switch
+    PinBuf<uint64_t> h_rep;
+    std::vector<jxg_strategy_report> rep;
+    bool rep_have = false;  // the last sweep computed `rep`
   } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
@@ -373,6 +383,9 @@ struct SweepReq {
   double* h_ms = nullptr;
   const float* pyr_o = nullptr;
   hipEvent_t ev_pyr = nullptr;
+  // strategy report behind the metrics (quality 1 / 2 with the switch on):
+  // pinned [kReportCells] table
+  uint64_t* h_rep = nullptr;
 };
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                        size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
@@ -458,6 +471,7 @@ struct ReconSse {
   size_t orig_stride;
   uint64_t* sse;        // device, zeroed on the stream before
   bool store;
+  uint32_t* block_sse = nullptr;  // device [bys][bxs] squared error per 8x8 block, or null
 };
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
                               size_t stride, const ReconSse* q = nullptr);
@@ -465,6 +479,14 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, u
 ReconFrame recon_frame_of_encode(uint32_t w, uint32_t h, const jxg_params& P);
 // the last one-at-a-time encode's decoded image, into device / host memory
 jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_device);
+
+// the strategy report of the last one-at-a-time encode: the
+// chain above with the block-map ending into scratch, then the reduction of
+// jxg_report.hip; block_sse (host or device as orig, may be null): the map
+jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device,
+                                jxg_strategy_report* out, uint32_t* block_sse);
+// the reduction alone, enqueued on c's stream: c->q.bsse -> c->q.rep (cleared first)
+jxg_status strategy_report_enqueue(Ctx* c, uint32_t w, uint32_t h);
 
 // ---- jxg_decode_dev.cpp ----
 jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, size_t row_stride,

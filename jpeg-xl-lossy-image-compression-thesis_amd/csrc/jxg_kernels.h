@@ -406,8 +406,25 @@ hipError_t launch_recon_colour(const ReconArgs& a, const float* src, hipStream_t
 // the same conversion fused with the squared error against the original
 // (orig: RGB8 rows of orig_stride bytes; *sse pre-zeroed, the exact integer sum
 // launch_metrics gives for the stored image); store: RGB8 also written to a.rgb
+// block_sse: also one u32 per 8x8 block, [bys][bxs], the squared error of the
+// block's image pixels (every word written; the strategy report's form)
 hipError_t launch_recon_colour_sse(const ReconArgs& a, const float* src, const uint8_t* orig,
-                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s);
+                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s,
+                                   uint32_t* block_sse = nullptr);
+// per-strategy statistics (jxg_report.hip): the table is
+// jxg_strategy_report as u64 cells [27 raw ids][8: varblocks, blocks, pixels,
+// non-zeros X / Y / B, quant-field sum, squared error], added into (pre-zeroed)
+constexpr uint32_t kReportStrategies = 27, kReportCols = 8,
+                   kReportCells = kReportStrategies * kReportCols;
+struct ReportArgs {
+  const uint8_t* acs;         // [nb] raw strategy, bit 7 on covered non-first blocks
+  const uint8_t* qf;          // [nb] raw - 1
+  const int16_t* ac;          // [nb][3][64], 16-byte aligned
+  const uint32_t* block_sse;  // [nb] (launch_recon_colour_sse)
+  uint32_t w, h, bxs, nb;
+  unsigned long long* table;  // [kReportCells]
+};
+hipError_t launch_strategy_report(const ReportArgs& a, hipStream_t s);
 // the decoder's pass groups (jxg_decode.hip): one wave per
 // group walks its section of the codestream with the decode core and writes
 // the non-zero coefficients into `ac` (it zeroes the group's area first)

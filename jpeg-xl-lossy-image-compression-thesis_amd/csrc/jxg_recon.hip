@@ -27,6 +27,8 @@
 //   recon_colour_sse_kernel  the same conversion fused with the squared error
 //                        against the original (jxg_sweep_rgb8); stores RGB8
 //                        only for SSIM.
+//   recon_colour_sse_map_kernel  the same, and one squared-error word per 8x8
+//                        block (the strategy report).
 // The last kernel of the chain writes RGB8 cropped to the image size.
 #include <algorithm>
 
@@ -591,10 +593,70 @@ __global__ __launch_bounds__(256) void recon_colour_sse_kernel(ReconArgs a, cons
   if (threadIdx.x == 0) atomicAdd(sse, (unsigned long long)(sW[0] + sW[1] + sW[2] + sW[3]));
 }
 
+// the form that keeps the block structure (strategy report):
+// the same conversion and comparison, and beside the frame's sum one u32 per
+// 8x8 block (image pixels only).  Workgroup = 64 columns (8 blocks) x 4 waves;
+// a wave takes a block row at a time, striding down the image, and adds its 8
+// pixel rows in a register; the 8 lanes of a block then reduce by shuffles and
+// the first of them stores the block's word (its column is inside the image
+// exactly when the block exists).  Lanes past the image add nothing and stay
+// for the shuffles.  Integer sums: the frame total is the other forms' u64.
+template <bool kStore>
+__global__ __launch_bounds__(256) void recon_colour_sse_map_kernel(ReconArgs a, const float* src,
+                                                                   const uint8_t* orig, size_t so,
+                                                                   unsigned long long* sse,
+                                                                   uint32_t* bmap) {
+  __shared__ uint64_t sW[4];
+  const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const size_t plane = (size_t)a.xp * a.yp;
+  uint64_t acc = 0;
+  for (uint32_t by = blockIdx.y * 4 + (threadIdx.x >> 6); by < a.bys; by += gridDim.y * 4) {
+    uint32_t blk = 0;
+    if (x < a.w) {
+      const uint32_t y1 = min(by * 8 + 8, a.h);
+      for (uint32_t y = by * 8; y < y1; y++) {
+        const size_t g = (size_t)y * a.xp + x;
+        uint8_t v[3];
+        rc_xyb_to_rgb8(a, src[g], src[plane + g], src[2 * plane + g], v);
+        const uint8_t* p = orig + (size_t)y * so + (size_t)x * 3;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const int d = (int)p[c] - (int)v[c];
+          blk += (uint32_t)(d * d);
+        }
+        if (kStore) {
+          uint8_t* o = a.rgb + (size_t)y * a.stride + (size_t)x * 3;
+          o[0] = v[0];
+          o[1] = v[1];
+          o[2] = v[2];
+        }
+      }
+    }
+    acc += blk;
+    for (int o = 1; o < 8; o <<= 1) blk += __shfl_xor(blk, o, 64);
+    if ((threadIdx.x & 7) == 0 && x < a.w) bmap[(size_t)by * a.bxs + (x >> 3)] = blk;
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(sse, (unsigned long long)(sW[0] + sW[1] + sW[2] + sW[3]));
+}
+
 hipError_t launch_recon_colour_sse(const ReconArgs& a, const float* src, const uint8_t* orig,
-                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s) {
-  const dim3 grid((a.w + 63) / 64, std::min((a.h + 3) / 4, kRcSseRows));
+                                   size_t orig_stride, uint64_t* sse, bool store, hipStream_t s,
+                                   uint32_t* block_sse) {
   unsigned long long* out = reinterpret_cast<unsigned long long*>(sse);
+  if (block_sse) {
+    const dim3 bgrid((a.w + 63) / 64, std::min((a.bys + 3) / 4, kRcSseRows));
+    if (store)
+      recon_colour_sse_map_kernel<true>
+          <<<bgrid, 256, 0, s>>>(a, src, orig, orig_stride, out, block_sse);
+    else
+      recon_colour_sse_map_kernel<false>
+          <<<bgrid, 256, 0, s>>>(a, src, orig, orig_stride, out, block_sse);
+    return hipGetLastError();
+  }
+  const dim3 grid((a.w + 63) / 64, std::min((a.h + 3) / 4, kRcSseRows));
   if (store)
     recon_colour_sse_kernel<true><<<grid, 256, 0, s>>>(a, src, orig, orig_stride, out);
   else

@@ -140,7 +140,8 @@ jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, u
     std::swap(src, dst);
   }
   if (q) {  // (enqueued only: the caller orders itself after the stream)
-    JXG_HIP(launch_recon_colour_sse(a, src, q->orig, q->orig_stride, q->sse, q->store, s));
+    JXG_HIP(launch_recon_colour_sse(a, src, q->orig, q->orig_stride, q->sse, q->store, s,
+                                    q->block_sse));
     return JXG_OK;
   }
   JXG_HIP(hipStreamSynchronize(s));
@@ -163,6 +164,52 @@ jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_dev
   JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc.rgb.p, row, row, c->rc.h,
                            hipMemcpyDeviceToHost, c->stream));
   JXG_HIP(hipStreamSynchronize(c->stream));
+  return JXG_OK;
+}
+
+jxg_status strategy_report_enqueue(Ctx* c, uint32_t w, uint32_t h) {
+  const Frame f = make_frame(w, h, 1.0f);
+  JXG_HIP(c->q.rep.ensure(kReportCells));
+  JXG_HIP(hipMemsetAsync(c->q.rep.p, 0, kReportCells * sizeof(uint64_t), c->stream));
+  const ReportArgs a{c->acs.p, c->qf.p, c->ac.p, c->q.bsse.p, w, h, f.bxs, f.bxs * f.bys,
+                     reinterpret_cast<unsigned long long*>(c->q.rep.p)};
+  JXG_HIP(launch_strategy_report(a, c->stream));
+  return JXG_OK;
+}
+
+jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device,
+                                jxg_strategy_report* out, uint32_t* block_sse) {
+  const uint32_t w = c->rc.w, h = c->rc.h;
+  if (!c->rc.ok || orig_stride < (size_t)w * 3) return JXG_ERR_INVALID_ARG;
+  hipStream_t s = c->stream;
+  const Frame f = make_frame(w, h, 1.0f);
+  const size_t nb = (size_t)f.bxs * f.bys;
+  const uint8_t* d_orig = orig;
+  size_t so = orig_stride;
+  if (on_device) {
+    const jxg_status st = order_input(c, c);
+    if (st) return st;
+  } else {
+    so = (size_t)w * 3;
+    JXG_HIP(c->q.orig.ensure(so * h));
+    JXG_HIP(hipMemcpy2DAsync(c->q.orig.p, so, orig, orig_stride, so, h, hipMemcpyHostToDevice, s));
+    d_orig = c->q.orig.p;
+  }
+  JXG_HIP(c->q.sse.ensure(1));
+  JXG_HIP(c->q.bsse.ensure(nb));
+  JXG_HIP(hipMemsetAsync(c->q.sse.p, 0, sizeof(uint64_t), s));
+  const ReconSse e{d_orig, so, c->q.sse.p, false, c->q.bsse.p};
+  jxg_status st = reconstruct_device(c, recon_frame_of_encode(w, h, c->params),
+                                     ReconMaps{c->acs.p, c->qf.p, c->dc.p, c->ac.p, c->cmap.p},
+                                     nullptr, so, &e);
+  if (!st) st = strategy_report_enqueue(c, w, h);
+  if (st) return st;
+  static_assert(sizeof(jxg_strategy_report) == kReportCells * sizeof(uint64_t), "table layout");
+  JXG_HIP(hipMemcpyAsync(out, c->q.rep.p, sizeof(*out), hipMemcpyDeviceToHost, s));
+  if (block_sse)
+    JXG_HIP(hipMemcpyAsync(block_sse, c->q.bsse.p, nb * sizeof(uint32_t),
+                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+  JXG_HIP(hipStreamSynchronize(s));
   return JXG_OK;
 }
 

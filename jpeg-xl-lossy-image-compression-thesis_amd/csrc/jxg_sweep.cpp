@@ -12,6 +12,9 @@
 // pyramid of its decoded image and the MS-SSIM kernels
 // against the original's pyramid, which the context built once on its own
 // stream; their scale 0 is the SSIM.
+// With jxg_set_sweep_report the chain ends in the kernel that also writes the
+// block error map, and the strategy reduction (jxg_report.hip, DESIGN.md
+// §3.16) follows the metrics; its table is a third pinned result.
 #include <cmath>
 #include <cstring>
 
@@ -34,9 +37,10 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(q.part.ensure(np));
     JXG_HIP(S->rc.rgb.ensure(row * h));
   }
+  if (rq.h_rep) JXG_HIP(q.bsse.ensure((size_t)((w + 7) / 8) * ((h + 7) / 8)));
   JXG_HIP(hipMemsetAsync(q.sse.p, 0, sizeof(uint64_t), s));
   JXG_HIP(hipEventRecord(rq.ev[0], s));
-  const ReconSse e{d_orig, so, q.sse.p, ssim};
+  const ReconSse e{d_orig, so, q.sse.p, ssim, rq.h_rep ? q.bsse.p : nullptr};
   const jxg_status st = reconstruct_device(
       S, recon_frame_of_encode(w, h, S->params),
       ReconMaps{S->acs.p, S->qf.p, S->dc.p, S->ac.p, S->cmap.p}, ssim ? S->rc.rgb.p : nullptr, row,
@@ -67,6 +71,12 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(hipMemcpyAsync(rq.h_ms, q.ms_out.p, 2 * kMsScales * sizeof(double),
                            hipMemcpyDeviceToHost, s));
     JXG_HIP(hipMemcpyAsync(rq.h_q + 1, q.ms_out.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (rq.h_rep) {
+    const jxg_status sr = strategy_report_enqueue(S, w, h);
+    if (sr) return sr;
+    JXG_HIP(hipMemcpyAsync(rq.h_rep, q.rep.p, kReportCells * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s));
   }
   JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   JXG_HIP(hipEventRecord(rq.ev[2], s));
@@ -108,6 +118,11 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.ms_have = false;
   sw.ms.clear();
   if (ms) sw.ms.assign(n, jxg_msssim{});
+  // the strategy reports ride on quality 1 / 2 (jxg_set_sweep_report)
+  const bool report = quality != 0 && sw.report;
+  sw.rep_have = false;
+  sw.rep.clear();
+  if (report) sw.rep.assign(n, jxg_strategy_report{});
   // the context is lane 0 and encodes with its frames' points: its own
   // parameters are put back however the call ends
   const jxg_params saved = c->params;
@@ -127,6 +142,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     }
     sw.stats.ms_call = ms_since(t0);
     sw.ms.clear();
+    sw.rep.clear();
     return e;
   };
   if (nv) {
@@ -149,6 +165,8 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         sw.ev.push_back(e);
       }
     }
+    if (report && sw.h_rep.ensure((size_t)nv * kReportCells) != hipSuccess)
+      return fail(JXG_ERR_OOM);
     if (ms_run) {  // the original's pyramid, once: every lane reads it after ev_pyr
       if (sw.h_ms.ensure((size_t)nv * 2 * kMsScales) != hipSuccess ||
           sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess)
@@ -186,6 +204,8 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         msssim_result(w, h, sw.h_ms.p + (size_t)k * 2 * kMsScales, &sw.ms[i]);
       else if (ms)
         msssim_nan(&sw.ms[i]);
+      if (report)
+        std::memcpy(&sw.rep[i], sw.h_rep.p + (size_t)k * kReportCells, sizeof(sw.rep[i]));
       sw.stats.ms_recon += elapsed(sw.ev[3 * k], sw.ev[3 * k + 1]);
       sw.stats.ms_metrics += elapsed(sw.ev[3 * k + 1], sw.ev[3 * k + 2]);
     };
@@ -206,6 +226,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.pyr_o = sw.pyr_o.p;
         rq.ev_pyr = sw.ev_pyr;
       }
+      if (report) rq.h_rep = sw.h_rep.p + (size_t)k * kReportCells;
       e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
       // completed points whose copies have landed (or when more than two wait)
       while (!e && pipe_done_ready(c)) take();
@@ -218,6 +239,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.stats.lanes = pipe_shape(f.ngroups, f.tiles_x * f.tiles_y, c->lane_cap, hw_queues()).lanes;
   if (statuses) std::copy(st.begin(), st.end(), statuses);
   sw.ms_have = ms;
+  sw.rep_have = report;
   sw.stats.ms_call = ms_since(t0);
   return first;
 }

@@ -104,6 +104,33 @@ class _Msssim(ctypes.Structure):
                 "ssim": [float(v) for v in self.ssim]}
 
 
+NUM_STRATEGIES = 27
+# the project's names of the raw AcStrategy ids 0..26 (rows x columns in pixels;
+# the encoder never emits AFV0..3)
+STRATEGY_NAMES = (
+    "DCT8", "IDENTITY", "DCT2X2", "DCT4X4", "DCT16X16", "DCT32X32", "DCT16X8", "DCT8X16",
+    "DCT32X8", "DCT8X32", "DCT32X16", "DCT16X32", "DCT4X8", "DCT8X4", "AFV0", "AFV1", "AFV2",
+    "AFV3", "DCT64X64", "DCT64X32", "DCT32X64", "DCT128X128", "DCT128X64", "DCT64X128",
+    "DCT256X256", "DCT256X128", "DCT128X256")
+
+
+class _StrategyRow(ctypes.Structure):
+    _fields_ = [("varblocks", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("pixels", ctypes.c_uint64), ("nonzeros", ctypes.c_uint64 * 3),
+                ("qf_sum", ctypes.c_uint64), ("sse", ctypes.c_uint64)]
+
+
+class _StrategyReport(ctypes.Structure):
+    _fields_ = [("row", _StrategyRow * NUM_STRATEGIES)]
+
+    def as_dict(self) -> dict:
+        """numpy arrays keyed by field name ([27] uint64, nonzeros [27, 3]) + names"""
+        t = np.frombuffer(bytes(self), dtype=np.uint64).reshape(NUM_STRATEGIES, 8)
+        return {"varblocks": t[:, 0].copy(), "blocks": t[:, 1].copy(), "pixels": t[:, 2].copy(),
+                "nonzeros": t[:, 3:6].copy(), "qf_sum": t[:, 6].copy(), "sse": t[:, 7].copy(),
+                "names": STRATEGY_NAMES}
+
+
 class _SweepPoint(ctypes.Structure):
     _fields_ = [("distance", ctypes.c_float), ("effort", ctypes.c_int),
                 ("proposals", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -134,6 +161,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_sweep_rgb8", "jxg_sweep_rgb8_device", "jxg_sweep_timings",
            "jxg_msssim_rgb8", "jxg_msssim_rgb8_device", "jxg_set_sweep_msssim",
            "jxg_sweep_msssim",
+           "jxg_strategy_report_rgb8", "jxg_strategy_report_rgb8_device",
+           "jxg_set_sweep_report", "jxg_sweep_report",
 )
 
 _lib = None
@@ -231,6 +260,11 @@ def load():
     lib.jxg_msssim_rgb8_device.argtypes = ms_args
     lib.jxg_set_sweep_msssim.argtypes = [vp, ctypes.c_int]
     lib.jxg_sweep_msssim.argtypes = [vp, ctypes.POINTER(_Msssim), ctypes.c_uint32]
+    rep_args = [vp, vp, sz, ctypes.POINTER(_StrategyReport), vp]
+    lib.jxg_strategy_report_rgb8.argtypes = rep_args
+    lib.jxg_strategy_report_rgb8_device.argtypes = rep_args
+    lib.jxg_set_sweep_report.argtypes = [vp, ctypes.c_int]
+    lib.jxg_sweep_report.argtypes = [vp, ctypes.POINTER(_StrategyReport), ctypes.c_uint32]
     _lib = lib
     return lib
 
@@ -331,6 +365,44 @@ class Encoder:
         w, _ = self._last_wh or (1, 1)
         _check(load().jxg_reconstruct_rgb8_device(self._ctx, ctypes.c_void_p(ptr),
                                                   row_stride or w * 3))
+
+    def strategy_report(self, orig: np.ndarray, block_map: bool = False) -> dict:
+        """Per-strategy statistics of the frame last encoded with
+        :meth:`encode` / :meth:`encode_device` against ``orig``, the (H, W, 3)
+        uint8 image it was encoded from (jxg_strategy_report_rgb8): a dict of
+        ``[27]`` uint64 arrays indexed by raw AcStrategy id -- ``varblocks``,
+        ``blocks``, ``pixels``, ``nonzeros`` (``[27, 3]``: X, Y, B), ``qf_sum``,
+        ``sse`` -- and ``names``.  Exact integer sums, reduced on the GPU; the
+        squared error is against exactly the pixels :meth:`reconstruct`
+        returns.  ``block_map=True`` adds ``block_sse``, the ``(bys, bxs)``
+        uint32 squared error of every 8x8 block.  Raises JxgError where
+        :meth:`reconstruct` does."""
+        orig = np.ascontiguousarray(orig, dtype=np.uint8)
+        w, h = self._last_wh or (1, 1)
+        if orig.shape != (h, w, 3):
+            raise ValueError("orig must be the (H, W, 3) uint8 image of the last encode")
+        rep = _StrategyReport()
+        bmap = np.empty(((h + 7) // 8, (w + 7) // 8), dtype=np.uint32) if block_map else None
+        _check(load().jxg_strategy_report_rgb8(
+            self._ctx, orig.ctypes.data, w * 3, ctypes.byref(rep),
+            bmap.ctypes.data if block_map else None))
+        out = rep.as_dict()
+        if block_map:
+            out["block_sse"] = bmap
+        return out
+
+    def strategy_report_device(self, ptr: int, row_stride: int | None = None,
+                               block_map_ptr: int | None = None) -> dict:
+        """:meth:`strategy_report` against a device-resident original (rows of
+        ``row_stride`` bytes, default 3 * width); ``block_map_ptr``: device
+        memory for the ``(bys, bxs)`` uint32 block map
+        (jxg_strategy_report_rgb8_device)."""
+        w, _ = self._last_wh or (1, 1)
+        rep = _StrategyReport()
+        _check(load().jxg_strategy_report_rgb8_device(
+            self._ctx, ctypes.c_void_p(ptr), row_stride or w * 3, ctypes.byref(rep),
+            ctypes.c_void_p(block_map_ptr) if block_map_ptr else None))
+        return rep.as_dict()
 
     def decode(self, data: bytes) -> np.ndarray:
         """Codestream bytes -> (H, W, 3) uint8, decoded on the GPU
@@ -491,10 +563,12 @@ class Encoder:
                 pts.append(_SweepPoint(p[0], p[1], *(tuple(p[2:4]) + (0, 0))[:2]))
         return pts
 
-    def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict):
+    def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False):
         if quality not in self._QUALITY:
             raise ValueError("quality: 'msssim', 'ssim', 'psnr' or None")
         level = self._QUALITY[quality]
+        if strategies and not level:
+            raise ValueError("strategies ride on a sweep's quality chain: quality must not be None")
         ms = quality == "msssim"
         pts = self._sweep_points(points)
         n = len(pts)
@@ -504,11 +578,17 @@ class Encoder:
         outs = (_Buffer * n)()
         qs = (_Quality * n)() if level else None
         st = (ctypes.c_int * n)()
-        mss = None
+        mss = reps = None
         if ms:
             _check(load().jxg_set_sweep_msssim(self._ctx, 1))
         try:
+            if strategies:
+                _check(load().jxg_set_sweep_report(self._ctx, 1))
             ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
+            if strategies:
+                r = (_StrategyReport * n)()
+                if load().jxg_sweep_report(self._ctx, r, n) == 0:
+                    reps = r
             if ms:  # (a sweep that failed as a whole has none: ret is raised below)
                 m = (_Msssim * n)()
                 if load().jxg_sweep_msssim(self._ctx, m, n) == 0:
@@ -516,6 +596,8 @@ class Encoder:
         finally:
             if ms:
                 load().jxg_set_sweep_msssim(self._ctx, 0)
+            if strategies:
+                load().jxg_set_sweep_report(self._ctx, 0)
         st = [int(v) for v in st]
         if ret != 0 and (strict or self._batch_call_failed(ret, st)):
             for i in range(n):
@@ -532,10 +614,13 @@ class Encoder:
                 if mss is not None:
                     q["ms_ssim"] = float(mss[i].ms_ssim)
                     q["cs"] = [float(v) for v in mss[i].cs]
+                if reps is not None:
+                    q["strategies"] = reps[i].as_dict()
             res.append((self._take(outs[i]), q))
         return res
 
-    def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True) -> list:
+    def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True,
+              strategies: bool = False) -> list:
         """One host (H, W, 3) uint8 image encoded at every point of ``points``
         in one call (jxg_sweep_rgb8): the image is uploaded once and the points
         run through the streaming pipeline's lanes of this context, whose own
@@ -550,22 +635,26 @@ class Encoder:
         in point order, each equal to a fresh ``Encoder(**point)``'s
         ``encode`` / ``reconstruct_device`` / ``compare_device``.  Raises
         JxgError on the first refused point; with ``strict=False`` a refused
-        point comes back as ``(None, status)``.  Afterwards :meth:`reconstruct`
+        point comes back as ``(None, status)``.  ``strategies=True`` (not with
+        ``quality=None``): each point's dict gains ``"strategies"``, the
+        :meth:`strategy_report` of that point, reduced on its lane
+        (jxg_set_sweep_report).  Afterwards :meth:`reconstruct`
         raises until the next :meth:`encode`."""
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("expected (H, W, 3) uint8")
         h, w = rgb.shape[:2]
         return self._sweep_call(load().jxg_sweep_rgb8, rgb.ctypes.data, w, h, w * 3, points,
-                                quality, strict)
+                                quality, strict, strategies)
 
     def sweep_device(self, ptr: int, width: int, height: int, points, quality="ssim",
-                     strict: bool = True, row_stride: int | None = None) -> list:
+                     strict: bool = True, row_stride: int | None = None,
+                     strategies: bool = False) -> list:
         """:meth:`sweep` of a device-resident RGB8 image (rows of ``row_stride``
         bytes, default 3 * width), which must stay unchanged until the call
         returns (jxg_sweep_rgb8_device)."""
         return self._sweep_call(load().jxg_sweep_rgb8_device, ctypes.c_void_p(ptr), width, height,
-                                row_stride or width * 3, points, quality, strict)
+                                row_stride or width * 3, points, quality, strict, strategies)
 
     def sweep_timings(self) -> dict:
         """The last :meth:`sweep` (jxg_sweep_timings): points encoded, lanes,

@@ -24,6 +24,11 @@ Mirrors pscoro/JPEG-XL-Lossy-Image-Compression-Thesis benchmark-jpegxl:
 * ``file_size_ratio`` -- metrics.rs:15-26.
 * ``sweep_and_compare`` -- the per-image loop of benchmark.rs:637-677 (every
   distance x effort: encode, decode, compare) as one Encoder.sweep call.
+
+The project's own extension (no counterpart in the reference): ``StrategyStat``
+rows -- one per (image, point, non-empty AC strategy) from the GPU's strategy
+report (Encoder.strategy_report) -- in ``strategy_stats.csv``,
+and ``compare_strategy_stats``, their A/B difference.
 """
 import csv
 import os
@@ -137,6 +142,121 @@ def file_size_ratio(orig: int, comp: int, denom: str) -> float:
     if denom == "comp":
         return float(orig) / float(comp)
     raise ValueError("Invalid denominator for file size ratio")
+
+
+STRATEGY_HEADER = [
+    "Original Image Name", "Compressed Image Name", "Distance", "Effort", "Strategy", "Name",
+    "Varblocks", "Blocks", "Pixels", "Area Share", "Nonzeros X", "Nonzeros Y", "Nonzeros B",
+    "Mean Quant Field", "SSE", "MSE",
+]
+STRATEGY_DIFF_HEADER = STRATEGY_HEADER[:6] + ["Diff " + h for h in STRATEGY_HEADER[6:]]
+
+
+@dataclass
+class StrategyStat:
+    """One strategy of one encode: the report's row and what follows from it
+    (area share = pixels / image pixels, mean quant field = qf_sum / blocks,
+    MSE = SSE / (3 * pixels))."""
+    orig_image_name: str
+    comp_image_name: str
+    distance: float  # f32
+    effort: int
+    strategy: int
+    name: str
+    varblocks: int
+    blocks: int
+    pixels: int
+    area_share: float
+    nonzeros_x: int
+    nonzeros_y: int
+    nonzeros_b: int
+    mean_quant_field: float
+    sse: int
+    mse: float
+
+    _FLOATS = ("area_share", "mean_quant_field", "mse")
+
+    def row(self):
+        return [self.orig_image_name, self.comp_image_name, rust_f32(self.distance),
+                str(self.effort), str(self.strategy), self.name] + [
+                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
+                    else str(getattr(self, f.name)) for f in fields(self)[6:]]
+
+    @classmethod
+    def parse(cls, rec):
+        vals = [float(v) if f.name in cls._FLOATS else int(v)
+                for f, v in zip(fields(cls)[6:], rec[6:16])]
+        return cls(rec[0], rec[1], float(np.float32(rec[2])), int(rec[3]), int(rec[4]), rec[5],
+                   *vals)
+
+
+@dataclass
+class StrategyStatDiff:
+    orig_image_name: str
+    comp_image_name: str
+    distance: float
+    effort: int
+    strategy: int
+    name: str
+    diffs: list  # run 2 - run 1 of the ten value columns, f64
+
+    def row(self):
+        return [self.orig_image_name, self.comp_image_name, rust_f32(self.distance),
+                str(self.effort), str(self.strategy), self.name] + [rust_f64(v) for v in self.diffs]
+
+
+def strategy_stats(orig_name: str, comp_name: str, distance: float, effort: int, report: dict,
+                   width: int, height: int):
+    """The StrategyStat rows of one report (Encoder.strategy_report / a
+    sweep point's ``"strategies"``): its non-empty strategies in id order."""
+    rows = []
+    for i in range(len(report["blocks"])):
+        blocks, pixels = int(report["blocks"][i]), int(report["pixels"][i])
+        if blocks == 0:
+            continue
+        sse = int(report["sse"][i])
+        nz = [int(v) for v in report["nonzeros"][i]]
+        rows.append(StrategyStat(
+            orig_name, comp_name, float(np.float32(distance)), int(effort), i,
+            report["names"][i], int(report["varblocks"][i]), blocks, pixels,
+            float(pixels) / (float(width) * float(height)), nz[0], nz[1], nz[2],
+            float(int(report["qf_sum"][i])) / float(blocks), sse,
+            float(sse) / (3.0 * float(pixels))))
+    return rows
+
+
+def write_strategy_stats(rows, strategy_file: str) -> None:
+    write_csv_header(strategy_file, STRATEGY_HEADER)
+    write_csv(rows, strategy_file)
+
+
+def read_strategy_stats(file_name: str):
+    with open(file_name, newline="") as f:
+        rows = list(csv.reader(f))
+    return [StrategyStat.parse(r) for r in rows[1:] if r]
+
+
+def compare_strategy_stats(file_1: str, file_2: str):
+    """Run 2 - run 1 per (image, compressed name, distance, effort, strategy):
+    a strategy that only one run uses counts as zeros in the other.  Writes
+    ``strategy_diffs.csv`` next to file_1 and returns the rows, sorted by key."""
+    value_fields = [f.name for f in fields(StrategyStat)[6:]]
+
+    def keyed(path):
+        return {(r.orig_image_name, r.comp_image_name, r.distance, r.effort, r.strategy): r
+                for r in read_strategy_stats(path)}
+
+    a, b = keyed(file_1), keyed(file_2)
+    diffs = []
+    for k in sorted(set(a) | set(b)):
+        ra, rb = a.get(k), b.get(k)
+        vals = [float(getattr(rb, n) if rb else 0) - float(getattr(ra, n) if ra else 0)
+                for n in value_fields]
+        diffs.append(StrategyStatDiff(k[0], k[1], k[2], k[3], k[4], (ra or rb).name, vals))
+    diff_file = os.path.join(os.path.dirname(os.path.abspath(file_1)), "strategy_diffs.csv")
+    write_csv_header(diff_file, STRATEGY_DIFF_HEADER)
+    write_csv(diffs, diff_file)
+    return diffs
 
 
 _DIFF_FIELDS = [f.name for f in fields(ComparisonResult)[4:]]
@@ -260,7 +380,8 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
 
 
 def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
-                      result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False):
+                      result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False,
+                      strategy_file: str | None = None):
     """The harness's per-image loop (benchmark.rs:637-677) in one call: the
     image is encoded at every point (dicts with ``distance`` / ``effort`` and
     optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
@@ -271,7 +392,9 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     (codestreams, records); the records, and the CSV rows in point order, equal
     per-point :func:`encode_and_compare` on an encoder of those parameters.
     ``ms_ssim`` (needs ``ssim``): the MS-SSIM column from the points' lanes
-    (``quality="msssim"``)."""
+    (``quality="msssim"``).  ``strategy_file``: every point's strategy report
+    is reduced on its lane as well (``strategies=True``) and one StrategyStat
+    row per non-empty strategy is appended to that file (strategy_stats.csv)."""
     if ms_ssim and not ssim:
         raise ValueError("ms_ssim rides on the quality-2 sweep: it needs ssim=True")
     o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
@@ -279,7 +402,8 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
         raise ValueError("orig_rgb must be (H, W, 3) uint8")
     h, w = o.shape[:2]
     points = list(points)
-    res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr")
+    res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr",
+                        strategies=strategy_file is not None)
     stem = os.path.splitext(orig_name)[0]
     raw = w * h * 3
     datas, records = [], []
@@ -288,4 +412,7 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
         datas.append(data)
         records.append(_record(orig_name, comp_image_name(stem, d, e), d, e, orig_file_size,
                                len(data), raw, q, ssim, result_file))
+        if strategy_file is not None:
+            write_strategy_stats(strategy_stats(orig_name, comp_image_name(stem, d, e), d, e,
+                                                q["strategies"], w, h), strategy_file)
     return datas, records

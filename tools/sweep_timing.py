@@ -5,6 +5,7 @@ against the loop it replaces on the same build: one cached context per point,
 each doing encode + reconstruct_device + compare_device.
 
     python tools/sweep_timing.py [--reps 5] [--sizes 8k,768] [--queues N] [--cli]
+    python tools/sweep_timing.py --strategies [--reps 5] [--sizes 8k,768] [--queues N]
 
 Per frame size (the 8K synthetic frame and a 768 x 512 one), input (host /
 device) and quality level (0 none, 1 sse/psnr, 2 also ssim): warm contexts,
@@ -14,7 +15,12 @@ device memory one sweeping context holds next to the 50 cached ones.  --queues
 sets GPU_MAX_HW_QUEUES before HIP starts (the pipeline has queues - 1 lanes).
 --cli: `jxg_cjxl IN OUTDIR --sweep=LIST` of the grid against 50 plain jxg_cjxl
 processes.  Prints one JSON line per measurement; the outputs of sweep and loop
-are compared before anything is timed."""
+are compared before anything is timed.
+--strategies: the cost of the strategy reports: the grid's
+`sweep_device` at quality 1 and 2 with jxg_set_sweep_report off and on,
+alternating; wall time and the ms_recon / ms_metrics of the median sweep.  On a
+library without the switch (JXG_LIB_PATH pointing at the parent commit's build)
+only the switch-off rows are measured, for the comparison on one box."""
 import argparse
 import json
 import os
@@ -124,6 +130,64 @@ def library(args):
         del cached, d_img, d_rec
 
 
+def strategies(args):
+    import torch
+
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8_device
+
+    has_switch = hasattr(jxg.load(), "jxg_set_sweep_report")
+    points = [dict(distance=d, effort=e, proposals=0, flags=jxg.FLAGS_CJXL_DEFAULTS)
+              for d in DISTANCES for e in EFFORTS]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        d_img = synth_rgb8_device(w, h, SEED_BASE + seed, 0)
+        torch.cuda.synchronize()
+        sweeper = jxg.Encoder()
+
+        def sweep(level, on):
+            kw = {"strategies": True} if on else {}
+            return sweeper.sweep_device(d_img.data_ptr(), w, h, points, quality=QUALITY[level],
+                                        **kw)
+
+        want = sweep(2, False)  # warm, all buffers
+        if has_switch:
+            got = sweep(2, True)
+            assert [g[0] for g in got] == [r[0] for r in want], "bytes differ with the switch on"
+            for g, r in zip(got, want):
+                assert int(g[1]["strategies"]["sse"].sum()) == g[1]["sse"] == r[1]["sse"]
+                assert int(g[1]["strategies"]["pixels"].sum()) == w * h
+        modes = (False, True) if has_switch else (False,)
+        for level in (1, 2):
+            wall = {m: [] for m in modes}
+            split = {m: [] for m in modes}
+            for rep in range(args.reps + 1):
+                for m in modes:
+                    t0 = time.perf_counter()
+                    sweep(level, m)
+                    t1 = time.perf_counter()
+                    if rep:
+                        wall[m].append((t1 - t0) * 1e3)
+                        split[m].append(sweeper.sweep_timings())
+            res = {"frame": name, "strategies": True, "library": os.path.relpath(jxg.LIB_PATH, ROOT), "quality": level,
+                   "points": len(points), "reps": args.reps,
+                   "queues": os.environ.get("GPU_MAX_HW_QUEUES", "default"),
+                   "lanes": sweeper.sweep_timings()["lanes"]}
+            for m in modes:
+                mid = sorted(range(len(wall[m])), key=lambda i: wall[m][i])[len(wall[m]) // 2]
+                key = "on" if m else "off"
+                res["ms_wall_" + key] = spread(wall[m])
+                res["ms_recon_" + key] = round(split[m][mid]["ms_recon"], 3)
+                res["ms_metrics_" + key] = round(split[m][mid]["ms_metrics"], 3)
+            if has_switch:
+                res["ms_added_per_point"] = round(
+                    (statistics.median(wall[True]) - statistics.median(wall[False])) / len(points),
+                    4)
+            print(json.dumps(res), flush=True)
+        sweeper.close()
+        del d_img
+
+
 def cli(args):
     import jxg
     from jxg.synth import SEED_BASE, synth_rgb8
@@ -168,6 +232,7 @@ def main():
     ap.add_argument("--sizes", default="8k,768")
     ap.add_argument("--queues", type=int, default=0)
     ap.add_argument("--cli", action="store_true")
+    ap.add_argument("--strategies", action="store_true")
     args = ap.parse_args()
     if not 0 <= args.queues <= 32:
         ap.error("--queues: at most 32 hardware queues (0: leave the environment's)")
@@ -177,6 +242,8 @@ def main():
         return cli(args)
     import torch  # noqa: F401  (one HIP runtime in the process: DESIGN.md §6)
 
+    if args.strategies:
+        return strategies(args)
     library(args)
 
 
