@@ -619,6 +619,70 @@ jxg_status jxg_strategy_report_rgb8_device(jxg_ctx* ctx, const void* d_orig, siz
 jxg_status jxg_set_sweep_report(jxg_ctx* ctx, int on);
 jxg_status jxg_sweep_report(jxg_ctx* ctx, jxg_strategy_report* out, uint32_t n);
 
+/* ---- coded bits per block and per strategy ----
+ * What the tokens of a varblock, and of all varblocks of a strategy, cost in
+ * the pass groups' AC streams as written.  Costs are exact integers in units of
+ * 1 / JXG_RATE_UNIT bit.  A token costs symbol_cost + JXG_RATE_UNIT * nbits
+ * (nbits: its raw bits).  Prefix codes: symbol_cost = JXG_RATE_UNIT * the length
+ * of the (cluster, token) code in the frame's final codes.  ANS: symbol_cost =
+ * jxg_rate_symbol_cost(f), f (1..4096) the symbol's normalised frequency in the
+ * histogram the stream carries.  A varblock's tokens are all tokens of its
+ * three channels, the non-zero-count token included, attributed to its first
+ * block.  Bound: a varblock has at most 3 x 65536 tokens of at most 7680 units
+ * (a symbol is at most 15 bits, raw bits at most 15), 1 509 949 440 < 2^32, so
+ * a u32 per block never overflows.
+ * Not attributed: the LF groups' streams (DC, strategy / quant-field metadata)
+ * and the headers -- they are what stream_bits - ac_bits leaves. */
+#define JXG_RATE_UNIT 256u
+/* floor(256 * log2(4096.0 / f) + 0.5) in double; 0 for f = 0 or f > 4096.
+ * Host only, needs no context.  Over f = 1..4096 the value nearest a rounding
+ * tie is 2.4e-4 away (f = 1203), so every libm gives the same table; the
+ * largest entry is 3072 (f = 1). */
+uint32_t jxg_rate_symbol_cost(uint32_t f);
+typedef struct {
+  uint64_t tokens[3];   /* X / Y / B */
+  uint64_t cost[3];     /* X / Y / B, 1/JXG_RATE_UNIT bit */
+} jxg_rate_row;
+/* (a struct tag, not a typedef: the report and the call that fills it share
+ * the name, which C and C++ allow only for a tag -- write `struct jxg_rate_report`) */
+struct jxg_rate_report {
+  jxg_rate_row row[JXG_NUM_STRATEGIES];   /* by raw AcStrategy id of the varblock */
+  uint64_t ac_bits;      /* exact: sum over pass groups of the bits of their AC streams as emitted
+                            (ANS: incl. the 32-bit state), no byte padding */
+  uint64_t stream_bits;  /* 8 * codestream bytes */
+  uint32_t ans;          /* 1 rANS, 0 prefix codes */
+  uint32_t groups;
+};
+/* The report of the context's last one-at-a-time encode, from what that encode
+ * left on the device: the token records, the final code tables and the emit
+ * pass's per-group bit counts; one kernel (csrc/jxg_rate.hip) prices every
+ * record.  Needs no original image and no reconstruction.  block_cost (host
+ * memory; d_block_cost device memory; may be NULL): [ysize_blocks]
+ * [xsize_blocks] u32, the geometry of block_sse -- a varblock's first block
+ * holds the sum of its three channels' costs, covered blocks 0, every word is
+ * written.  Nothing the encoder, jxg_reconstruct_rgb8 or
+ * jxg_strategy_report_rgb8 reads is modified: the calls can follow each other
+ * in any order, and two calls give the same bits.  Both return when the results
+ * are complete.  JXG_ERR_INVALID_ARG for a null ctx / out, where
+ * jxg_reconstruct_rgb8 gives it (no encode yet; the last use was a batch,
+ * streamed, sharded or warm-up encode, or a decode), and while streamed frames
+ * are pending. */
+jxg_status jxg_rate_report(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t* block_cost);
+jxg_status jxg_rate_report_device(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t* d_block_cost);
+/* Rate reports in a sweep.  With the switch on (default 0; JXG_ERR_INVALID_ARG
+ * while streamed frames are pending) every sweep -- quality 0 included, nothing
+ * here needs decoded pixels -- fills one report per point on its lane, after
+ * that point's emission.  Codestreams, q[], MS-SSIM results and strategy
+ * reports are unchanged, ms_metrics includes the added kernel (quality 1 / 2),
+ * and with the switch off a sweep launches what it launched before.
+ * jxg_sweep_rates copies the last sweep's reports out in point order, each
+ * bit-equal to jxg_rate_report after a one-at-a-time encode with that point (a
+ * refused point zero-filled; block maps are not kept); JXG_ERR_INVALID_ARG
+ * when the last sweep computed none, when n is not that sweep's, or while
+ * streamed frames are pending. */
+jxg_status jxg_set_sweep_rates(jxg_ctx* ctx, int on);
+jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n);
+
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result
  * discarded), which allocates the size's device buffers and loads every

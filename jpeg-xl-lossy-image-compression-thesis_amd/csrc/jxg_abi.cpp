@@ -505,6 +505,37 @@ jxg_status jxg_strategy_report_rgb8_device(jxg_ctx* ctx, const void* d_orig, siz
                                    d_block_sse);
 }
 
+jxg_status jxg_rate_report(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t* block_cost) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : rate_report_last(c, out, block_cost, false);
+}
+
+jxg_status jxg_rate_report_device(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t* d_block_cost) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : rate_report_last(c, out, d_block_cost, true);
+}
+
+jxg_status jxg_set_sweep_rates(jxg_ctx* ctx, int on) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  c->sw.rates = on != 0;
+  return JXG_OK;
+}
+
+jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+  const Ctx::Sweep& sw = c->sw;
+  if (pipe_busy(c) || !sw.rate_have || n != sw.rate.size()) return JXG_ERR_INVALID_ARG;
+  std::copy(sw.rate.begin(), sw.rate.end(), out);
+  return JXG_OK;
+}
+
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
   Ctx* c;

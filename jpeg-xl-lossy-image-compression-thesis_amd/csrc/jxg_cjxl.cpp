@@ -249,6 +249,34 @@ bool write_report_rows(const char* path, const std::string& orig_name,
   return std::fclose(f) == 0;
 }
 
+// --jxg_rates=FILE.csv: the rows of jxg/harness.py rate_stats / write_rate_stats
+// for one encode -- one per strategy of the rate report that holds tokens
+bool write_rate_rows(const char* path, const std::string& orig_name, const std::string& comp_name,
+                     float distance, int effort, const struct jxg_rate_report& rep) {
+  std::error_code ec;
+  const auto size = std::filesystem::file_size(path, ec);
+  const bool header = ec || size == 0;
+  FILE* f = std::fopen(path, header ? "w" : "a");
+  if (!f) return false;
+  if (header)
+    std::fputs("Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
+               "Tokens X,Tokens Y,Tokens B,Bits X,Bits Y,Bits B,AC Bits,Stream Bits\n", f);
+  for (int i = 0; i < JXG_NUM_STRATEGIES; i++) {
+    const jxg_rate_row& r = rep.row[i];
+    if (!(r.tokens[0] + r.tokens[1] + r.tokens[2])) continue;
+    std::fprintf(f, "%s,%s,%s,%d,%d,%s,%llu,%llu,%llu,%s,%s,%s,%llu,%llu\n",
+                 csv_field(orig_name).c_str(), csv_field(comp_name).c_str(),
+                 rust_f32(distance).c_str(), effort, i, kStrategyNames[i],
+                 (unsigned long long)r.tokens[0], (unsigned long long)r.tokens[1],
+                 (unsigned long long)r.tokens[2],
+                 rust_f64((double)r.cost[0] / (double)JXG_RATE_UNIT).c_str(),
+                 rust_f64((double)r.cost[1] / (double)JXG_RATE_UNIT).c_str(),
+                 rust_f64((double)r.cost[2] / (double)JXG_RATE_UNIT).c_str(),
+                 (unsigned long long)rep.ac_bits, (unsigned long long)rep.stream_bits);
+  }
+  return std::fclose(f) == 0;
+}
+
 struct SweepLine {
   double distance;
   int effort;
@@ -272,7 +300,7 @@ bool read_sweep_list(const char* path, std::vector<SweepLine>& out) {
 // INPUT at every point of the list -> OUTDIR/<stem>-<distance>-<effort>.jxl
 int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* outdir,
               const std::vector<SweepLine>& list, const std::vector<uint8_t>& rgb, uint32_t w,
-              uint32_t h, const char* report_path) {
+              uint32_t h, const char* report_path, const char* rates_path) {
   const size_t n = list.size();
   std::vector<jxg_sweep_point> pts(n);
   for (size_t i = 0; i < n; i++)
@@ -283,6 +311,9 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   std::vector<jxg_quality> qs(report_path ? n : 0);
   std::vector<jxg_strategy_report> reps(report_path ? n : 0);
   if (report_path && jxg_set_sweep_report(ctx, 1) != JXG_OK) return 1;
+  // (the rate reports need no chain: they follow each point's emission)
+  std::vector<struct jxg_rate_report> rates(rates_path ? n : 0);
+  if (rates_path && jxg_set_sweep_rates(ctx, 1) != JXG_OK) return 1;
   const auto t0 = std::chrono::steady_clock::now();
   const jxg_status st =
       jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(), (uint32_t)n,
@@ -297,6 +328,10 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   }
   if (report_path && jxg_sweep_report(ctx, reps.data(), (uint32_t)n) != JXG_OK) {
     std::fprintf(stderr, "sweep report failed\n");
+    return 1;
+  }
+  if (rates_path && jxg_sweep_rates(ctx, rates.data(), (uint32_t)n) != JXG_OK) {
+    std::fprintf(stderr, "sweep rates failed\n");
     return 1;
   }
   std::error_code ec;
@@ -317,6 +352,12 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
         !write_report_rows(report_path, std::filesystem::path(input).filename().string(), name,
                            pts[i].distance, pts[i].effort, reps[i], w, h)) {
       std::fprintf(stderr, "cannot write %s\n", report_path);
+      rc = 1;
+    }
+    if (rates_path &&
+        !write_rate_rows(rates_path, std::filesystem::path(input).filename().string(), name,
+                         pts[i].distance, pts[i].effort, rates[i])) {
+      std::fprintf(stderr, "cannot write %s\n", rates_path);
       rc = 1;
     }
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -342,7 +383,7 @@ int main(int argc, char** argv) {
                  "usage: %s INPUT OUTPUT [--distance=D] [--effort=E] "
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
                  "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH] "
-                 "[--jxg_report=FILE.csv]\n"
+                 "[--jxg_report=FILE.csv] [--jxg_rates=FILE.csv]\n"
                  "       %s INPUT OUTDIR --sweep=LIST [the same flags]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
@@ -360,6 +401,9 @@ int main(int argc, char** argv) {
   // --jxg_report=FILE.csv (not a cjxl option): append the per-strategy
   // statistics of the encode, or of every point of --sweep= (jxg_strategy_report_rgb8)
   const char* report_path = nullptr;
+  // --jxg_rates=FILE.csv (not a cjxl option): append the coded bits per strategy
+  // of the encode, or of every point of --sweep= (jxg_rate_report)
+  const char* rates_path = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -405,6 +449,8 @@ int main(int argc, char** argv) {
       sweep_path = a + 8;
     else if (!std::strncmp(a, "--jxg_report=", 13))
       report_path = a + 13;
+    else if (!std::strncmp(a, "--jxg_rates=", 12))
+      rates_path = a + 12;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -487,7 +533,8 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (sweep_path) {
-    const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h, report_path);
+    const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h, report_path,
+                             rates_path);
     std::fflush(nullptr);
     std::_Exit(rc);  // (as below: no exit-time teardown)
   }
@@ -537,6 +584,20 @@ int main(int argc, char** argv) {
                            std::filesystem::path(argv[2]).filename().string(), p.distance,
                            p.effort, rep, w, h)) {
       std::fprintf(stderr, "cannot write %s\n", report_path);
+      return fail(1);
+    }
+  }
+  if (rates_path) {
+    struct jxg_rate_report rates{};
+    st = jxg_rate_report(ctx, &rates, nullptr);
+    if (st != JXG_OK) {
+      std::fprintf(stderr, "rate report failed: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    if (!write_rate_rows(rates_path, std::filesystem::path(argv[1]).filename().string(),
+                         std::filesystem::path(argv[2]).filename().string(), p.distance, p.effort,
+                         rates)) {
+      std::fprintf(stderr, "cannot write %s\n", rates_path);
       return fail(1);
     }
   }

@@ -106,6 +106,8 @@ enum EncEvent : int {
   kNumEncEvents = 10
 };
 
+// (include/jxg.h: the report shares its name with the call that fills it)
+using RateReport = struct ::jxg_rate_report;
 struct Ctx;
 struct Job;
 struct Pipe;
@@ -190,6 +192,22 @@ struct Ctx : EncArenas {
     bool ok = false;
     uint32_t w = 0, h = 0;
   } rc;
+  // rate report (jxg_rate_report, a sweep's lane; jxg_rate.cpp): the symbol
+  // cost table (uploaded once), the 27 x 6 table, the host variant's device
+  // map -- allocated by the first use -- and what the last finished encode of
+  // a whole frame left for it (rate_note): its coder, histograms, group count
+  // and kernel geometry, the emitted AC bits, the codestream's bits.  The
+  // records, code tables and strategy map are the context's own buffers
+  // (tokens, codes_ac / ans_tab, bandtok, acs, ac, nz), valid as long as rc.ok
+  struct Rate {
+    DevBuf<uint16_t> ftab;
+    bool ftab_ready = false;
+    DevBuf<uint64_t> table;
+    DevBuf<uint32_t> map;
+    bool have = false, ans = false, whole_group = false;
+    uint32_t nhist = 0, groups = 0;
+    uint64_t ac_bits = 0, stream_bits = 0;
+  } rt;
   // decoder (jxg_decode_rgb8; jxg_decode_dev.cpp), allocated by its first
   // call: the codestream's words, the pass groups' section bounds, the AC
   // stream's decode tables [ctxmap | histograms | prefix or alias tables], the
@@ -236,6 +254,12 @@ struct Ctx : EncArenas {
     PinBuf<uint64_t> h_rep;
     std::vector<jxg_strategy_report> rep;
     bool rep_have = false;  // the last sweep computed `rep`
+    // with jxg_set_sweep_rates: the points' pinned results [n][kRateWords],
+    // the last sweep's rate reports in point order
+    bool rates = false;  // the switch
+    PinBuf<uint64_t> h_rate;
+    std::vector<RateReport> rate;
+    bool rate_have = false;  // the last sweep computed `rate`
   } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
@@ -386,6 +410,9 @@ struct SweepReq {
   // strategy report behind the metrics (quality 1 / 2 with the switch on):
   // pinned [kReportCells] table
   uint64_t* h_rep = nullptr;
+  // rate report behind the emission (any quality, with the switch on): pinned
+  // [kRateWords], the table and the four scalars of jxg_rate_report
+  uint64_t* h_rate = nullptr;
 };
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                        size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
@@ -487,6 +514,23 @@ jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride,
                                 jxg_strategy_report* out, uint32_t* block_sse);
 // the reduction alone, enqueued on c's stream: c->q.bsse -> c->q.rep (cleared first)
 jxg_status strategy_report_enqueue(Ctx* c, uint32_t w, uint32_t h);
+
+// ---- jxg_rate.cpp: coded bits per block and strategy ----
+// a pinned result of a sweep's point: the table, then ac_bits, stream_bits,
+// ans, groups
+constexpr size_t kRateWords = kRateCells + 4;
+// the encode of J on c has its emission's bit counts on the host and its
+// codestream's size known: keep what the report needs (the Job goes away)
+void rate_note(Ctx* c, const Job& J);
+// the kernel alone, enqueued on c's stream: c->rt.table (cleared first) and,
+// when d_block_cost is not null, the map of the w x h frame c encoded last
+jxg_status rate_enqueue(Ctx* c, uint32_t w, uint32_t h, uint32_t* d_block_cost);
+// a sweep's point on its lane: the kernel, the table's copy to rq.h_rate and
+// the scalars beside it
+jxg_status sweep_rate_enqueue(Ctx* lane, const SweepReq& rq, uint32_t w, uint32_t h);
+void rate_from_words(const uint64_t* words, RateReport* out);
+// the report of the last one-at-a-time encode; block_cost host or device memory, or null
+jxg_status rate_report_last(Ctx* c, RateReport* out, uint32_t* block_cost, bool on_device);
 
 // ---- jxg_decode_dev.cpp ----
 jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, size_t row_stride,

@@ -848,6 +848,7 @@ jxg_status enc_finish_start(Ctx* c, Job& J, bool split) {
     if ((st = stage_concat(c, J, true, nullptr, nullptr, &J.host_out, &J.out_bytes))) return st;
   }
   J.ms_finish_layout = split ? J.ms_layout : ms_since(t_layout);
+  rate_note(c, J);  // (host bookkeeping: the emission's bit counts are here by now)
   return JXG_OK;
 }
 // the frame's stats (the lane's jxg_stats); `assembled`: the assembly has

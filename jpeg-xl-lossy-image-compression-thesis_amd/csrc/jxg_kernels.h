@@ -425,6 +425,23 @@ struct ReportArgs {
   unsigned long long* table;  // [kReportCells]
 };
 hipError_t launch_strategy_report(const ReportArgs& a, hipStream_t s);
+// coded bits per varblock and strategy (jxg_rate.hip): the
+// table is jxg_rate_report's rows as u64 cells [27 raw ids][6: tokens X / Y / B,
+// cost X / Y / B in 1 / kRateUnit bit], added into (pre-zeroed)
+constexpr uint32_t kRateStrategies = 27, kRateCols = 6, kRateCells = kRateStrategies * kRateCols,
+                   kRateUnit = 256, kRateFreqs = 4097;
+struct RateArgs {
+  AcArgs ac;                  // of the encode: acs, ac, nz, geometry, group slots, tokens, and
+                              //   with prefix codes `codes`; the rest unused
+  const uint8_t* ans_tab;     // the encode's ANS table blob (AnsArgs::tab), or null: prefix codes
+  uint32_t nhist;             //   its histograms in use
+  const uint16_t* ftab;       // [kRateFreqs] jxg_rate_symbol_cost(f) (ANS)
+  uint32_t* block_cost;       // [bys][bxs] out: a varblock's cost at its first block, 0 at
+                              //   covered blocks (every word written), or null
+  unsigned long long* table;  // [kRateCells]
+};
+// one workgroup per (group, band) as launch_ac_hist; whole_group as there
+hipError_t launch_rate(const RateArgs& a, uint32_t ngroups, bool whole_group, hipStream_t s);
 // the decoder's pass groups (jxg_decode.hip): one wave per
 // group walks its section of the codestream with the decode core and writes
 // the non-zero coefficients into `ac` (it zeroes the group's area first)

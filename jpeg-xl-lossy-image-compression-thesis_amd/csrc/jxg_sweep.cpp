@@ -15,6 +15,9 @@
 // With jxg_set_sweep_report the chain ends in the kernel that also writes the
 // block error map, and the strategy reduction (jxg_report.hip, DESIGN.md
 // §3.16) follows the metrics; its table is a third pinned result.
+// With jxg_set_sweep_rates every point's lane prices its token records
+// (jxg_rate.hip) behind the codestream's copy -- ahead of the
+// metrics' end event with quality, alone with quality 0.
 #include <cmath>
 #include <cstring>
 
@@ -78,6 +81,10 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(hipMemcpyAsync(rq.h_rep, q.rep.p, kReportCells * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, s));
   }
+  if (rq.h_rate) {
+    const jxg_status sr = sweep_rate_enqueue(S, rq, w, h);
+    if (sr) return sr;
+  }
   JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   JXG_HIP(hipEventRecord(rq.ev[2], s));
   return JXG_OK;
@@ -123,6 +130,11 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.rep_have = false;
   sw.rep.clear();
   if (report) sw.rep.assign(n, jxg_strategy_report{});
+  // the rate reports ride on every sweep (jxg_set_sweep_rates)
+  const bool rates = sw.rates;
+  sw.rate_have = false;
+  sw.rate.clear();
+  if (rates) sw.rate.assign(n, RateReport{});
   // the context is lane 0 and encodes with its frames' points: its own
   // parameters are put back however the call ends
   const jxg_params saved = c->params;
@@ -143,6 +155,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     sw.stats.ms_call = ms_since(t0);
     sw.ms.clear();
     sw.rep.clear();
+    sw.rate.clear();
     return e;
   };
   if (nv) {
@@ -167,6 +180,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     }
     if (report && sw.h_rep.ensure((size_t)nv * kReportCells) != hipSuccess)
       return fail(JXG_ERR_OOM);
+    if (rates && sw.h_rate.ensure((size_t)nv * kRateWords) != hipSuccess) return fail(JXG_ERR_OOM);
     if (ms_run) {  // the original's pyramid, once: every lane reads it after ev_pyr
       if (sw.h_ms.ensure((size_t)nv * 2 * kMsScales) != hipSuccess ||
           sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess)
@@ -189,6 +203,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       const uint32_t k = got++, i = valid[k];
       if ((e = pipe_receive(c, &outs[i]))) return;
       sw.stats.ms_encode += c->stats.ms_total;
+      if (rates) rate_from_words(sw.h_rate.p + (size_t)k * kRateWords, &sw.rate[i]);
       if (!quality) return;
       const uint64_t sse = sw.h_q.p[2 * k];
       double ssum;
@@ -227,6 +242,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.ev_pyr = sw.ev_pyr;
       }
       if (report) rq.h_rep = sw.h_rep.p + (size_t)k * kReportCells;
+      if (rates) rq.h_rate = sw.h_rate.p + (size_t)k * kRateWords;
       e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
       // completed points whose copies have landed (or when more than two wait)
       while (!e && pipe_done_ready(c)) take();
@@ -240,6 +256,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   if (statuses) std::copy(st.begin(), st.end(), statuses);
   sw.ms_have = ms;
   sw.rep_have = report;
+  sw.rate_have = rates;
   sw.stats.ms_call = ms_since(t0);
   return first;
 }

@@ -131,6 +131,32 @@ class _StrategyReport(ctypes.Structure):
                 "names": STRATEGY_NAMES}
 
 
+RATE_UNIT = 256  # JXG_RATE_UNIT: costs are integers in 1 / 256 bit
+
+
+class _RateRow(ctypes.Structure):
+    _fields_ = [("tokens", ctypes.c_uint64 * 3), ("cost", ctypes.c_uint64 * 3)]
+
+
+class _RateReport(ctypes.Structure):
+    _fields_ = [("row", _RateRow * NUM_STRATEGIES), ("ac_bits", ctypes.c_uint64),
+                ("stream_bits", ctypes.c_uint64), ("ans", ctypes.c_uint32),
+                ("groups", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        """``tokens`` / ``cost`` [27, 3] uint64 (X, Y, B; cost in 1 / RATE_UNIT bit),
+        the four scalars, names"""
+        t = np.frombuffer(bytes(self.row), dtype=np.uint64).reshape(NUM_STRATEGIES, 6)
+        return {"tokens": t[:, 0:3].copy(), "cost": t[:, 3:6].copy(),
+                "ac_bits": int(self.ac_bits), "stream_bits": int(self.stream_bits),
+                "ans": int(self.ans), "groups": int(self.groups), "names": STRATEGY_NAMES}
+
+
+def rate_symbol_cost(f: int) -> int:
+    """jxg_rate_symbol_cost: an ANS symbol of normalised frequency f in 1 / 256 bit"""
+    return int(load().jxg_rate_symbol_cost(f))
+
+
 class _SweepPoint(ctypes.Structure):
     _fields_ = [("distance", ctypes.c_float), ("effort", ctypes.c_int),
                 ("proposals", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -163,6 +189,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_sweep_msssim",
            "jxg_strategy_report_rgb8", "jxg_strategy_report_rgb8_device",
            "jxg_set_sweep_report", "jxg_sweep_report",
+           "jxg_rate_symbol_cost", "jxg_rate_report", "jxg_rate_report_device",
+           "jxg_set_sweep_rates", "jxg_sweep_rates",
 )
 
 _lib = None
@@ -265,6 +293,12 @@ def load():
     lib.jxg_strategy_report_rgb8_device.argtypes = rep_args
     lib.jxg_set_sweep_report.argtypes = [vp, ctypes.c_int]
     lib.jxg_sweep_report.argtypes = [vp, ctypes.POINTER(_StrategyReport), ctypes.c_uint32]
+    lib.jxg_rate_symbol_cost.argtypes = [ctypes.c_uint32]
+    lib.jxg_rate_symbol_cost.restype = ctypes.c_uint32
+    lib.jxg_rate_report.argtypes = [vp, ctypes.POINTER(_RateReport), vp]
+    lib.jxg_rate_report_device.argtypes = [vp, ctypes.POINTER(_RateReport), vp]
+    lib.jxg_set_sweep_rates.argtypes = [vp, ctypes.c_int]
+    lib.jxg_sweep_rates.argtypes = [vp, ctypes.POINTER(_RateReport), ctypes.c_uint32]
     _lib = lib
     return lib
 
@@ -401,6 +435,37 @@ class Encoder:
         rep = _StrategyReport()
         _check(load().jxg_strategy_report_rgb8_device(
             self._ctx, ctypes.c_void_p(ptr), row_stride or w * 3, ctypes.byref(rep),
+            ctypes.c_void_p(block_map_ptr) if block_map_ptr else None))
+        return rep.as_dict()
+
+    def rate_report(self, block_map: bool = False) -> dict:
+        """Coded bits of the frame last encoded with :meth:`encode` /
+        :meth:`encode_device`, per AC strategy (jxg_rate_report): ``tokens`` and
+        ``cost`` are ``[27, 3]`` uint64 arrays (raw AcStrategy id; X, Y, B), cost
+        in 1 / ``RATE_UNIT`` bit of the pass groups' AC streams as written;
+        ``ac_bits`` is the exact size of those streams, ``stream_bits`` the
+        codestream's, ``ans`` the coder, ``groups`` the pass groups.  Exact
+        integer sums priced on the GPU from the encode's own token records and
+        final code tables; needs no image.  ``block_map=True`` adds
+        ``block_cost``, ``(bys, bxs)`` uint32: a varblock's cost at its first
+        block, 0 at the blocks it covers.  Raises JxgError where
+        :meth:`reconstruct` does."""
+        w, h = self._last_wh or (1, 1)
+        rep = _RateReport()
+        bmap = np.empty(((h + 7) // 8, (w + 7) // 8), dtype=np.uint32) if block_map else None
+        _check(load().jxg_rate_report(self._ctx, ctypes.byref(rep),
+                                      bmap.ctypes.data if block_map else None))
+        out = rep.as_dict()
+        if block_map:
+            out["block_cost"] = bmap
+        return out
+
+    def rate_report_device(self, block_map_ptr: int | None = None) -> dict:
+        """:meth:`rate_report` with the ``(bys, bxs)`` uint32 block map written
+        to device memory at ``block_map_ptr`` (jxg_rate_report_device)."""
+        rep = _RateReport()
+        _check(load().jxg_rate_report_device(
+            self._ctx, ctypes.byref(rep),
             ctypes.c_void_p(block_map_ptr) if block_map_ptr else None))
         return rep.as_dict()
 
@@ -563,7 +628,8 @@ class Encoder:
                 pts.append(_SweepPoint(p[0], p[1], *(tuple(p[2:4]) + (0, 0))[:2]))
         return pts
 
-    def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False):
+    def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False,
+                    rates=False):
         if quality not in self._QUALITY:
             raise ValueError("quality: 'msssim', 'ssim', 'psnr' or None")
         level = self._QUALITY[quality]
@@ -578,17 +644,23 @@ class Encoder:
         outs = (_Buffer * n)()
         qs = (_Quality * n)() if level else None
         st = (ctypes.c_int * n)()
-        mss = reps = None
+        mss = reps = rts = None
         if ms:
             _check(load().jxg_set_sweep_msssim(self._ctx, 1))
         try:
             if strategies:
                 _check(load().jxg_set_sweep_report(self._ctx, 1))
+            if rates:
+                _check(load().jxg_set_sweep_rates(self._ctx, 1))
             ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
             if strategies:
                 r = (_StrategyReport * n)()
                 if load().jxg_sweep_report(self._ctx, r, n) == 0:
                     reps = r
+            if rates:
+                r = (_RateReport * n)()
+                if load().jxg_sweep_rates(self._ctx, r, n) == 0:
+                    rts = r
             if ms:  # (a sweep that failed as a whole has none: ret is raised below)
                 m = (_Msssim * n)()
                 if load().jxg_sweep_msssim(self._ctx, m, n) == 0:
@@ -598,6 +670,8 @@ class Encoder:
                 load().jxg_set_sweep_msssim(self._ctx, 0)
             if strategies:
                 load().jxg_set_sweep_report(self._ctx, 0)
+            if rates:
+                load().jxg_set_sweep_rates(self._ctx, 0)
         st = [int(v) for v in st]
         if ret != 0 and (strict or self._batch_call_failed(ret, st)):
             for i in range(n):
@@ -616,11 +690,13 @@ class Encoder:
                     q["cs"] = [float(v) for v in mss[i].cs]
                 if reps is not None:
                     q["strategies"] = reps[i].as_dict()
+            if rts is not None:
+                q = dict(q or {}, rates=rts[i].as_dict())
             res.append((self._take(outs[i]), q))
         return res
 
     def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True,
-              strategies: bool = False) -> list:
+              strategies: bool = False, rates: bool = False) -> list:
         """One host (H, W, 3) uint8 image encoded at every point of ``points``
         in one call (jxg_sweep_rgb8): the image is uploaded once and the points
         run through the streaming pipeline's lanes of this context, whose own
@@ -638,23 +714,27 @@ class Encoder:
         point comes back as ``(None, status)``.  ``strategies=True`` (not with
         ``quality=None``): each point's dict gains ``"strategies"``, the
         :meth:`strategy_report` of that point, reduced on its lane
-        (jxg_set_sweep_report).  Afterwards :meth:`reconstruct`
+        (jxg_set_sweep_report).  ``rates=True``: each point's dict gains
+        ``"rates"``, the :meth:`rate_report` of that point, priced on its lane
+        after its emission (jxg_set_sweep_rates); with ``quality=None`` the dict
+        holds only that.  Afterwards :meth:`reconstruct`
         raises until the next :meth:`encode`."""
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("expected (H, W, 3) uint8")
         h, w = rgb.shape[:2]
         return self._sweep_call(load().jxg_sweep_rgb8, rgb.ctypes.data, w, h, w * 3, points,
-                                quality, strict, strategies)
+                                quality, strict, strategies, rates)
 
     def sweep_device(self, ptr: int, width: int, height: int, points, quality="ssim",
                      strict: bool = True, row_stride: int | None = None,
-                     strategies: bool = False) -> list:
+                     strategies: bool = False, rates: bool = False) -> list:
         """:meth:`sweep` of a device-resident RGB8 image (rows of ``row_stride``
         bytes, default 3 * width), which must stay unchanged until the call
         returns (jxg_sweep_rgb8_device)."""
         return self._sweep_call(load().jxg_sweep_rgb8_device, ctypes.c_void_p(ptr), width, height,
-                                row_stride or width * 3, points, quality, strict, strategies)
+                                row_stride or width * 3, points, quality, strict, strategies,
+                                rates)
 
     def sweep_timings(self) -> dict:
         """The last :meth:`sweep` (jxg_sweep_timings): points encoded, lanes,

@@ -28,7 +28,9 @@ Mirrors pscoro/JPEG-XL-Lossy-Image-Compression-Thesis benchmark-jpegxl:
 The project's own extension (no counterpart in the reference): ``StrategyStat``
 rows -- one per (image, point, non-empty AC strategy) from the GPU's strategy
 report (Encoder.strategy_report) -- in ``strategy_stats.csv``,
-and ``compare_strategy_stats``, their A/B difference.
+and ``compare_strategy_stats``, their A/B difference; ``RateStat`` rows -- one
+per (image, point, strategy that holds tokens) from the GPU's rate report
+(Encoder.rate_report): tokens and coded bits per channel.
 """
 import csv
 import os
@@ -259,6 +261,75 @@ def compare_strategy_stats(file_1: str, file_2: str):
     return diffs
 
 
+RATE_HEADER = [
+    "Original Image Name", "Compressed Image Name", "Distance", "Effort", "Strategy", "Name",
+    "Tokens X", "Tokens Y", "Tokens B", "Bits X", "Bits Y", "Bits B", "AC Bits", "Stream Bits",
+]
+
+
+@dataclass
+class RateStat:
+    """One strategy of one encode in the rate report (Encoder.rate_report,
+    DESIGN.md 3.17): the tokens of its varblocks per channel and what they cost
+    in the written AC streams, in bits (the report's cost / 256); beside them
+    the point's ``ac_bits`` and ``stream_bits``, the same on every row of it."""
+    orig_image_name: str
+    comp_image_name: str
+    distance: float  # f32
+    effort: int
+    strategy: int
+    name: str
+    tokens_x: int
+    tokens_y: int
+    tokens_b: int
+    bits_x: float
+    bits_y: float
+    bits_b: float
+    ac_bits: int
+    stream_bits: int
+
+    _FLOATS = ("bits_x", "bits_y", "bits_b")
+
+    def row(self):
+        return [self.orig_image_name, self.comp_image_name, rust_f32(self.distance),
+                str(self.effort), str(self.strategy), self.name] + [
+                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
+                    else str(getattr(self, f.name)) for f in fields(self)[6:]]
+
+    @classmethod
+    def parse(cls, rec):
+        vals = [float(v) if f.name in cls._FLOATS else int(v)
+                for f, v in zip(fields(cls)[6:], rec[6:14])]
+        return cls(rec[0], rec[1], float(np.float32(rec[2])), int(rec[3]), int(rec[4]), rec[5],
+                   *vals)
+
+
+def rate_stats(orig_name: str, comp_name: str, distance: float, effort: int, report: dict):
+    """The RateStat rows of one report (Encoder.rate_report / a sweep point's
+    ``"rates"``): the strategies that hold tokens, in id order."""
+    rows = []
+    for i in range(len(report["tokens"])):
+        tok = [int(v) for v in report["tokens"][i]]
+        if sum(tok) == 0:
+            continue
+        bits = [float(int(v)) / 256.0 for v in report["cost"][i]]
+        rows.append(RateStat(orig_name, comp_name, float(np.float32(distance)), int(effort), i,
+                             report["names"][i], tok[0], tok[1], tok[2], bits[0], bits[1], bits[2],
+                             int(report["ac_bits"]), int(report["stream_bits"])))
+    return rows
+
+
+def write_rate_stats(rows, rate_file: str) -> None:
+    write_csv_header(rate_file, RATE_HEADER)
+    write_csv(rows, rate_file)
+
+
+def read_rate_stats(file_name: str):
+    with open(file_name, newline="") as f:
+        rows = list(csv.reader(f))
+    return [RateStat.parse(r) for r in rows[1:] if r]
+
+
 _DIFF_FIELDS = [f.name for f in fields(ComparisonResult)[4:]]
 
 
@@ -381,7 +452,7 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
 
 def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
                       result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False,
-                      strategy_file: str | None = None):
+                      strategy_file: str | None = None, rate_file: str | None = None):
     """The harness's per-image loop (benchmark.rs:637-677) in one call: the
     image is encoded at every point (dicts with ``distance`` / ``effort`` and
     optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
@@ -394,7 +465,10 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     ``ms_ssim`` (needs ``ssim``): the MS-SSIM column from the points' lanes
     (``quality="msssim"``).  ``strategy_file``: every point's strategy report
     is reduced on its lane as well (``strategies=True``) and one StrategyStat
-    row per non-empty strategy is appended to that file (strategy_stats.csv)."""
+    row per non-empty strategy is appended to that file (strategy_stats.csv).
+    ``rate_file``: every point's rate report is priced on its lane
+    (``rates=True``) and one RateStat row per strategy that holds tokens is
+    appended to that file."""
     if ms_ssim and not ssim:
         raise ValueError("ms_ssim rides on the quality-2 sweep: it needs ssim=True")
     o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
@@ -403,7 +477,7 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     h, w = o.shape[:2]
     points = list(points)
     res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr",
-                        strategies=strategy_file is not None)
+                        strategies=strategy_file is not None, rates=rate_file is not None)
     stem = os.path.splitext(orig_name)[0]
     raw = w * h * 3
     datas, records = [], []
@@ -415,4 +489,7 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
         if strategy_file is not None:
             write_strategy_stats(strategy_stats(orig_name, comp_image_name(stem, d, e), d, e,
                                                 q["strategies"], w, h), strategy_file)
+        if rate_file is not None:
+            write_rate_stats(rate_stats(orig_name, comp_image_name(stem, d, e), d, e, q["rates"]),
+                             rate_file)
     return datas, records

@@ -20,7 +20,12 @@ are compared before anything is timed.
 `sweep_device` at quality 1 and 2 with jxg_set_sweep_report off and on,
 alternating; wall time and the ms_recon / ms_metrics of the median sweep.  On a
 library without the switch (JXG_LIB_PATH pointing at the parent commit's build)
-only the switch-off rows are measured, for the comparison on one box."""
+only the switch-off rows are measured, for the comparison on one box.
+--rates: the cost of the rate reports: the grid's
+`sweep_device` at quality 0 and 1 with jxg_set_sweep_rates off and on,
+alternating; then the kernel alone -- the ms_metrics (events) of a one-point
+sweep, switch on minus off -- and the wall time of rate_report_device.  On a
+library without the switch only the switch-off rows are measured."""
 import argparse
 import json
 import os
@@ -188,6 +193,87 @@ def strategies(args):
         del d_img
 
 
+def rates(args):
+    import torch
+
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8_device
+
+    has_switch = hasattr(jxg.load(), "jxg_set_sweep_rates")
+    points = [dict(distance=d, effort=e, proposals=0, flags=jxg.FLAGS_CJXL_DEFAULTS)
+              for d in DISTANCES for e in EFFORTS]
+    one = [dict(distance=1.0, effort=7, proposals=0, flags=jxg.FLAGS_CJXL_DEFAULTS)]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        d_img = synth_rgb8_device(w, h, SEED_BASE + seed, 0)
+        torch.cuda.synchronize()
+        sweeper = jxg.Encoder()
+
+        def sweep(level, on, pts=points):
+            kw = {"rates": True} if on else {}
+            return sweeper.sweep_device(d_img.data_ptr(), w, h, pts, quality=QUALITY[level], **kw)
+
+        want = sweep(1, False)  # warm, all buffers
+        if has_switch:
+            got = sweep(1, True)
+            assert [g[0] for g in got] == [r[0] for r in want], "bytes differ with the switch on"
+            for g in got:
+                assert g[1]["rates"]["stream_bits"] == 8 * len(g[0])
+        modes = (False, True) if has_switch else (False,)
+        for level in (0, 1):
+            wall = {m: [] for m in modes}
+            split = {m: [] for m in modes}
+            for rep in range(args.reps + 1):
+                for m in modes:
+                    t0 = time.perf_counter()
+                    sweep(level, m)
+                    t1 = time.perf_counter()
+                    if rep:
+                        wall[m].append((t1 - t0) * 1e3)
+                        split[m].append(sweeper.sweep_timings())
+            res = {"frame": name, "rates": True, "library": os.path.relpath(jxg.LIB_PATH, ROOT),
+                   "quality": level, "points": len(points), "reps": args.reps,
+                   "queues": os.environ.get("GPU_MAX_HW_QUEUES", "default"),
+                   "lanes": sweeper.sweep_timings()["lanes"]}
+            for m in modes:
+                mid = sorted(range(len(wall[m])), key=lambda i: wall[m][i])[len(wall[m]) // 2]
+                key = "on" if m else "off"
+                res["ms_wall_" + key] = spread(wall[m])
+                res["ms_encode_" + key] = round(split[m][mid]["ms_encode"], 3)
+                res["ms_metrics_" + key] = round(split[m][mid]["ms_metrics"], 3)
+            if has_switch:
+                res["ms_added_per_point"] = round(
+                    (statistics.median(wall[True]) - statistics.median(wall[False])) / len(points),
+                    4)
+            print(json.dumps(res), flush=True)
+        if has_switch:
+            # the kernel alone (with the table's memset and 1.3 KB copy), by the
+            # events around a point's metrics: a one-point sweep (d1 e7, cjxl's
+            # defaults) at quality 1, switch off and on, alternating; and the
+            # one-at-a-time call's host wall time after an encode of that point
+            ms = {False: [], True: []}
+            for rep in range(4 * args.reps + 1):
+                for m in (False, True):
+                    sweep(1, m, one)
+                    if rep:
+                        ms[m].append(sweeper.sweep_timings()["ms_metrics"])
+            with jxg.Encoder(**one[0]) as enc:
+                enc.encode_device(d_img.data_ptr(), w, h)
+                tokens = int(enc.rate_report_device()["tokens"].sum())
+                call = []
+                for rep in range(4 * args.reps):
+                    t0 = time.perf_counter()
+                    enc.rate_report_device()
+                    call.append((time.perf_counter() - t0) * 1e3)
+            print(json.dumps({"frame": name, "rates": True, "point": "d1 e7", "tokens": tokens,
+                              "ms_metrics_off": spread(ms[False]), "ms_metrics_on": spread(ms[True]),
+                              "ms_kernel_by_events": round(statistics.median(ms[True]) -
+                                                           statistics.median(ms[False]), 4),
+                              "ms_rate_report_call_wall": spread(call)}), flush=True)
+        sweeper.close()
+        del d_img
+
+
 def cli(args):
     import jxg
     from jxg.synth import SEED_BASE, synth_rgb8
@@ -233,6 +319,7 @@ def main():
     ap.add_argument("--queues", type=int, default=0)
     ap.add_argument("--cli", action="store_true")
     ap.add_argument("--strategies", action="store_true")
+    ap.add_argument("--rates", action="store_true")
     args = ap.parse_args()
     if not 0 <= args.queues <= 32:
         ap.error("--queues: at most 32 hardware queues (0: leave the environment's)")
@@ -244,6 +331,8 @@ def main():
 
     if args.strategies:
         return strategies(args)
+    if args.rates:
+        return rates(args)
     library(args)
 
 
