@@ -683,6 +683,79 @@ jxg_status jxg_rate_report_device(jxg_ctx* ctx, struct jxg_rate_report* out, uin
 jxg_status jxg_set_sweep_rates(jxg_ctx* ctx, int on);
 jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n);
 
+/* ---- A/B report of two encodes: strategy transitions ----
+ * Side A and side B are two encodes of the same image, the same xsize x ysize,
+ * any parameters.  Everything is counted per 8x8 block of the block grid:
+ *   from / to  the raw strategy id of the varblock covering the block in A / in
+ *              B (the low 7 bits of the ac_strategy byte);
+ *   pixels     the block's image pixels, cropped as jxg_strategy_row.pixels;
+ *   sse_a / b  the block's word of that side's block_sse
+ *              (jxg_strategy_report_rgb8);
+ *   cost_a / b the block's share of its varblock's coded cost, in
+ *              1 / JXG_RATE_UNIT bit: a varblock of cost C (its word of
+ *              jxg_rate_report's block_cost) covering n = across x down blocks,
+ *              numbered k = 0 .. n-1 in raster order inside the varblock, gives
+ *              block k  C / n + (k < C % n ? 1 : 0)  in integer arithmetic.
+ *              The shares of a varblock add up to C exactly; a share is below
+ *              2^31 (C <= 1 509 949 440).
+ * The two sides partition the image differently; the shares make a varblock's
+ * cost comparable block by block.  Every field is an exact integer sum: summed
+ * over `to` the cells give side A's per-strategy blocks, pixels, sse and cost,
+ * summed over `from` side B's. */
+typedef struct {
+  uint64_t blocks, pixels;
+  uint64_t sse_a, sse_b;
+  uint64_t cost_a, cost_b;      /* 1 / JXG_RATE_UNIT bit */
+} jxg_ab_cell;                   /* 48 bytes */
+typedef struct {
+  jxg_ab_cell cell[JXG_NUM_STRATEGIES][JXG_NUM_STRATEGIES];  /* [from][to] */
+} jxg_ab_report;
+/* a and b: two contexts on the same HIP device (a == b is allowed and gives a
+ * diagonal table), each one's last use a one-at-a-time encode of the same
+ * image size; orig / d_orig is that image (RGB8, rows of orig_stride bytes).
+ * Each context runs, on its own stream, the reconstruction chain into its block
+ * error map, the rate kernel into its cost map and the share pass; the
+ * transition kernel (csrc/jxg_ab.hip) runs on b's stream behind a's, without a
+ * host wait in between.  Both contexts are used from the calling thread, and
+ * the call returns when the results are complete.  block_delta (host memory;
+ * d_block_delta device memory; may be NULL): [2][ysize_blocks][xsize_blocks]
+ * int32, plane 0 sse_b - sse_a, plane 1 cost_b - cost_a (the shares), every
+ * word written.  Nothing the encoder, jxg_reconstruct_rgb8,
+ * jxg_strategy_report_rgb8 or jxg_rate_report reads is modified on either
+ * context: those calls and this one can follow each other in any order, two
+ * calls give the same bits and a re-encode the same bytes.
+ * JXG_ERR_INVALID_ARG for a null a, b, orig or out, orig_stride < 3 * xsize,
+ * different devices or frame sizes, a context where jxg_reconstruct_rgb8 or
+ * jxg_rate_report would give it, and streamed frames pending on either. */
+jxg_status jxg_ab_report_rgb8(jxg_ctx* a, jxg_ctx* b, const uint8_t* orig, size_t orig_stride,
+                              jxg_ab_report* out, int32_t* block_delta);
+jxg_status jxg_ab_report_rgb8_device(jxg_ctx* a, jxg_ctx* b, const void* d_orig, size_t orig_stride,
+                                     jxg_ab_report* out, int32_t* d_block_delta);
+/* A/B reports in a sweep.  jxg_set_sweep_ab names, for later sweeps of exactly
+ * n points, the point each point is compared against: base[i] is -1 (no
+ * comparison) or an index < i -- the baseline comes earlier in point order.
+ * The array is copied; base == NULL or n == 0 switches it off (the default).
+ * JXG_ERR_INVALID_ARG for a base[i] >= i or < -1 and while streamed frames are
+ * pending.  With the switch on a sweep of another n is JXG_ERR_INVALID_ARG at
+ * call level, nothing touched; a sweep of quality 1 or 2 fills one report for
+ * every point with base[i] >= 0, side A point base[i], side B point i (a
+ * quality-0 sweep computes none).  The points involved run the block-map form
+ * of the fused colour + error kernel and the rate kernel with its map whether
+ * or not jxg_set_sweep_report / jxg_set_sweep_rates are on; those switches
+ * alone decide whether their reports are returned.  A baseline's block errors,
+ * shares and strategy bytes are kept in a snapshot for the call, 9 bytes a
+ * block per distinct baseline (4.7 MB at 7680 x 4320).  Codestreams, q[],
+ * MS-SSIM results, strategy and rate reports are unchanged, ms_metrics
+ * includes the added kernels, and with the switch off a sweep launches and
+ * allocates what it did before.
+ * jxg_sweep_ab copies the last sweep's reports out in point order, each
+ * bit-equal to jxg_ab_report_rgb8_device on two one-at-a-time contexts created
+ * with those two points (zero-filled: base[i] = -1, a refused point, a refused
+ * baseline); JXG_ERR_INVALID_ARG when the last sweep computed none, when n is
+ * not that sweep's, or while streamed frames are pending. */
+jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n);
+jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n);
+
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result
  * discarded), which allocates the size's device buffers and loads every

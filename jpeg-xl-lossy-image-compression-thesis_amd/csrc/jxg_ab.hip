@@ -1,0 +1,127 @@
+// jxg_ab.hip -- A/B report of two encodes of one image on gfx950
+// (jxg_ab_report_rgb8, a sweep's lane): which strategy every
+// 8x8 block had in A and in B, with the bits and the error of both sides.
+//
+//   ab_share_kernel  one lane per block of one side: the block's share of its
+//                    varblock's coded cost C (the first-block map of
+//                    rate_kernel), C / n + (k < C % n) for covered block k of
+//                    n in raster order inside the varblock.  Gather form: the
+//                    first block is at the block's position rounded down to
+//                    the varblock's size.  The encoder guarantees that
+//                    alignment for every shape: up to 64 px by the merge
+//                    stage's construction inside 64x64 tiles (jxg_actask.h,
+//                    slice_task relies on it), for the 128 / 256 px shapes by
+//                    big_region / big_cand (jxg_bigvb.hip): a region starts at
+//                    a multiple of 16 (32) blocks of a pass group that starts
+//                    at a multiple of 32, and a half candidate at the region's
+//                    origin or half its size further.  n is a power of two.
+//   ab_report_kernel a workgroup of 4 waves takes chunks of 256 blocks,
+//                    striding over the frame; one lane per block reads the two
+//                    strategy bytes, error words and shares and derives its
+//                    image pixels from its position.  Neighbouring blocks
+//                    mostly share a (from, to) pair, so the wave first sums
+//                    the lanes of each pair present and one lane adds the six
+//                    sums to the workgroup's 27 x 27 x 6 table in LDS.  A
+//                    wave's error sums fit u32 (64 x 64 x 3 x 255^2 < 2^32);
+//                    its share sums do not (64 x 1.5e9), so the low and high
+//                    16 bits of the shares are summed apart (64 x 65535 each)
+//                    and put together in 64 bits.  The same pass writes the
+//                    two delta planes when asked for (every word).  At the end
+//                    one 64-bit global add per non-empty cell.
+// Every sum is an integer: the table does not depend on the order of the adds.
+#include <algorithm>
+
+#include "jxg_actask.h"
+
+namespace jxg {
+
+constexpr uint32_t kAbChunk = 256;  // blocks per workgroup step
+constexpr uint32_t kAbGrid = 1024;  // workgroups, at most
+
+__global__ __launch_bounds__(256) void ab_share_kernel(AbShareArgs a) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= a.nb) return;
+  int lcb, cx, cy;
+  varblock_dims(a.acs[b] & 0x7F, lcb, cx, cy);
+  const uint32_t bx = b % a.bxs, by = b / a.bxs;
+  // (ox <= bx, oy <= by: the first block is inside the frame)
+  const uint32_t ox = bx & ~(uint32_t)(cx - 1), oy = by & ~(uint32_t)(cy - 1);
+  const uint32_t C = a.block_cost[(size_t)oy * a.bxs + ox];
+  const uint32_t k = (by - oy) * (uint32_t)cx + (bx - ox);
+  a.share[b] = (C >> lcb) + (k < (C & ((1u << lcb) - 1u)) ? 1u : 0u);
+}
+
+__device__ __forceinline__ uint32_t ab_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void ab_report_kernel(AbArgs a) {
+  __shared__ unsigned long long sT[kAbWords];
+  for (uint32_t i = threadIdx.x; i < kAbWords; i += 256) sT[i] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nchunks = (a.nb + kAbChunk - 1) / kAbChunk;
+  for (uint32_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const uint32_t b = ch * kAbChunk + threadIdx.x;
+    const bool in = b < a.nb;
+    uint32_t pair = 0xFFFFu, px = 0, ea = 0, eb = 0, ca = 0, cb = 0;
+    bool todo = false;
+    if (in) {
+      const uint32_t from = a.acs_a[b] & 0x7Fu, to = a.acs_b[b] & 0x7Fu;
+      const uint32_t bx = b % a.bxs, by = b / a.bxs;
+      px = min(8u, a.w - bx * 8) * min(8u, a.h - by * 8);
+      ea = a.sse_a[b];
+      eb = a.sse_b[b];
+      ca = a.share_a[b];
+      cb = a.share_b[b];
+      if (a.delta) {
+        a.delta[b] = (int32_t)eb - (int32_t)ea;
+        a.delta[(size_t)a.nb + b] = (int32_t)cb - (int32_t)ca;
+      }
+      // (other ids: not a stream this encoder writes)
+      todo = from < kAbStrategies && to < kAbStrategies;
+      pair = from * kAbStrategies + to;
+    }
+    while (true) {
+      const unsigned long long m = __ballot(todo);
+      if (!m) break;
+      const int src = __ffsll((long long)m) - 1;
+      const uint32_t p0 = (uint32_t)__shfl((int)pair, src, 64);
+      const bool mine = todo && pair == p0;
+      const uint32_t n = ab_wave_sum(mine ? 1u : 0u), np = ab_wave_sum(mine ? px : 0u),
+                     nea = ab_wave_sum(mine ? ea : 0u), neb = ab_wave_sum(mine ? eb : 0u),
+                     cal = ab_wave_sum(mine ? ca & 0xFFFFu : 0u),
+                     cah = ab_wave_sum(mine ? ca >> 16 : 0u),
+                     cbl = ab_wave_sum(mine ? cb & 0xFFFFu : 0u),
+                     cbh = ab_wave_sum(mine ? cb >> 16 : 0u);
+      if ((int)lane == src) {
+        unsigned long long* r = sT + p0 * kAbCols;
+        atomicAdd(r + 0, (unsigned long long)n);
+        atomicAdd(r + 1, (unsigned long long)np);
+        atomicAdd(r + 2, (unsigned long long)nea);
+        atomicAdd(r + 3, (unsigned long long)neb);
+        atomicAdd(r + 4, ((unsigned long long)cah << 16) + cal);
+        atomicAdd(r + 5, ((unsigned long long)cbh << 16) + cbl);
+      }
+      if (mine) todo = false;
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < kAbWords; i += 256)
+    if (sT[i]) atomicAdd(a.table + i, sT[i]);
+}
+
+hipError_t launch_ab_share(const AbShareArgs& a, hipStream_t s) {
+  ab_share_kernel<<<(a.nb + 255) / 256, 256, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ab_report(const AbArgs& a, hipStream_t s) {
+  const uint32_t nchunks = (a.nb + kAbChunk - 1) / kAbChunk;
+  ab_report_kernel<<<std::min(nchunks, kAbGrid), 256, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace jxg

@@ -536,6 +536,54 @@ jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n
   return JXG_OK;
 }
 
+static jxg_status ab_report_entry(jxg_ctx* a, jxg_ctx* b, const void* orig, size_t orig_stride,
+                                  bool on_device, jxg_ab_report* out, int32_t* block_delta) {
+  if (!a || !b || !orig || !out) return JXG_ERR_INVALID_ARG;
+  Ctx *ca, *cb;
+  jxg_status st = ctx_enter(a, true, &ca);
+  if (!st) st = ctx_enter(b, true, &cb);
+  if (st) return st;
+  return guarded([&] {
+    return ab_report_pair(ca, cb, static_cast<const uint8_t*>(orig), orig_stride, on_device, out,
+                          block_delta);
+  });
+}
+
+jxg_status jxg_ab_report_rgb8(jxg_ctx* a, jxg_ctx* b, const uint8_t* orig, size_t orig_stride,
+                              jxg_ab_report* out, int32_t* block_delta) {
+  return ab_report_entry(a, b, orig, orig_stride, false, out, block_delta);
+}
+
+jxg_status jxg_ab_report_rgb8_device(jxg_ctx* a, jxg_ctx* b, const void* d_orig, size_t orig_stride,
+                                     jxg_ab_report* out, int32_t* d_block_delta) {
+  return ab_report_entry(a, b, d_orig, orig_stride, true, out, d_block_delta);
+}
+
+jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  if (!base || n == 0) {
+    c->sw.ab_base.clear();
+    return JXG_OK;
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (base[i] < -1 || base[i] >= (int32_t)i) return JXG_ERR_INVALID_ARG;
+  return guarded([&] {
+    c->sw.ab_base.assign(base, base + n);
+    return JXG_OK;
+  });
+}
+
+jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+  const Ctx::Sweep& sw = c->sw;
+  if (pipe_busy(c) || !sw.ab_have || n != sw.ab.size()) return JXG_ERR_INVALID_ARG;
+  std::copy(sw.ab.begin(), sw.ab.end(), out);
+  return JXG_OK;
+}
+
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {
   if (!ctx || !frame_args_ok(xsize, ysize, (size_t)xsize * 3)) return JXG_ERR_INVALID_ARG;
   Ctx* c;

@@ -13,6 +13,10 @@
 // flags apply to every point) and writes OUTDIR/<stem>-<distance>-<effort>.jxl,
 // the harness's names (benchmark.rs:644-650) -- its per-image loop without a
 // process start per setting.
+//
+// `--jxg_report=`, `--jxg_rates=` and `--jxg_ab=` (not cjxl options) append the
+// encode's strategy report, rate report and A/B report against the same encode
+// with other proposals as the CSV text of jxg/harness.py.
 #include <zlib.h>
 
 #include <charconv>
@@ -277,6 +281,40 @@ bool write_rate_rows(const char* path, const std::string& orig_name, const std::
   return std::fclose(f) == 0;
 }
 
+// --jxg_ab=FILE.csv: the rows of jxg/harness.py ab_stats / write_ab_stats for
+// one pair of encodes -- one per non-empty cell of the A/B report
+bool write_ab_rows(const char* path, const std::string& orig_name, const std::string& comp_a,
+                   const std::string& comp_b, float distance, int effort, const jxg_ab_report& rep,
+                   uint32_t w, uint32_t h) {
+  std::error_code ec;
+  const auto size = std::filesystem::file_size(path, ec);
+  const bool header = ec || size == 0;
+  FILE* f = std::fopen(path, header ? "w" : "a");
+  if (!f) return false;
+  if (header)
+    std::fputs("Original Image Name,Compressed Image Name A,Compressed Image Name B,Distance,"
+               "Effort,From,From Name,To,To Name,Blocks,Pixels,Area Share,SSE A,SSE B,Bits A,"
+               "Bits B,Diff SSE,Diff Bits\n", f);
+  for (int i = 0; i < JXG_NUM_STRATEGIES; i++)
+    for (int j = 0; j < JXG_NUM_STRATEGIES; j++) {
+      const jxg_ab_cell& c = rep.cell[i][j];
+      if (!c.blocks) continue;
+      std::fprintf(f, "%s,%s,%s,%s,%d,%d,%s,%d,%s,%llu,%llu,%s,%llu,%llu,%s,%s,%lld,%s\n",
+                   csv_field(orig_name).c_str(), csv_field(comp_a).c_str(),
+                   csv_field(comp_b).c_str(), rust_f32(distance).c_str(), effort, i,
+                   kStrategyNames[i], j, kStrategyNames[j], (unsigned long long)c.blocks,
+                   (unsigned long long)c.pixels,
+                   rust_f64((double)c.pixels / ((double)w * (double)h)).c_str(),
+                   (unsigned long long)c.sse_a, (unsigned long long)c.sse_b,
+                   rust_f64((double)c.cost_a / (double)JXG_RATE_UNIT).c_str(),
+                   rust_f64((double)c.cost_b / (double)JXG_RATE_UNIT).c_str(),
+                   (long long)c.sse_b - (long long)c.sse_a,
+                   rust_f64((double)((long long)c.cost_b - (long long)c.cost_a) /
+                            (double)JXG_RATE_UNIT).c_str());
+    }
+  return std::fclose(f) == 0;
+}
+
 struct SweepLine {
   double distance;
   int effort;
@@ -300,28 +338,39 @@ bool read_sweep_list(const char* path, std::vector<SweepLine>& out) {
 // INPUT at every point of the list -> OUTDIR/<stem>-<distance>-<effort>.jxl
 int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* outdir,
               const std::vector<SweepLine>& list, const std::vector<uint8_t>& rgb, uint32_t w,
-              uint32_t h, const char* report_path, const char* rates_path) {
-  const size_t n = list.size();
+              uint32_t h, const char* report_path, const char* rates_path, const char* ab_path,
+              uint32_t ab_base) {
+  // with --jxg_ab the list's points with the base proposals go in front: point
+  // m + i is the command line's own and is compared with point i
+  const size_t m = list.size(), o = ab_path ? m : 0, n = m + o;
   std::vector<jxg_sweep_point> pts(n);
-  for (size_t i = 0; i < n; i++)
-    pts[i] = jxg_sweep_point{(float)list[i].distance, list[i].effort, p.proposals, p.flags};
+  std::vector<int32_t> base(n, -1);
+  for (size_t i = 0; i < m; i++) {
+    pts[o + i] = jxg_sweep_point{(float)list[i].distance, list[i].effort, p.proposals, p.flags};
+    if (ab_path) {
+      pts[i] = jxg_sweep_point{(float)list[i].distance, list[i].effort, ab_base, p.flags};
+      base[o + i] = (int32_t)i;
+    }
+  }
+  const bool chain = report_path || ab_path;  // the points' chains run (quality 1)
   std::vector<jxg_buffer> outs(n, jxg_buffer{nullptr, 0});
   std::vector<jxg_status> sts(n, JXG_OK);
   // with a report the points' chains run (quality 1) and end in the reduction
-  std::vector<jxg_quality> qs(report_path ? n : 0);
+  std::vector<jxg_quality> qs(chain ? n : 0);
   std::vector<jxg_strategy_report> reps(report_path ? n : 0);
   if (report_path && jxg_set_sweep_report(ctx, 1) != JXG_OK) return 1;
   // (the rate reports need no chain: they follow each point's emission)
   std::vector<struct jxg_rate_report> rates(rates_path ? n : 0);
   if (rates_path && jxg_set_sweep_rates(ctx, 1) != JXG_OK) return 1;
+  std::vector<jxg_ab_report> abs(ab_path ? n : 0);
+  if (ab_path && jxg_set_sweep_ab(ctx, base.data(), (uint32_t)n) != JXG_OK) return 1;
   const auto t0 = std::chrono::steady_clock::now();
   const jxg_status st =
       jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(), (uint32_t)n,
-                     report_path ? 1 : 0, outs.data(), report_path ? qs.data() : nullptr,
-                     sts.data());
+                     chain ? 1 : 0, outs.data(), chain ? qs.data() : nullptr, sts.data());
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   bool any = false;
-  for (size_t i = 0; i < n; i++) any = any || outs[i].data;
+  for (size_t i = o; i < n; i++) any = any || outs[i].data;
   if (st != JXG_OK && !any) {
     std::fprintf(stderr, "sweep failed: %s\n", jxg_status_str(st));
     return 1;
@@ -334,19 +383,24 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
     std::fprintf(stderr, "sweep rates failed\n");
     return 1;
   }
+  if (ab_path && jxg_sweep_ab(ctx, abs.data(), (uint32_t)n) != JXG_OK) {
+    std::fprintf(stderr, "sweep A/B reports failed\n");
+    return 1;
+  }
   std::error_code ec;
   std::filesystem::create_directories(outdir, ec);
   const std::string stem = std::filesystem::path(input).stem().string();
   int rc = 0;
-  for (size_t i = 0; i < n; i++) {
+  for (size_t i = o; i < n; i++) {
+    const SweepLine& l = list[i - o];
     if (!outs[i].data) {  // a refused point: the harness skips it
-      std::fprintf(stderr, "distance %s effort %d: %s\n", rust_f64(list[i].distance).c_str(),
-                   list[i].effort, jxg_status_str(sts[i]));
+      std::fprintf(stderr, "distance %s effort %d: %s\n", rust_f64(l.distance).c_str(), l.effort,
+                   jxg_status_str(sts[i]));
       rc = 1;
       continue;
     }
     const std::string name =
-        stem + "-" + rust_f64(list[i].distance) + "-" + std::to_string(list[i].effort) + ".jxl";
+        stem + "-" + rust_f64(l.distance) + "-" + std::to_string(l.effort) + ".jxl";
     const std::string path = (std::filesystem::path(outdir) / name).string();
     if (report_path &&
         !write_report_rows(report_path, std::filesystem::path(input).filename().string(), name,
@@ -358,6 +412,12 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
         !write_rate_rows(rates_path, std::filesystem::path(input).filename().string(), name,
                          pts[i].distance, pts[i].effort, rates[i])) {
       std::fprintf(stderr, "cannot write %s\n", rates_path);
+      rc = 1;
+    }
+    if (ab_path &&
+        !write_ab_rows(ab_path, std::filesystem::path(input).filename().string(), name, name,
+                       pts[i].distance, pts[i].effort, abs[i], w, h)) {
+      std::fprintf(stderr, "cannot write %s\n", ab_path);
       rc = 1;
     }
     FILE* f = std::fopen(path.c_str(), "wb");
@@ -372,6 +432,7 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   }
   std::printf("Sweep of %zu points, %u x %u, %.2f MP/s\n", n, w, h,
               (double)n * w * h / 1e6 / sec);
+  for (size_t i = 0; i < o; i++) jxg_buffer_free(&outs[i]);  // (the base points' streams)
   return rc;
 }
 
@@ -383,7 +444,8 @@ int main(int argc, char** argv) {
                  "usage: %s INPUT OUTPUT [--distance=D] [--effort=E] "
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
                  "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH] "
-                 "[--jxg_report=FILE.csv] [--jxg_rates=FILE.csv]\n"
+                 "[--jxg_report=FILE.csv] [--jxg_rates=FILE.csv] "
+                 "[--jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF]]\n"
                  "       %s INPUT OUTDIR --sweep=LIST [the same flags]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
@@ -404,6 +466,12 @@ int main(int argc, char** argv) {
   // --jxg_rates=FILE.csv (not a cjxl option): append the coded bits per strategy
   // of the encode, or of every point of --sweep= (jxg_rate_report)
   const char* rates_path = nullptr;
+  // --jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF] (not cjxl options): the
+  // encode, or every point of --sweep=, is also run with the base proposals
+  // (default none) and the A/B report of the two (jxg_ab_report_rgb8; side B is
+  // --proposals) is appended; the codestreams written are unchanged
+  const char* ab_path = nullptr;
+  uint32_t ab_base = 0;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -451,7 +519,12 @@ int main(int argc, char** argv) {
       report_path = a + 13;
     else if (!std::strncmp(a, "--jxg_rates=", 12))
       rates_path = a + 12;
-    else {
+    else if (!std::strncmp(a, "--jxg_ab=", 9))
+      ab_path = a + 9;
+    else if (!std::strncmp(a, "--jxg_ab_base=", 14)) {
+      const char* v = a + 14;
+      ab_base = (std::strchr(v, 'P') ? JXG_PROPOSAL_P : 0u) | (std::strchr(v, 'F') ? JXG_PROPOSAL_F : 0u);
+    } else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
     }
@@ -534,7 +607,7 @@ int main(int argc, char** argv) {
   }
   if (sweep_path) {
     const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h, report_path,
-                             rates_path);
+                             rates_path, ab_path, ab_base);
     std::fflush(nullptr);
     std::_Exit(rc);  // (as below: no exit-time teardown)
   }
@@ -598,6 +671,26 @@ int main(int argc, char** argv) {
                          std::filesystem::path(argv[2]).filename().string(), p.distance, p.effort,
                          rates)) {
       std::fprintf(stderr, "cannot write %s\n", rates_path);
+      return fail(1);
+    }
+  }
+  if (ab_path) {
+    jxg_params pa = p;
+    pa.proposals = ab_base;
+    jxg_ctx* base = nullptr;
+    jxg_buffer out_a{};
+    jxg_ab_report ab{};
+    st = jxg_create(&pa, &base);
+    if (st == JXG_OK) st = jxg_encode_rgb8(base, rgb.data(), w, h, (size_t)w * 3, &out_a);
+    if (st == JXG_OK) st = jxg_ab_report_rgb8(base, ctx, rgb.data(), (size_t)w * 3, &ab, nullptr);
+    if (st != JXG_OK) {
+      std::fprintf(stderr, "A/B report failed: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    const std::string name = std::filesystem::path(argv[2]).filename().string();
+    if (!write_ab_rows(ab_path, std::filesystem::path(argv[1]).filename().string(), name, name,
+                       p.distance, p.effort, ab, w, h)) {
+      std::fprintf(stderr, "cannot write %s\n", ab_path);
       return fail(1);
     }
   }

@@ -246,6 +246,9 @@ void ctx_destroy(Ctx* c) {
   for (auto& e : c->sw.ev)
     if (e) (void)hipEventDestroy(e);
   if (c->sw.ev_pyr) (void)hipEventDestroy(c->sw.ev_pyr);
+  for (auto& e : c->sw.ab_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->ab.ev) (void)hipEventDestroy(c->ab.ev);
   if (c->rc.ev_sigma) (void)hipEventDestroy(c->rc.ev_sigma);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_write) (void)hipEventDestroy(c->ev_write);

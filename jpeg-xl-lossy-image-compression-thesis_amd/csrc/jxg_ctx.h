@@ -193,8 +193,8 @@ struct Ctx : EncArenas {
     uint32_t w = 0, h = 0;
   } rc;
   // rate report (jxg_rate_report, a sweep's lane; jxg_rate.cpp): the symbol
-  // cost table (uploaded once), the 27 x 6 table, the host variant's device
-  // map -- allocated by the first use -- and what the last finished encode of
+  // cost table (uploaded once), the 27 x 6 table, the device map of the host
+  // variant and of an A/B report -- allocated by the first use -- and what the last finished encode of
   // a whole frame left for it (rate_note): its coder, histograms, group count
   // and kernel geometry, the emitted AC bits, the codestream's bits.  The
   // records, code tables and strategy map are the context's own buffers
@@ -208,6 +208,16 @@ struct Ctx : EncArenas {
     uint32_t nhist = 0, groups = 0;
     uint64_t ac_bits = 0, stream_bits = 0;
   } rt;
+  // A/B report (jxg_ab_report_rgb8, a sweep's lane; jxg_ab.cpp), allocated by
+  // the first use: this side's cost shares, the 27 x 27 x 6 table and the host
+  // variant's delta planes (side B's context), the event side A's prepare step
+  // ends with
+  struct Ab {
+    DevBuf<uint32_t> share;
+    DevBuf<uint64_t> table;
+    DevBuf<int32_t> delta;
+    hipEvent_t ev = nullptr;
+  } ab;
   // decoder (jxg_decode_rgb8; jxg_decode_dev.cpp), allocated by its first
   // call: the codestream's words, the pass groups' section bounds, the AC
   // stream's decode tables [ctxmap | histograms | prefix or alias tables], the
@@ -260,6 +270,16 @@ struct Ctx : EncArenas {
     PinBuf<uint64_t> h_rate;
     std::vector<RateReport> rate;
     bool rate_have = false;  // the last sweep computed `rate`
+    // with jxg_set_sweep_ab: the base index of every point (empty: off), one
+    // snapshot slot [kAbSnapBytes per block] and one event per distinct
+    // baseline of the call, the comparing points' pinned tables [n][kAbWords],
+    // the last sweep's reports in point order
+    std::vector<int32_t> ab_base;
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>> ab_snap;
+    std::vector<hipEvent_t> ab_ev;
+    PinBuf<uint64_t> h_ab;
+    std::vector<jxg_ab_report> ab;
+    bool ab_have = false;  // the last sweep computed `ab`
   } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
@@ -413,6 +433,18 @@ struct SweepReq {
   // rate report behind the emission (any quality, with the switch on): pinned
   // [kRateWords], the table and the four scalars of jxg_rate_report
   uint64_t* h_rate = nullptr;
+  // A/B report (quality 1 / 2 with jxg_set_sweep_ab; jxg_ab.cpp).  ab: the
+  // point is a baseline or compares -- its chain writes the block error map and
+  // its rate kernel the cost map, whatever the two switches above say.  A
+  // baseline copies its triple to ab_snap and records ab_ev_snap; a comparing
+  // point waits for ab_ev_base, reduces ab_base against its own triple and
+  // copies the table to the pinned h_ab [kAbWords]
+  bool ab = false;
+  uint8_t* ab_snap = nullptr;
+  hipEvent_t ab_ev_snap = nullptr;
+  const uint8_t* ab_base = nullptr;
+  hipEvent_t ab_ev_base = nullptr;
+  uint64_t* h_ab = nullptr;
 };
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                        size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
@@ -514,6 +546,10 @@ jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride,
                                 jxg_strategy_report* out, uint32_t* block_sse);
 // the reduction alone, enqueued on c's stream: c->q.bsse -> c->q.rep (cleared first)
 jxg_status strategy_report_enqueue(Ctx* c, uint32_t w, uint32_t h);
+// the report's front half, enqueued on c's stream: the original to the device
+// (host variant: c->q.orig) and the chain ending in the block-map kernel ->
+// c->q.bsse, c->q.sse (JXG_ERR_INVALID_ARG as the report gives it)
+jxg_status block_sse_enqueue(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device);
 
 // ---- jxg_rate.cpp: coded bits per block and strategy ----
 // a pinned result of a sweep's point: the table, then ac_bits, stream_bits,
@@ -528,9 +564,24 @@ jxg_status rate_enqueue(Ctx* c, uint32_t w, uint32_t h, uint32_t* d_block_cost);
 // a sweep's point on its lane: the kernel, the table's copy to rq.h_rate and
 // the scalars beside it
 jxg_status sweep_rate_enqueue(Ctx* lane, const SweepReq& rq, uint32_t w, uint32_t h);
+// the device map of the host variant and of an A/B report's prepare step
+jxg_status rate_map_ensure(Ctx* c, uint32_t w, uint32_t h);
 void rate_from_words(const uint64_t* words, RateReport* out);
 // the report of the last one-at-a-time encode; block_cost host or device memory, or null
 jxg_status rate_report_last(Ctx* c, RateReport* out, uint32_t* block_cost, bool on_device);
+
+// ---- jxg_ab.cpp: A/B report of two encodes ----
+// a baseline's snapshot: per block the error word, the share, the strategy
+// byte -- [nb] u32 | [nb] u32 | [nb] u8
+constexpr size_t kAbSnapBytes = 9;
+// the cost-share pass on c's stream: c->rt.map (rate_enqueue with a map) and
+// c->acs -> c->ab.share
+jxg_status ab_share_enqueue(Ctx* c, uint32_t w, uint32_t h);
+// a sweep's point on its lane, behind its chain (block map) and its rate
+// kernel (cost map): the share pass, then the snapshot and / or the comparison
+jxg_status sweep_ab_enqueue(Ctx* lane, const SweepReq& rq, uint32_t w, uint32_t h);
+jxg_status ab_report_pair(Ctx* a, Ctx* b, const uint8_t* orig, size_t orig_stride, bool on_device,
+                          jxg_ab_report* out, int32_t* block_delta);
 
 // ---- jxg_decode_dev.cpp ----
 jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, size_t row_stride,

@@ -442,6 +442,28 @@ struct RateArgs {
 };
 // one workgroup per (group, band) as launch_ac_hist; whole_group as there
 hipError_t launch_rate(const RateArgs& a, uint32_t ngroups, bool whole_group, hipStream_t s);
+// A/B report of two encodes (jxg_ab.hip).  The share pass
+// turns one side's first-block cost map into a cost per block; the table is
+// jxg_ab_report's cells as u64 words [27 from][27 to][6: blocks, pixels, sse_a,
+// sse_b, cost_a, cost_b], added into (pre-zeroed)
+constexpr uint32_t kAbStrategies = 27, kAbCols = 6,
+                   kAbWords = kAbStrategies * kAbStrategies * kAbCols;
+struct AbShareArgs {
+  const uint8_t* acs;          // [nb] strategy bytes
+  const uint32_t* block_cost;  // [nb] RateArgs::block_cost
+  uint32_t* share;             // [nb] out, every word written
+  uint32_t bxs, nb;
+};
+hipError_t launch_ab_share(const AbShareArgs& a, hipStream_t s);
+struct AbArgs {
+  const uint8_t *acs_a, *acs_b;  // [nb] strategy bytes of the two sides
+  const uint32_t *sse_a, *sse_b;      // [nb] block error maps
+  const uint32_t *share_a, *share_b;  // [nb] cost shares (ab_share_kernel)
+  uint32_t w, h, bxs, nb;
+  int32_t* delta;              // [2][nb] out: sse_b - sse_a, share_b - share_a; or null
+  unsigned long long* table;   // [kAbWords]
+};
+hipError_t launch_ab_report(const AbArgs& a, hipStream_t s);
 // the decoder's pass groups (jxg_decode.hip): one wave per
 // group walks its section of the codestream with the decode core and writes
 // the non-zero coefficients into `ac` (it zeroes the group's area first)

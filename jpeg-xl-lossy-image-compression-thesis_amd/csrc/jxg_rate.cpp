@@ -78,9 +78,18 @@ void rate_from_words(const uint64_t* words, RateReport* out) {
   out->groups = (uint32_t)words[kRateCells + 3];
 }
 
+jxg_status rate_map_ensure(Ctx* c, uint32_t w, uint32_t h) {
+  const Frame f = make_frame(w, h, 1.0f);
+  JXG_HIP(c->rt.map.ensure((size_t)f.bxs * f.bys));
+  return JXG_OK;
+}
+
 jxg_status sweep_rate_enqueue(Ctx* S, const SweepReq& rq, uint32_t w, uint32_t h) {
-  const jxg_status st = rate_enqueue(S, w, h, nullptr);
-  if (st) return st;
+  // a point of an A/B comparison (jxg_ab.cpp) also needs the cost map, and
+  // runs the kernel whether or not the rate report is returned
+  jxg_status st = rq.ab ? rate_map_ensure(S, w, h) : JXG_OK;
+  if (!st) st = rate_enqueue(S, w, h, rq.ab ? S->rt.map.p : nullptr);
+  if (st || !rq.h_rate) return st;
   JXG_HIP(hipMemcpyAsync(rq.h_rate, S->rt.table.p, kRateCells * sizeof(uint64_t),
                          hipMemcpyDeviceToHost, S->stream));
   rq.h_rate[kRateCells] = S->rt.ac_bits;
@@ -102,7 +111,8 @@ jxg_status rate_report_last(Ctx* c, RateReport* out, uint32_t* block_cost, bool 
     if (st) return st;
     d_map = block_cost;
   } else if (block_cost) {
-    JXG_HIP(c->rt.map.ensure(nb));
+    const jxg_status st = rate_map_ensure(c, w, h);
+    if (st) return st;
     d_map = c->rt.map.p;
   }
   const jxg_status st = rate_enqueue(c, w, h, d_map);

@@ -177,8 +177,7 @@ jxg_status strategy_report_enqueue(Ctx* c, uint32_t w, uint32_t h) {
   return JXG_OK;
 }
 
-jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device,
-                                jxg_strategy_report* out, uint32_t* block_sse) {
+jxg_status block_sse_enqueue(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device) {
   const uint32_t w = c->rc.w, h = c->rc.h;
   if (!c->rc.ok || orig_stride < (size_t)w * 3) return JXG_ERR_INVALID_ARG;
   hipStream_t s = c->stream;
@@ -199,11 +198,20 @@ jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride,
   JXG_HIP(c->q.bsse.ensure(nb));
   JXG_HIP(hipMemsetAsync(c->q.sse.p, 0, sizeof(uint64_t), s));
   const ReconSse e{d_orig, so, c->q.sse.p, false, c->q.bsse.p};
-  jxg_status st = reconstruct_device(c, recon_frame_of_encode(w, h, c->params),
-                                     ReconMaps{c->acs.p, c->qf.p, c->dc.p, c->ac.p, c->cmap.p},
-                                     nullptr, so, &e);
-  if (!st) st = strategy_report_enqueue(c, w, h);
+  return reconstruct_device(c, recon_frame_of_encode(w, h, c->params),
+                            ReconMaps{c->acs.p, c->qf.p, c->dc.p, c->ac.p, c->cmap.p}, nullptr, so,
+                            &e);
+}
+
+jxg_status strategy_report_last(Ctx* c, const uint8_t* orig, size_t orig_stride, bool on_device,
+                                jxg_strategy_report* out, uint32_t* block_sse) {
+  jxg_status st = block_sse_enqueue(c, orig, orig_stride, on_device);
+  if (!st) st = strategy_report_enqueue(c, c->rc.w, c->rc.h);
   if (st) return st;
+  const uint32_t w = c->rc.w, h = c->rc.h;
+  hipStream_t s = c->stream;
+  const Frame f = make_frame(w, h, 1.0f);
+  const size_t nb = (size_t)f.bxs * f.bys;
   static_assert(sizeof(jxg_strategy_report) == kReportCells * sizeof(uint64_t), "table layout");
   JXG_HIP(hipMemcpyAsync(out, c->q.rep.p, sizeof(*out), hipMemcpyDeviceToHost, s));
   if (block_sse)

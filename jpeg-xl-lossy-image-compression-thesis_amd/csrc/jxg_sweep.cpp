@@ -18,6 +18,13 @@
 // With jxg_set_sweep_rates every point's lane prices its token records
 // (jxg_rate.hip) behind the codestream's copy -- ahead of the
 // metrics' end event with quality, alone with quality 0.
+// With jxg_set_sweep_ab (quality 1 / 2) a point some later point names as its
+// baseline copies its triple -- block errors, cost shares, strategy bytes, 9
+// bytes a block -- into a snapshot slot of the sweep (one per distinct
+// baseline, kept for the call: 4.7 MB per baseline at 8K) and records an
+// event; a comparing point's lane waits for it and reduces the snapshot against
+// its own triple (jxg_ab.hip); the table is one more pinned
+// result ahead of the metrics' end event.
 #include <cmath>
 #include <cstring>
 
@@ -40,10 +47,11 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(q.part.ensure(np));
     JXG_HIP(S->rc.rgb.ensure(row * h));
   }
-  if (rq.h_rep) JXG_HIP(q.bsse.ensure((size_t)((w + 7) / 8) * ((h + 7) / 8)));
+  const bool bmap = rq.h_rep || rq.ab;  // the block-map form of the chain's last kernel
+  if (bmap) JXG_HIP(q.bsse.ensure((size_t)((w + 7) / 8) * ((h + 7) / 8)));
   JXG_HIP(hipMemsetAsync(q.sse.p, 0, sizeof(uint64_t), s));
   JXG_HIP(hipEventRecord(rq.ev[0], s));
-  const ReconSse e{d_orig, so, q.sse.p, ssim, rq.h_rep ? q.bsse.p : nullptr};
+  const ReconSse e{d_orig, so, q.sse.p, ssim, bmap ? q.bsse.p : nullptr};
   const jxg_status st = reconstruct_device(
       S, recon_frame_of_encode(w, h, S->params),
       ReconMaps{S->acs.p, S->qf.p, S->dc.p, S->ac.p, S->cmap.p}, ssim ? S->rc.rgb.p : nullptr, row,
@@ -81,8 +89,12 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(hipMemcpyAsync(rq.h_rep, q.rep.p, kReportCells * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, s));
   }
-  if (rq.h_rate) {
+  if (rq.h_rate || rq.ab) {
     const jxg_status sr = sweep_rate_enqueue(S, rq, w, h);
+    if (sr) return sr;
+  }
+  if (rq.ab) {
+    const jxg_status sr = sweep_ab_enqueue(S, rq, w, h);
     if (sr) return sr;
   }
   JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -102,6 +114,8 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
                  jxg_quality* q, jxg_status* statuses) {
   const Clock::time_point t0 = Clock::now();
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;  // (nothing touched)
+  // jxg_set_sweep_ab names the base points of sweeps of exactly its n
+  if (!c->sw.ab_base.empty() && c->sw.ab_base.size() != n) return JXG_ERR_INVALID_ARG;
   std::vector<jxg_status> st(n, JXG_OK);
   std::vector<uint32_t> valid;
   jxg_status first = JXG_OK;
@@ -135,6 +149,11 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.rate_have = false;
   sw.rate.clear();
   if (rates) sw.rate.assign(n, RateReport{});
+  // the A/B reports ride on quality 1 / 2 (jxg_set_sweep_ab)
+  const bool ab = quality != 0 && !sw.ab_base.empty();
+  sw.ab_have = false;
+  sw.ab.clear();
+  if (ab) sw.ab.assign(n, jxg_ab_report{});
   // the context is lane 0 and encodes with its frames' points: its own
   // parameters are put back however the call ends
   const jxg_params saved = c->params;
@@ -156,6 +175,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     sw.ms.clear();
     sw.rep.clear();
     sw.rate.clear();
+    sw.ab.clear();
     return e;
   };
   if (nv) {
@@ -181,6 +201,32 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     if (report && sw.h_rep.ensure((size_t)nv * kReportCells) != hipSuccess)
       return fail(JXG_ERR_OOM);
     if (rates && sw.h_rate.ensure((size_t)nv * kRateWords) != hipSuccess) return fail(JXG_ERR_OOM);
+    // A/B: the comparisons whose two points are both valid, a snapshot slot and
+    // an event per distinct baseline (by its position among the valid points)
+    std::vector<int32_t> ab_of, ab_slot;  // per valid point: its baseline's position; its slot
+    if (ab) {
+      std::vector<int32_t> pos(n, -1);
+      for (uint32_t k = 0; k < nv; k++) pos[valid[k]] = (int32_t)k;
+      ab_of.assign(nv, -1);
+      ab_slot.assign(nv, -1);
+      uint32_t nslots = 0;
+      for (uint32_t k = 0; k < nv; k++) {
+        const int32_t bi = sw.ab_base[valid[k]];
+        if (bi < 0 || pos[bi] < 0) continue;  // (a refused baseline: the report stays zero)
+        ab_of[k] = pos[bi];
+        if (ab_slot[pos[bi]] < 0) ab_slot[pos[bi]] = (int32_t)nslots++;
+      }
+      const size_t snap = kAbSnapBytes * ((size_t)((w + 7) / 8) * ((h + 7) / 8));
+      while (sw.ab_snap.size() < nslots) sw.ab_snap.emplace_back(new DevBuf<uint8_t>());
+      for (uint32_t j = 0; j < nslots; j++)
+        if (sw.ab_snap[j]->ensure(snap) != hipSuccess) return fail(JXG_ERR_OOM);
+      while (sw.ab_ev.size() < nslots) {
+        hipEvent_t e = nullptr;
+        if (make_event(&e, hipEventDisableTiming) != hipSuccess) return fail(JXG_ERR_HIP);
+        sw.ab_ev.push_back(e);
+      }
+      if (sw.h_ab.ensure((size_t)nv * kAbWords) != hipSuccess) return fail(JXG_ERR_OOM);
+    }
     if (ms_run) {  // the original's pyramid, once: every lane reads it after ev_pyr
       if (sw.h_ms.ensure((size_t)nv * 2 * kMsScales) != hipSuccess ||
           sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess)
@@ -221,6 +267,8 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         msssim_nan(&sw.ms[i]);
       if (report)
         std::memcpy(&sw.rep[i], sw.h_rep.p + (size_t)k * kReportCells, sizeof(sw.rep[i]));
+      if (ab && ab_of[k] >= 0)
+        std::memcpy(&sw.ab[i], sw.h_ab.p + (size_t)k * kAbWords, sizeof(sw.ab[i]));
       sw.stats.ms_recon += elapsed(sw.ev[3 * k], sw.ev[3 * k + 1]);
       sw.stats.ms_metrics += elapsed(sw.ev[3 * k + 1], sw.ev[3 * k + 2]);
     };
@@ -243,6 +291,17 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       }
       if (report) rq.h_rep = sw.h_rep.p + (size_t)k * kReportCells;
       if (rates) rq.h_rate = sw.h_rate.p + (size_t)k * kRateWords;
+      if (ab && ab_slot[k] >= 0) {
+        rq.ab = true;
+        rq.ab_snap = sw.ab_snap[ab_slot[k]]->p;
+        rq.ab_ev_snap = sw.ab_ev[ab_slot[k]];
+      }
+      if (ab && ab_of[k] >= 0) {
+        rq.ab = true;
+        rq.ab_base = sw.ab_snap[ab_slot[ab_of[k]]]->p;
+        rq.ab_ev_base = sw.ab_ev[ab_slot[ab_of[k]]];
+        rq.h_ab = sw.h_ab.p + (size_t)k * kAbWords;
+      }
       e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
       // completed points whose copies have landed (or when more than two wait)
       while (!e && pipe_done_ready(c)) take();
@@ -257,6 +316,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.ms_have = ms;
   sw.rep_have = report;
   sw.rate_have = rates;
+  sw.ab_have = ab;
   sw.stats.ms_call = ms_since(t0);
   return first;
 }

@@ -152,6 +152,20 @@ class _RateReport(ctypes.Structure):
                 "ans": int(self.ans), "groups": int(self.groups), "names": STRATEGY_NAMES}
 
 
+class _AbReport(ctypes.Structure):
+    _fields_ = [("cell", ctypes.c_uint64 * (NUM_STRATEGIES * NUM_STRATEGIES * 6))]
+
+    _KEYS = ("blocks", "pixels", "sse_a", "sse_b", "cost_a", "cost_b")
+
+    def as_dict(self) -> dict:
+        """six ``[27, 27]`` uint64 arrays indexed ``[from, to]`` (costs in
+        1 / RATE_UNIT bit) + names"""
+        t = np.frombuffer(bytes(self), dtype=np.uint64).reshape(NUM_STRATEGIES, NUM_STRATEGIES, 6)
+        out = {k: t[:, :, i].copy() for i, k in enumerate(self._KEYS)}
+        out["names"] = STRATEGY_NAMES
+        return out
+
+
 def rate_symbol_cost(f: int) -> int:
     """jxg_rate_symbol_cost: an ANS symbol of normalised frequency f in 1 / 256 bit"""
     return int(load().jxg_rate_symbol_cost(f))
@@ -191,6 +205,8 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_set_sweep_report", "jxg_sweep_report",
            "jxg_rate_symbol_cost", "jxg_rate_report", "jxg_rate_report_device",
            "jxg_set_sweep_rates", "jxg_sweep_rates",
+           "jxg_ab_report_rgb8", "jxg_ab_report_rgb8_device",
+           "jxg_set_sweep_ab", "jxg_sweep_ab",
 )
 
 _lib = None
@@ -299,6 +315,11 @@ def load():
     lib.jxg_rate_report_device.argtypes = [vp, ctypes.POINTER(_RateReport), vp]
     lib.jxg_set_sweep_rates.argtypes = [vp, ctypes.c_int]
     lib.jxg_sweep_rates.argtypes = [vp, ctypes.POINTER(_RateReport), ctypes.c_uint32]
+    ab_args = [vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(_AbReport), vp]
+    lib.jxg_ab_report_rgb8.argtypes = ab_args
+    lib.jxg_ab_report_rgb8_device.argtypes = ab_args
+    lib.jxg_set_sweep_ab.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32]
+    lib.jxg_sweep_ab.argtypes = [vp, ctypes.POINTER(_AbReport), ctypes.c_uint32]
     _lib = lib
     return lib
 
@@ -629,7 +650,7 @@ class Encoder:
         return pts
 
     def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False,
-                    rates=False):
+                    rates=False, ab=None):
         if quality not in self._QUALITY:
             raise ValueError("quality: 'msssim', 'ssim', 'psnr' or None")
         level = self._QUALITY[quality]
@@ -638,13 +659,21 @@ class Encoder:
         ms = quality == "msssim"
         pts = self._sweep_points(points)
         n = len(pts)
+        if ab is not None:
+            ab = [int(v) for v in ab]
+            if not level:
+                raise ValueError("ab rides on a sweep's quality chain: quality must not be None")
+            if len(ab) != n:
+                raise ValueError("ab: one base index per point")
+            if any(v < -1 or v >= i for i, v in enumerate(ab)):
+                raise ValueError("ab: a base index is -1 or that of an earlier point")
         if n == 0:
             return []
         c_pts = (_SweepPoint * n)(*pts)
         outs = (_Buffer * n)()
         qs = (_Quality * n)() if level else None
         st = (ctypes.c_int * n)()
-        mss = reps = rts = None
+        mss = reps = rts = abs_ = None
         if ms:
             _check(load().jxg_set_sweep_msssim(self._ctx, 1))
         try:
@@ -652,6 +681,8 @@ class Encoder:
                 _check(load().jxg_set_sweep_report(self._ctx, 1))
             if rates:
                 _check(load().jxg_set_sweep_rates(self._ctx, 1))
+            if ab is not None:
+                _check(load().jxg_set_sweep_ab(self._ctx, (ctypes.c_int32 * n)(*ab), n))
             ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
             if strategies:
                 r = (_StrategyReport * n)()
@@ -661,6 +692,10 @@ class Encoder:
                 r = (_RateReport * n)()
                 if load().jxg_sweep_rates(self._ctx, r, n) == 0:
                     rts = r
+            if ab is not None:
+                r = (_AbReport * n)()
+                if load().jxg_sweep_ab(self._ctx, r, n) == 0:
+                    abs_ = r
             if ms:  # (a sweep that failed as a whole has none: ret is raised below)
                 m = (_Msssim * n)()
                 if load().jxg_sweep_msssim(self._ctx, m, n) == 0:
@@ -672,6 +707,8 @@ class Encoder:
                 load().jxg_set_sweep_report(self._ctx, 0)
             if rates:
                 load().jxg_set_sweep_rates(self._ctx, 0)
+            if ab is not None:
+                load().jxg_set_sweep_ab(self._ctx, None, 0)
         st = [int(v) for v in st]
         if ret != 0 and (strict or self._batch_call_failed(ret, st)):
             for i in range(n):
@@ -690,13 +727,15 @@ class Encoder:
                     q["cs"] = [float(v) for v in mss[i].cs]
                 if reps is not None:
                     q["strategies"] = reps[i].as_dict()
+                if abs_ is not None and ab[i] >= 0:
+                    q["ab"] = abs_[i].as_dict()
             if rts is not None:
                 q = dict(q or {}, rates=rts[i].as_dict())
             res.append((self._take(outs[i]), q))
         return res
 
     def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True,
-              strategies: bool = False, rates: bool = False) -> list:
+              strategies: bool = False, rates: bool = False, ab=None) -> list:
         """One host (H, W, 3) uint8 image encoded at every point of ``points``
         in one call (jxg_sweep_rgb8): the image is uploaded once and the points
         run through the streaming pipeline's lanes of this context, whose own
@@ -717,24 +756,29 @@ class Encoder:
         (jxg_set_sweep_report).  ``rates=True``: each point's dict gains
         ``"rates"``, the :meth:`rate_report` of that point, priced on its lane
         after its emission (jxg_set_sweep_rates); with ``quality=None`` the dict
-        holds only that.  Afterwards :meth:`reconstruct`
+        holds only that.  ``ab=[base indices]`` (one per point, -1 or the index
+        of an earlier point; not with ``quality=None``): the dict of every point
+        with a base >= 0 gains ``"ab"``, the :func:`ab_report` of the base point
+        (side A) and this point (side B), reduced on its lane against a snapshot
+        of the base point's maps (jxg_set_sweep_ab; all zero where the base
+        point was refused).  Afterwards :meth:`reconstruct`
         raises until the next :meth:`encode`."""
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("expected (H, W, 3) uint8")
         h, w = rgb.shape[:2]
         return self._sweep_call(load().jxg_sweep_rgb8, rgb.ctypes.data, w, h, w * 3, points,
-                                quality, strict, strategies, rates)
+                                quality, strict, strategies, rates, ab)
 
     def sweep_device(self, ptr: int, width: int, height: int, points, quality="ssim",
                      strict: bool = True, row_stride: int | None = None,
-                     strategies: bool = False, rates: bool = False) -> list:
+                     strategies: bool = False, rates: bool = False, ab=None) -> list:
         """:meth:`sweep` of a device-resident RGB8 image (rows of ``row_stride``
         bytes, default 3 * width), which must stay unchanged until the call
         returns (jxg_sweep_rgb8_device)."""
         return self._sweep_call(load().jxg_sweep_rgb8_device, ctypes.c_void_p(ptr), width, height,
                                 row_stride or width * 3, points, quality, strict, strategies,
-                                rates)
+                                rates, ab)
 
     def sweep_timings(self) -> dict:
         """The last :meth:`sweep` (jxg_sweep_timings): points encoded, lanes,
@@ -984,6 +1028,51 @@ class Encoder:
             self._ctx, ctypes.c_void_p(d_orig), orig_stride or width * 3, ctypes.c_void_p(d_comp),
             comp_stride or width * 3, width, height, ctypes.byref(m)))
         return m.as_dict()
+
+
+# ---------------------------------------------------------------------------
+# A/B report of two encodes (jxg_ab_report_rgb8)
+# ---------------------------------------------------------------------------
+def ab_report(enc_a: Encoder, enc_b: Encoder, orig: np.ndarray, block_delta: bool = False) -> dict:
+    """Strategy transitions between two encodes of ``orig``, the (H, W, 3) uint8
+    image both encoders encoded last with :meth:`Encoder.encode` /
+    :meth:`Encoder.encode_device` (jxg_ab_report_rgb8): a dict of ``[27, 27]``
+    uint64 arrays indexed ``[from, to]`` by the raw AcStrategy id a block's
+    varblock has in A and in B -- ``blocks``, ``pixels``, ``sse_a``, ``sse_b``
+    (the blocks' words of :meth:`Encoder.strategy_report`'s ``block_sse``),
+    ``cost_a``, ``cost_b`` (the blocks' shares of their varblocks' coded cost,
+    1 / ``RATE_UNIT`` bit: a varblock of cost C over n blocks gives block k, in
+    raster order, ``C // n + (k < C % n)``) -- and ``names``.  Exact integer
+    sums, reduced on the GPU.  ``block_delta=True`` adds ``block_delta``,
+    ``(2, bys, bxs)`` int32: ``sse_b - sse_a`` and ``cost_b - cost_a`` per
+    block.  ``enc_a is enc_b`` gives a diagonal table.  Raises JxgError where
+    :meth:`Encoder.reconstruct` does on either encoder, and for encodes of
+    different sizes."""
+    orig = np.ascontiguousarray(orig, dtype=np.uint8)
+    w, h = enc_a._last_wh or (1, 1)
+    if orig.shape != (h, w, 3):
+        raise ValueError("orig must be the (H, W, 3) uint8 image of the last encodes")
+    rep = _AbReport()
+    dmap = np.empty((2, (h + 7) // 8, (w + 7) // 8), dtype=np.int32) if block_delta else None
+    _check(load().jxg_ab_report_rgb8(enc_a._ctx, enc_b._ctx, orig.ctypes.data, w * 3,
+                                     ctypes.byref(rep), dmap.ctypes.data if block_delta else None))
+    out = rep.as_dict()
+    if block_delta:
+        out["block_delta"] = dmap
+    return out
+
+
+def ab_report_device(enc_a: Encoder, enc_b: Encoder, ptr: int, row_stride: int | None = None,
+                     block_delta_ptr: int | None = None) -> dict:
+    """:func:`ab_report` against a device-resident original (rows of
+    ``row_stride`` bytes, default 3 * width); ``block_delta_ptr``: device memory
+    for the ``(2, bys, bxs)`` int32 planes (jxg_ab_report_rgb8_device)."""
+    w, _ = enc_a._last_wh or (1, 1)
+    rep = _AbReport()
+    _check(load().jxg_ab_report_rgb8_device(
+        enc_a._ctx, enc_b._ctx, ctypes.c_void_p(ptr), row_stride or w * 3, ctypes.byref(rep),
+        ctypes.c_void_p(block_delta_ptr) if block_delta_ptr else None))
+    return rep.as_dict()
 
 
 # ---------------------------------------------------------------------------

@@ -30,7 +30,10 @@ rows -- one per (image, point, non-empty AC strategy) from the GPU's strategy
 report (Encoder.strategy_report) -- in ``strategy_stats.csv``,
 and ``compare_strategy_stats``, their A/B difference; ``RateStat`` rows -- one
 per (image, point, strategy that holds tokens) from the GPU's rate report
-(Encoder.rate_report): tokens and coded bits per channel.
+(Encoder.rate_report, DESIGN.md 3.17): tokens and coded bits per channel;
+``AbStat`` rows -- one per (image, pair of points, non-empty cell) from the
+GPU's A/B report (jxg.ab_report): the blocks that moved from
+one strategy to another between two encodes, with bits and error of both.
 """
 import csv
 import os
@@ -330,6 +333,85 @@ def read_rate_stats(file_name: str):
     return [RateStat.parse(r) for r in rows[1:] if r]
 
 
+AB_HEADER = [
+    "Original Image Name", "Compressed Image Name A", "Compressed Image Name B", "Distance",
+    "Effort", "From", "From Name", "To", "To Name", "Blocks", "Pixels", "Area Share", "SSE A",
+    "SSE B", "Bits A", "Bits B", "Diff SSE", "Diff Bits",
+]
+
+
+@dataclass
+class AbStat:
+    """One non-empty cell of an A/B report (jxg.ab_report / a sweep point's
+    ``"ab"``): the 8x8 blocks whose varblock has strategy
+    ``from`` in encode A and ``to`` in encode B, their squared error and their
+    shares of the coded bits (the report's cost / 256) on both sides, and B - A
+    of the two.  Distance and effort are B's."""
+    orig_image_name: str
+    comp_image_name_a: str
+    comp_image_name_b: str
+    distance: float  # f32
+    effort: int
+    from_strategy: int
+    from_name: str
+    to_strategy: int
+    to_name: str
+    blocks: int
+    pixels: int
+    area_share: float
+    sse_a: int
+    sse_b: int
+    bits_a: float
+    bits_b: float
+    diff_sse: int
+    diff_bits: float
+
+    _FLOATS = ("area_share", "bits_a", "bits_b", "diff_bits")
+
+    def row(self):
+        return [self.orig_image_name, self.comp_image_name_a, self.comp_image_name_b,
+                rust_f32(self.distance), str(self.effort), str(self.from_strategy), self.from_name,
+                str(self.to_strategy), self.to_name] + [
+                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
+                    else str(getattr(self, f.name)) for f in fields(self)[9:]]
+
+    @classmethod
+    def parse(cls, rec):
+        vals = [float(v) if f.name in cls._FLOATS else int(v)
+                for f, v in zip(fields(cls)[9:], rec[9:18])]
+        return cls(rec[0], rec[1], rec[2], float(np.float32(rec[3])), int(rec[4]), int(rec[5]),
+                   rec[6], int(rec[7]), rec[8], *vals)
+
+
+def ab_stats(orig_name: str, comp_name_a: str, comp_name_b: str, distance: float, effort: int,
+             report: dict, width: int, height: int):
+    """The AbStat rows of one report: its non-empty cells, by from id, then to id."""
+    rows = []
+    names = report["names"]
+    for f, t in np.argwhere(np.asarray(report["blocks"]) != 0):
+        f, t = int(f), int(t)
+        pixels = int(report["pixels"][f, t])
+        sse_a, sse_b = int(report["sse_a"][f, t]), int(report["sse_b"][f, t])
+        cost_a, cost_b = int(report["cost_a"][f, t]), int(report["cost_b"][f, t])
+        rows.append(AbStat(orig_name, comp_name_a, comp_name_b, float(np.float32(distance)),
+                           int(effort), f, names[f], t, names[t], int(report["blocks"][f, t]),
+                           pixels, float(pixels) / (float(width) * float(height)), sse_a, sse_b,
+                           float(cost_a) / 256.0, float(cost_b) / 256.0, sse_b - sse_a,
+                           float(cost_b - cost_a) / 256.0))
+    return rows
+
+
+def write_ab_stats(rows, ab_file: str) -> None:
+    write_csv_header(ab_file, AB_HEADER)
+    write_csv(rows, ab_file)
+
+
+def read_ab_stats(file_name: str):
+    with open(file_name, newline="") as f:
+        rows = list(csv.reader(f))
+    return [AbStat.parse(r) for r in rows[1:] if r]
+
+
 _DIFF_FIELDS = [f.name for f in fields(ComparisonResult)[4:]]
 
 
@@ -452,7 +534,8 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
 
 def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
                       result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False,
-                      strategy_file: str | None = None, rate_file: str | None = None):
+                      strategy_file: str | None = None, rate_file: str | None = None,
+                      ab_file: str | None = None, ab_base=None):
     """The harness's per-image loop (benchmark.rs:637-677) in one call: the
     image is encoded at every point (dicts with ``distance`` / ``effort`` and
     optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
@@ -468,7 +551,12 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     row per non-empty strategy is appended to that file (strategy_stats.csv).
     ``rate_file``: every point's rate report is priced on its lane
     (``rates=True``) and one RateStat row per strategy that holds tokens is
-    appended to that file."""
+    appended to that file.  ``ab_file`` with ``ab_base`` (one base index per
+    point: -1, or the index of an earlier point): every point with a base is
+    compared with it on its lane (``ab=ab_base``) and one AbStat row per
+    non-empty cell of that A/B report is appended to that file."""
+    if (ab_file is None) != (ab_base is None):
+        raise ValueError("ab_file and ab_base go together")
     if ms_ssim and not ssim:
         raise ValueError("ms_ssim rides on the quality-2 sweep: it needs ssim=True")
     o = np.ascontiguousarray(orig_rgb, dtype=np.uint8)
@@ -477,11 +565,17 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     h, w = o.shape[:2]
     points = list(points)
     res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr",
-                        strategies=strategy_file is not None, rates=rate_file is not None)
+                        strategies=strategy_file is not None, rates=rate_file is not None,
+                        **({} if ab_base is None else {"ab": list(ab_base)}))
     stem = os.path.splitext(orig_name)[0]
     raw = w * h * 3
     datas, records = [], []
-    for p, (data, q) in zip(points, res):
+
+    def name_of(p):
+        d, e = (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
+        return comp_image_name(stem, d, e)
+
+    for i, (p, (data, q)) in enumerate(zip(points, res)):
         d, e = (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
         datas.append(data)
         records.append(_record(orig_name, comp_image_name(stem, d, e), d, e, orig_file_size,
@@ -492,4 +586,7 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
         if rate_file is not None:
             write_rate_stats(rate_stats(orig_name, comp_image_name(stem, d, e), d, e, q["rates"]),
                              rate_file)
+        if ab_file is not None and ab_base[i] >= 0:
+            write_ab_stats(ab_stats(orig_name, name_of(points[ab_base[i]]), name_of(p), d, e,
+                                    q["ab"], w, h), ab_file)
     return datas, records

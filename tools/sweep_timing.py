@@ -25,7 +25,13 @@ only the switch-off rows are measured, for the comparison on one box.
 `sweep_device` at quality 0 and 1 with jxg_set_sweep_rates off and on,
 alternating; then the kernel alone -- the ms_metrics (events) of a one-point
 sweep, switch on minus off -- and the wall time of rate_report_device.  On a
-library without the switch only the switch-off rows are measured."""
+library without the switch only the switch-off rows are measured.
+--ab: the cost of the A/B reports: the grid as a 100-point
+`sweep_device` at quality 1 -- 50 base points, then 50 P+F points each compared
+with its base -- with jxg_set_sweep_ab off and on, alternating; then the added
+kernels alone by the events of a two-point sweep, and the wall time of
+ab_report_device after two encodes.  On a library without the switch only the
+switch-off rows are measured."""
 import argparse
 import json
 import os
@@ -274,6 +280,101 @@ def rates(args):
         del d_img
 
 
+def ab(args):
+    import torch
+
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8_device
+
+    has_switch = hasattr(jxg.load(), "jxg_set_sweep_ab")
+    grid = [(d, e) for d in DISTANCES for e in EFFORTS]
+    flags = jxg.FLAGS_CJXL_DEFAULTS
+    # 50 base points, then 50 P+F points each compared with its base
+    points = [dict(distance=d, effort=e, proposals=0, flags=flags) for d, e in grid] + \
+             [dict(distance=d, effort=e, proposals=3, flags=flags) for d, e in grid]
+    base = [-1] * len(grid) + list(range(len(grid)))
+    two = [dict(distance=1.0, effort=7, proposals=0, flags=flags),
+           dict(distance=1.0, effort=7, proposals=3, flags=flags)]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        d_img = synth_rgb8_device(w, h, SEED_BASE + seed, 0)
+        torch.cuda.synchronize()
+        sweeper = jxg.Encoder()
+
+        def sweep(on, pts=points, bs=base, **kw):
+            if on:
+                kw["ab"] = bs
+            return sweeper.sweep_device(d_img.data_ptr(), w, h, pts, quality="psnr", **kw)
+
+        want = sweep(False)  # warm, all buffers
+        if has_switch:
+            got = sweep(True)
+            assert [g[0] for g in got] == [r[0] for r in want], "bytes differ with the switch on"
+            for g in got[len(grid):]:
+                assert int(g[1]["ab"]["pixels"].sum()) == w * h
+                assert int(g[1]["ab"]["sse_b"].sum()) == g[1]["sse"]
+        modes = (False, True) if has_switch else (False,)
+        wall = {m: [] for m in modes}
+        split = {m: [] for m in modes}
+        for rep in range(args.reps + 1):
+            for m in modes:
+                t0 = time.perf_counter()
+                sweep(m)
+                t1 = time.perf_counter()
+                if rep:
+                    wall[m].append((t1 - t0) * 1e3)
+                    split[m].append(sweeper.sweep_timings())
+        res = {"frame": name, "ab": True, "library": os.path.relpath(jxg.LIB_PATH, ROOT),
+               "quality": 1, "points": len(points), "reps": args.reps,
+               "queues": os.environ.get("GPU_MAX_HW_QUEUES", "default"),
+               "lanes": sweeper.sweep_timings()["lanes"]}
+        for m in modes:
+            mid = sorted(range(len(wall[m])), key=lambda i: wall[m][i])[len(wall[m]) // 2]
+            key = "on" if m else "off"
+            res["ms_wall_" + key] = spread(wall[m])
+            res["ms_recon_" + key] = round(split[m][mid]["ms_recon"], 3)
+            res["ms_metrics_" + key] = round(split[m][mid]["ms_metrics"], 3)
+        if has_switch:
+            res["ms_added_per_pair"] = round(
+                (statistics.median(wall[True]) - statistics.median(wall[False])) / len(grid), 4)
+        print(json.dumps(res), flush=True)
+        if has_switch:
+            # the kernels alone, by the events around the metrics of a two-point
+            # sweep (d1 e7, none then P+F), alternating.  Against a plain sweep:
+            # everything the switch adds (block-map form, rate kernel with its map,
+            # two share passes, the snapshot, the transition kernel, the table's
+            # copy).  Against a sweep that already runs the strategy and rate
+            # reports: the share passes, the snapshot and the transition kernel.
+            ms = {k: [] for k in ("plain", "plain_ab", "reports", "reports_ab")}
+            for rep in range(4 * args.reps + 1):
+                for k in ms:
+                    kw = {"strategies": True, "rates": True} if k.startswith("reports") else {}
+                    sweep(k.endswith("_ab"), two, [-1, 0], **kw)
+                    if rep:
+                        ms[k].append(sweeper.sweep_timings()["ms_metrics"])
+            with jxg.Encoder(**two[0]) as ea, jxg.Encoder(**two[1]) as eb:
+                ea.encode_device(d_img.data_ptr(), w, h)
+                eb.encode_device(d_img.data_ptr(), w, h)
+                moved = jxg.ab_report_device(ea, eb, d_img.data_ptr())["blocks"]
+                call = []
+                for rep in range(4 * args.reps):
+                    t0 = time.perf_counter()
+                    jxg.ab_report_device(ea, eb, d_img.data_ptr())
+                    call.append((time.perf_counter() - t0) * 1e3)
+            print(json.dumps({
+                "frame": name, "ab": True, "pair": "d1 e7 none -> PF",
+                "blocks": int(moved.sum()), "blocks_moved": int(moved.sum() - moved.trace()),
+                "cells": int((moved != 0).sum()),
+                "ms_metrics": {k: spread(v) for k, v in ms.items()},
+                "ms_all_added_by_events": round(statistics.median(ms["plain_ab"]) -
+                                                statistics.median(ms["plain"]), 4),
+                "ms_share_snapshot_transition_by_events": round(
+                    statistics.median(ms["reports_ab"]) - statistics.median(ms["reports"]), 4),
+                "ms_ab_report_call_wall": spread(call)}), flush=True)
+        sweeper.close()
+        del d_img
+
+
 def cli(args):
     import jxg
     from jxg.synth import SEED_BASE, synth_rgb8
@@ -320,6 +421,7 @@ def main():
     ap.add_argument("--cli", action="store_true")
     ap.add_argument("--strategies", action="store_true")
     ap.add_argument("--rates", action="store_true")
+    ap.add_argument("--ab", action="store_true")
     args = ap.parse_args()
     if not 0 <= args.queues <= 32:
         ap.error("--queues: at most 32 hardware queues (0: leave the environment's)")
@@ -333,6 +435,8 @@ def main():
         return strategies(args)
     if args.rates:
         return rates(args)
+    if args.ab:
+        return ab(args)
     library(args)
 
 
