@@ -87,8 +87,18 @@ typedef enum {
 /* opaque encoder context (one HIP device, its streams and buffers) */
 typedef struct jxg_ctx jxg_ctx;
 
+/* The bottom of the distance range.  0 < distance <= 25 is accepted (<= 0, NaN
+ * and > 25 are JXG_ERR_INVALID_ARG); a context or a sweep point computes with
+ * the effective distance max(distance, JXG_MIN_DISTANCE).  Below about 1e-4
+ * everything derived from the distance is already at its clamp (global scale
+ * 73727, raw quant field 256, quant_dc), so any two distances <= 1e-6 give the
+ * same bytes, and no codestream of a distance >= 1e-6 depends on the floor.
+ * It keeps the quant field's float -> int conversion (qf_base * inv_g < 2^21)
+ * inside int range; without it a distance below ~3.3e-10 overflowed it. */
+#define JXG_MIN_DISTANCE 1e-6f
+
 typedef struct {
-  float distance;      /* cjxl --distance (butteraugli target), (0, 25] */
+  float distance;      /* cjxl --distance (butteraugli target), (0, 25]; see JXG_MIN_DISTANCE */
   int effort;          /* cjxl --effort 1..9 (>=5: 8x8-class ACS search) */
   uint32_t proposals;  /* JXG_PROPOSAL_* */
   int num_devices;     /* informative; multi-GPU runs one context per rank */
@@ -528,7 +538,7 @@ jxg_status jxg_decode_batch_timings(jxg_ctx* ctx, jxg_decode_batch_stats* stats)
  * (and any other failure of the pipeline) are call-level: every output is
  * released and every status filled. */
 typedef struct {
-  float distance;
+  float distance; /* (0, 25], computed with max(distance, JXG_MIN_DISTANCE) */
   int effort;
   uint32_t proposals;
   uint32_t flags;

@@ -3,6 +3,7 @@
 #include "jxg_ctx.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 
 #include "jxg_tables.h"
@@ -200,9 +201,11 @@ jxg_status ctx_new_lane(const jxg_params& params, Ctx** out) {
   return JXG_OK;
 }
 
-jxg_status ctx_create(const jxg_params& params, Ctx** out) {
+jxg_status ctx_create(const jxg_params& requested, Ctx** out) {
   *out = nullptr;
-  if (!(params.distance > 0.0f) || params.distance > 25.0f) return JXG_ERR_INVALID_ARG;
+  if (!(requested.distance > 0.0f) || requested.distance > 25.0f) return JXG_ERR_INVALID_ARG;
+  jxg_params params = requested;  // the effective distance (jxg.h JXG_MIN_DISTANCE)
+  params.distance = std::fmax(requested.distance, JXG_MIN_DISTANCE);
   if (params.effort < 1 || params.effort > 10) return JXG_ERR_INVALID_ARG;
   if (params.proposals & ~3u) return JXG_ERR_INVALID_ARG;
   int ndev = 0;

@@ -275,7 +275,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     for (uint32_t k = 0; k < nv && !e; k++) {
       SweepReq rq;
       rq.params = saved;
-      rq.params.distance = points[valid[k]].distance;
+      rq.params.distance = std::fmax(points[valid[k]].distance, JXG_MIN_DISTANCE);  // as ctx_create
       rq.params.effort = points[valid[k]].effort;
       rq.params.proposals = points[valid[k]].proposals;
       rq.params.flags = points[valid[k]].flags;

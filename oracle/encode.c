@@ -679,6 +679,10 @@ int jxo_encode_rgb8(const uint8_t* rgb, uint32_t w, uint32_t h, size_t row_strid
   if (!(p->distance > 0.0f) || p->distance > 25.0f) return -2;
   if (p->coder != 0 && p->coder != 1) return -3;
   if (p->filters & ~(JXO_FILTER_GAB | JXO_FILTER_EPF | JXO_OPT_AQ_MASKING)) return -4;
+  /* the effective distance (jxo.h JXO_MIN_DISTANCE): everything below reads pe */
+  jxo_params pe = *p;
+  pe.distance = jxo_effective_distance(p->distance);
+  p = &pe;
   jxo_frame f;
   jxo_frame_init(&f, w, h, p);
   const size_t plane = (size_t)f.xp * f.yp, nb = (size_t)f.bxs * f.bys;
@@ -826,6 +830,9 @@ int jxo_encode_maps(uint32_t w, uint32_t h, const jxo_params* p, const uint8_t* 
   if (!(p->distance > 0.0f) || p->distance > 25.0f) return -2;
   if (p->coder != 0 && p->coder != 1) return -3;
   if (p->filters & ~(JXO_FILTER_GAB | JXO_FILTER_EPF | JXO_OPT_AQ_MASKING)) return -4;
+  jxo_params pe = *p; /* the effective distance, as in jxo_encode_rgb8 */
+  pe.distance = jxo_effective_distance(p->distance);
+  p = &pe;
   jxo_frame f;
   jxo_frame_init(&f, w, h, p);
   const size_t nb = (size_t)f.bxs * f.bys;

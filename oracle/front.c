@@ -370,7 +370,11 @@ static inline float tree8(const float* v) {
   return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
 /* dead zone 0.58, round half up, clamp to int16 (the coefficient storage
- * type of the GPU path; |q| <= 32767 holds for distance >= ~0.05) */
+ * type of the GPU path).  The clamp is live: a full-range step edge reaches
+ * +-32767 in merged varblocks from distance 0.004 down and in 8x8-class blocks
+ * at 0.001 (tests/highrate_cases.py); the magnitude equals the kernels'
+ * floorf(fminf(a, 32767) + 0.5f) for every float, inf and NaN (-> 32767)
+ * included (tests/test_quant_identities.py) */
 static inline int quant1(float v) {
   float a = fabsf(v);
   if (a < 0.58f) return 0;

@@ -58,8 +58,22 @@ void jxo_homog_map(const jxo_xyb* img, float distance, int h1_mode, float* r3,
                    uint8_t* type);
 
 /* ---------------- full encoder oracle (encode.c) ---------------- */
+/* The bottom of the distance range.  A request is valid for 0 < distance <= 25
+ * (<= 0, NaN and > 25 are refused); the encoder computes with the effective
+ * distance max(distance, JXO_MIN_DISTANCE).  Below about 1e-4 every quantity
+ * derived from the distance is already at its clamp (global scale 73727, raw
+ * quant field 256, quant_dc), so the floor changes no codestream of a distance
+ * >= 1e-6; it keeps qf_base * inv_g (front.c, aq.c) below 2^21, where the
+ * float -> int conversion is defined.  Without it a distance below ~3.3e-10
+ * made that conversion overflow (undefined behaviour; raw came out as 1, the
+ * coarsest field, on x86). */
+#define JXO_MIN_DISTANCE 1e-6f
+static inline float jxo_effective_distance(float distance) {
+  return distance < JXO_MIN_DISTANCE ? JXO_MIN_DISTANCE : distance;
+}
+
 typedef struct {
-  float distance;
+  float distance;     /* (0, 25]; computed with jxo_effective_distance() */
   int effort;
   uint32_t proposals; /* bit0 = P (homogeneity-partitioning), bit1 = F */
   int coder;          /* 0 = prefix codes, 1 = ANS */

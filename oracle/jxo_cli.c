@@ -3,6 +3,8 @@
  * (P6, 8-bit) with the CPU restatement.  Mirrors the cjxl argv shape used by
  * benchmark-jpegxl/src/docker_manager.rs:126-136.
  *   jxo_cli in.ppm out.jxl --distance=D --effort=E [--proposals=none|P|F|PF]
+ *           [--coder=prefix|ans] [--filters=MASK]   (MASK: jxo.h JXO_FILTER_* |
+ *           JXO_OPT_AQ_MASKING; 7 with --coder=ans is cjxl's defaults)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,7 +44,8 @@ int main(int argc, char** argv) {
     else if (!strncmp(argv[i], "--proposals=", 12)) {
       const char* v = argv[i] + 12;
       p.proposals = (strchr(v, 'P') ? 1u : 0u) | (strchr(v, 'F') ? 2u : 0u);
-    }
+    } else if (!strncmp(argv[i], "--coder=", 8)) p.coder = !strcmp(argv[i] + 8, "ans");
+    else if (!strncmp(argv[i], "--filters=", 10)) p.filters = (uint32_t)atoi(argv[i] + 10);
   }
   uint32_t w, h;
   uint8_t* rgb = read_ppm(argv[1], &w, &h);
