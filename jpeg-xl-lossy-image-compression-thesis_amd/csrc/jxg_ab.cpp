@@ -86,7 +86,7 @@ jxg_status sweep_ab_enqueue(Ctx* S, const SweepReq& rq, uint32_t w, uint32_t h) 
   const size_t nb = (size_t)f.bxs * f.bys;
   const jxg_status st = ab_share_enqueue(S, w, h);
   if (st) return st;
-  if (rq.h_ab) {
+  if (rq.h[kRiderAb]) {
     // The baseline's event has been recorded by now: quality chains are
     // enqueued in submission order (pipe_complete_oldest) and the baseline
     // comes earlier in point order, so this is never a wait for an event
@@ -95,7 +95,7 @@ jxg_status sweep_ab_enqueue(Ctx* S, const SweepReq& rq, uint32_t w, uint32_t h) 
     const uint32_t* sse_a = reinterpret_cast<const uint32_t*>(rq.ab_base);
     const jxg_status sr = ab_reduce(S, rq.ab_base + 8 * nb, sse_a, sse_a + nb, w, h, nullptr);
     if (sr) return sr;
-    JXG_HIP(hipMemcpyAsync(rq.h_ab, S->ab.table.p, kAbWords * sizeof(uint64_t),
+    JXG_HIP(hipMemcpyAsync(rq.h[kRiderAb], S->ab.table.p, kAbWords * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, s));
   }
   if (rq.ab_snap) {  // a baseline of later points: the lane's next frame overwrites the triple

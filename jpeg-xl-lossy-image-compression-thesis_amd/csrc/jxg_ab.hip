@@ -51,17 +51,10 @@ __global__ __launch_bounds__(256) void ab_share_kernel(AbShareArgs a) {
   a.share[b] = (C >> lcb) + (k < (C & ((1u << lcb) - 1u)) ? 1u : 0u);
 }
 
-__device__ __forceinline__ uint32_t ab_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void ab_report_kernel(AbArgs a) {
   __shared__ unsigned long long sT[kAbWords];
-  for (uint32_t i = threadIdx.x; i < kAbWords; i += 256) sT[i] = 0;
+  lds_table_zero<256>(sT, kAbWords);
   __syncthreads();
-  const uint32_t lane = threadIdx.x & 63;
   const uint32_t nchunks = (a.nb + kAbChunk - 1) / kAbChunk;
   for (uint32_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const uint32_t b = ch * kAbChunk + threadIdx.x;
@@ -84,33 +77,20 @@ __global__ __launch_bounds__(256) void ab_report_kernel(AbArgs a) {
       todo = from < kAbStrategies && to < kAbStrategies;
       pair = from * kAbStrategies + to;
     }
-    while (true) {
-      const unsigned long long m = __ballot(todo);
-      if (!m) break;
-      const int src = __ffsll((long long)m) - 1;
-      const uint32_t p0 = (uint32_t)__shfl((int)pair, src, 64);
-      const bool mine = todo && pair == p0;
-      const uint32_t n = ab_wave_sum(mine ? 1u : 0u), np = ab_wave_sum(mine ? px : 0u),
-                     nea = ab_wave_sum(mine ? ea : 0u), neb = ab_wave_sum(mine ? eb : 0u),
-                     cal = ab_wave_sum(mine ? ca & 0xFFFFu : 0u),
-                     cah = ab_wave_sum(mine ? ca >> 16 : 0u),
-                     cbl = ab_wave_sum(mine ? cb & 0xFFFFu : 0u),
-                     cbh = ab_wave_sum(mine ? cb >> 16 : 0u);
-      if ((int)lane == src) {
-        unsigned long long* r = sT + p0 * kAbCols;
-        atomicAdd(r + 0, (unsigned long long)n);
-        atomicAdd(r + 1, (unsigned long long)np);
-        atomicAdd(r + 2, (unsigned long long)nea);
-        atomicAdd(r + 3, (unsigned long long)neb);
-        atomicAdd(r + 4, ((unsigned long long)cah << 16) + cal);
-        atomicAdd(r + 5, ((unsigned long long)cbh << 16) + cbl);
-      }
-      if (mine) todo = false;
-    }
+    // (the shares' low and high halves apart: a wave's sum of either fits u32)
+    const uint32_t v[8] = {1u, px, ea, eb, ca & 0xFFFFu, ca >> 16, cb & 0xFFFFu, cb >> 16};
+    wave_sum_by_key(todo, pair, v, [&](uint32_t p0, const uint32_t* s) {
+      unsigned long long* r = sT + p0 * kAbCols;
+      atomicAdd(r + 0, (unsigned long long)s[0]);
+      atomicAdd(r + 1, (unsigned long long)s[1]);
+      atomicAdd(r + 2, (unsigned long long)s[2]);
+      atomicAdd(r + 3, (unsigned long long)s[3]);
+      atomicAdd(r + 4, ((unsigned long long)s[5] << 16) + s[4]);
+      atomicAdd(r + 5, ((unsigned long long)s[7] << 16) + s[6]);
+    });
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < kAbWords; i += 256)
-    if (sT[i]) atomicAdd(a.table + i, sT[i]);
+  lds_table_flush<256>(sT, a.table, kAbWords);
 }
 
 hipError_t launch_ab_share(const AbShareArgs& a, hipStream_t s) {

@@ -8,6 +8,35 @@
 
 using namespace jxg;
 
+// ---- a sweep's riders (kRiderRules): one switch, one getter ----
+// a rider's switch (A/B: its base indices, none when off)
+static jxg_status sweep_switch(jxg_ctx* ctx, Rider r, bool on, const int32_t* base = nullptr,
+                               uint32_t n = 0) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
+  return guarded([&] {
+    if (r == kRiderAb) c->sw.ab_base.assign(base, base + (on ? n : 0));
+    c->sw.rider[r].on = on;
+    return JXG_OK;
+  });
+}
+
+// a rider's results of the last sweep.  while_pending: jxg_sweep_msssim alone
+// answers while frames are pending; the later getters refuse.  The difference
+// is the ABI's as it stands and is kept here, not decided
+template <class T>
+static jxg_status sweep_results(jxg_ctx* ctx, Rider r, T* out, uint32_t n,
+                                bool while_pending = false) {
+  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
+  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+  const Ctx::Sweep::RiderSlot& sl = c->sw.rider[r];
+  if ((!while_pending && pipe_busy(c)) || !sl.have || (size_t)n * sizeof(T) != sl.out.size())
+    return JXG_ERR_INVALID_ARG;
+  std::memcpy(out, sl.out.data(), sl.out.size());
+  return JXG_OK;
+}
+
 extern "C" {
 
 const char* jxg_status_str(jxg_status s) {
@@ -455,36 +484,32 @@ jxg_status jxg_sweep_timings(jxg_ctx* ctx, jxg_sweep_stats* stats) {
 }
 
 jxg_status jxg_set_sweep_msssim(jxg_ctx* ctx, int on) {
-  if (!ctx) return JXG_ERR_INVALID_ARG;
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
-  c->sw.msssim = on != 0;
-  return JXG_OK;
+  return sweep_switch(ctx, kRiderMsssim, on != 0);
 }
-
 jxg_status jxg_sweep_msssim(jxg_ctx* ctx, jxg_msssim* out, uint32_t n) {
-  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
-  const Ctx::Sweep& sw = reinterpret_cast<const Ctx*>(ctx)->sw;
-  if (!sw.ms_have || n != sw.ms.size()) return JXG_ERR_INVALID_ARG;
-  std::copy(sw.ms.begin(), sw.ms.end(), out);
-  return JXG_OK;
+  return sweep_results(ctx, kRiderMsssim, out, n, /*while_pending=*/true);
 }
-
 jxg_status jxg_set_sweep_report(jxg_ctx* ctx, int on) {
-  if (!ctx) return JXG_ERR_INVALID_ARG;
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
-  c->sw.report = on != 0;
-  return JXG_OK;
+  return sweep_switch(ctx, kRiderReport, on != 0);
 }
-
 jxg_status jxg_sweep_report(jxg_ctx* ctx, jxg_strategy_report* out, uint32_t n) {
-  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
-  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-  const Ctx::Sweep& sw = c->sw;
-  if (pipe_busy(c) || !sw.rep_have || n != sw.rep.size()) return JXG_ERR_INVALID_ARG;
-  std::copy(sw.rep.begin(), sw.rep.end(), out);
-  return JXG_OK;
+  return sweep_results(ctx, kRiderReport, out, n);
+}
+jxg_status jxg_set_sweep_rates(jxg_ctx* ctx, int on) {
+  return sweep_switch(ctx, kRiderRates, on != 0);
+}
+jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n) {
+  return sweep_results(ctx, kRiderRates, out, n);
+}
+// a base index is -1 or that of an earlier point; null or no indices: off
+jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n) {
+  if (!base) n = 0;
+  for (uint32_t i = 0; i < n; i++)
+    if (base[i] < -1 || base[i] >= (int32_t)i) return JXG_ERR_INVALID_ARG;
+  return sweep_switch(ctx, kRiderAb, n != 0, base, n);
+}
+jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n) {
+  return sweep_results(ctx, kRiderAb, out, n);
 }
 
 jxg_status jxg_strategy_report_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
@@ -519,23 +544,6 @@ jxg_status jxg_rate_report_device(jxg_ctx* ctx, struct jxg_rate_report* out, uin
   return st ? st : rate_report_last(c, out, d_block_cost, true);
 }
 
-jxg_status jxg_set_sweep_rates(jxg_ctx* ctx, int on) {
-  if (!ctx) return JXG_ERR_INVALID_ARG;
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
-  c->sw.rates = on != 0;
-  return JXG_OK;
-}
-
-jxg_status jxg_sweep_rates(jxg_ctx* ctx, struct jxg_rate_report* out, uint32_t n) {
-  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
-  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-  const Ctx::Sweep& sw = c->sw;
-  if (pipe_busy(c) || !sw.rate_have || n != sw.rate.size()) return JXG_ERR_INVALID_ARG;
-  std::copy(sw.rate.begin(), sw.rate.end(), out);
-  return JXG_OK;
-}
-
 static jxg_status ab_report_entry(jxg_ctx* a, jxg_ctx* b, const void* orig, size_t orig_stride,
                                   bool on_device, jxg_ab_report* out, int32_t* block_delta) {
   if (!a || !b || !orig || !out) return JXG_ERR_INVALID_ARG;
@@ -557,31 +565,6 @@ jxg_status jxg_ab_report_rgb8(jxg_ctx* a, jxg_ctx* b, const uint8_t* orig, size_
 jxg_status jxg_ab_report_rgb8_device(jxg_ctx* a, jxg_ctx* b, const void* d_orig, size_t orig_stride,
                                      jxg_ab_report* out, int32_t* d_block_delta) {
   return ab_report_entry(a, b, d_orig, orig_stride, true, out, d_block_delta);
-}
-
-jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n) {
-  if (!ctx) return JXG_ERR_INVALID_ARG;
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
-  if (!base || n == 0) {
-    c->sw.ab_base.clear();
-    return JXG_OK;
-  }
-  for (uint32_t i = 0; i < n; i++)
-    if (base[i] < -1 || base[i] >= (int32_t)i) return JXG_ERR_INVALID_ARG;
-  return guarded([&] {
-    c->sw.ab_base.assign(base, base + n);
-    return JXG_OK;
-  });
-}
-
-jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n) {
-  if (!ctx || !out) return JXG_ERR_INVALID_ARG;
-  const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-  const Ctx::Sweep& sw = c->sw;
-  if (pipe_busy(c) || !sw.ab_have || n != sw.ab.size()) return JXG_ERR_INVALID_ARG;
-  std::copy(sw.ab.begin(), sw.ab.end(), out);
-  return JXG_OK;
 }
 
 jxg_status jxg_warmup(jxg_ctx* ctx, uint32_t xsize, uint32_t ysize) {

@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -223,25 +224,42 @@ std::string csv_field(const std::string& v) {  // (Python's csv module, minimal 
   }
   return q + "\"";
 }
-bool write_report_rows(const char* path, const std::string& orig_name,
-                       const std::string& comp_name, float distance, int effort,
-                       const jxg_strategy_report& rep, uint32_t w, uint32_t h) {
+// a report's CSV, opened for appending rows: the header goes only into a
+// missing or empty file
+FILE* open_csv(const char* path, const char* header) {
   std::error_code ec;
   const auto size = std::filesystem::file_size(path, ec);
-  const bool header = ec || size == 0;
-  FILE* f = std::fopen(path, header ? "w" : "a");
+  const bool fresh = ec || size == 0;
+  FILE* f = std::fopen(path, fresh ? "w" : "a");
+  if (f && fresh) std::fputs(header, f);
+  return f;
+}
+// whose rows: the original's name, the compressed name, distance, effort -- the
+// columns every row of a report starts with (A/B: the compressed name twice,
+// sides A and B)
+struct RowKey {
+  std::string orig_name, comp_name;
+  float distance;
+  int effort;
+  std::string lead(bool ab = false) const {
+    return csv_field(orig_name) + "," + csv_field(comp_name) + "," +
+           (ab ? csv_field(comp_name) + "," : "") + rust_f32(distance) + "," +
+           std::to_string(effort);
+  }
+};
+bool write_report_rows(const char* path, const RowKey& key, const jxg_strategy_report& rep,
+                       uint32_t w, uint32_t h) {
+  FILE* f = open_csv(path,
+                     "Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
+                     "Varblocks,Blocks,Pixels,Area Share,Nonzeros X,Nonzeros Y,Nonzeros B,"
+                     "Mean Quant Field,SSE,MSE\n");
   if (!f) return false;
-  if (header)
-    std::fputs("Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
-               "Varblocks,Blocks,Pixels,Area Share,Nonzeros X,Nonzeros Y,Nonzeros B,"
-               "Mean Quant Field,SSE,MSE\n", f);
+  const std::string lead = key.lead();
   for (int i = 0; i < JXG_NUM_STRATEGIES; i++) {
     const jxg_strategy_row& r = rep.row[i];
     if (!r.blocks) continue;
-    std::fprintf(f, "%s,%s,%s,%d,%d,%s,%llu,%llu,%llu,%s,%llu,%llu,%llu,%s,%llu,%s\n",
-                 csv_field(orig_name).c_str(), csv_field(comp_name).c_str(),
-                 rust_f32(distance).c_str(), effort, i, kStrategyNames[i],
-                 (unsigned long long)r.varblocks, (unsigned long long)r.blocks,
+    std::fprintf(f, "%s,%d,%s,%llu,%llu,%llu,%s,%llu,%llu,%llu,%s,%llu,%s\n", lead.c_str(), i,
+                 kStrategyNames[i], (unsigned long long)r.varblocks, (unsigned long long)r.blocks,
                  (unsigned long long)r.pixels,
                  rust_f64((double)r.pixels / ((double)w * (double)h)).c_str(),
                  (unsigned long long)r.nonzeros[0], (unsigned long long)r.nonzeros[1],
@@ -255,23 +273,18 @@ bool write_report_rows(const char* path, const std::string& orig_name,
 
 // --jxg_rates=FILE.csv: the rows of jxg/harness.py rate_stats / write_rate_stats
 // for one encode -- one per strategy of the rate report that holds tokens
-bool write_rate_rows(const char* path, const std::string& orig_name, const std::string& comp_name,
-                     float distance, int effort, const struct jxg_rate_report& rep) {
-  std::error_code ec;
-  const auto size = std::filesystem::file_size(path, ec);
-  const bool header = ec || size == 0;
-  FILE* f = std::fopen(path, header ? "w" : "a");
+bool write_rate_rows(const char* path, const RowKey& key, const struct jxg_rate_report& rep) {
+  FILE* f = open_csv(path,
+                     "Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
+                     "Tokens X,Tokens Y,Tokens B,Bits X,Bits Y,Bits B,AC Bits,Stream Bits\n");
   if (!f) return false;
-  if (header)
-    std::fputs("Original Image Name,Compressed Image Name,Distance,Effort,Strategy,Name,"
-               "Tokens X,Tokens Y,Tokens B,Bits X,Bits Y,Bits B,AC Bits,Stream Bits\n", f);
+  const std::string lead = key.lead();
   for (int i = 0; i < JXG_NUM_STRATEGIES; i++) {
     const jxg_rate_row& r = rep.row[i];
     if (!(r.tokens[0] + r.tokens[1] + r.tokens[2])) continue;
-    std::fprintf(f, "%s,%s,%s,%d,%d,%s,%llu,%llu,%llu,%s,%s,%s,%llu,%llu\n",
-                 csv_field(orig_name).c_str(), csv_field(comp_name).c_str(),
-                 rust_f32(distance).c_str(), effort, i, kStrategyNames[i],
-                 (unsigned long long)r.tokens[0], (unsigned long long)r.tokens[1],
+    std::fprintf(f, "%s,%d,%s,%llu,%llu,%llu,%s,%s,%s,%llu,%llu\n", lead.c_str(), i,
+                 kStrategyNames[i], (unsigned long long)r.tokens[0],
+                 (unsigned long long)r.tokens[1],
                  (unsigned long long)r.tokens[2],
                  rust_f64((double)r.cost[0] / (double)JXG_RATE_UNIT).c_str(),
                  rust_f64((double)r.cost[1] / (double)JXG_RATE_UNIT).c_str(),
@@ -283,25 +296,19 @@ bool write_rate_rows(const char* path, const std::string& orig_name, const std::
 
 // --jxg_ab=FILE.csv: the rows of jxg/harness.py ab_stats / write_ab_stats for
 // one pair of encodes -- one per non-empty cell of the A/B report
-bool write_ab_rows(const char* path, const std::string& orig_name, const std::string& comp_a,
-                   const std::string& comp_b, float distance, int effort, const jxg_ab_report& rep,
-                   uint32_t w, uint32_t h) {
-  std::error_code ec;
-  const auto size = std::filesystem::file_size(path, ec);
-  const bool header = ec || size == 0;
-  FILE* f = std::fopen(path, header ? "w" : "a");
+bool write_ab_rows(const char* path, const RowKey& key, const jxg_ab_report& rep, uint32_t w,
+                   uint32_t h) {
+  FILE* f = open_csv(path,
+                     "Original Image Name,Compressed Image Name A,Compressed Image Name B,Distance,"
+                     "Effort,From,From Name,To,To Name,Blocks,Pixels,Area Share,SSE A,SSE B,Bits A,"
+                     "Bits B,Diff SSE,Diff Bits\n");
   if (!f) return false;
-  if (header)
-    std::fputs("Original Image Name,Compressed Image Name A,Compressed Image Name B,Distance,"
-               "Effort,From,From Name,To,To Name,Blocks,Pixels,Area Share,SSE A,SSE B,Bits A,"
-               "Bits B,Diff SSE,Diff Bits\n", f);
+  const std::string lead = key.lead(true);
   for (int i = 0; i < JXG_NUM_STRATEGIES; i++)
     for (int j = 0; j < JXG_NUM_STRATEGIES; j++) {
       const jxg_ab_cell& c = rep.cell[i][j];
       if (!c.blocks) continue;
-      std::fprintf(f, "%s,%s,%s,%s,%d,%d,%s,%d,%s,%llu,%llu,%s,%llu,%llu,%s,%s,%lld,%s\n",
-                   csv_field(orig_name).c_str(), csv_field(comp_a).c_str(),
-                   csv_field(comp_b).c_str(), rust_f32(distance).c_str(), effort, i,
+      std::fprintf(f, "%s,%d,%s,%d,%s,%llu,%llu,%s,%llu,%llu,%s,%s,%lld,%s\n", lead.c_str(), i,
                    kStrategyNames[i], j, kStrategyNames[j], (unsigned long long)c.blocks,
                    (unsigned long long)c.pixels,
                    rust_f64((double)c.pixels / ((double)w * (double)h)).c_str(),
@@ -357,13 +364,32 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   std::vector<jxg_status> sts(n, JXG_OK);
   // with a report the points' chains run (quality 1) and end in the reduction
   std::vector<jxg_quality> qs(chain ? n : 0);
+  // the report kinds that ride on the sweep (the rate reports need no chain:
+  // they follow each point's emission): file, name in messages, switch, getter,
+  // the rows of point i
   std::vector<jxg_strategy_report> reps(report_path ? n : 0);
-  if (report_path && jxg_set_sweep_report(ctx, 1) != JXG_OK) return 1;
-  // (the rate reports need no chain: they follow each point's emission)
   std::vector<struct jxg_rate_report> rates(rates_path ? n : 0);
-  if (rates_path && jxg_set_sweep_rates(ctx, 1) != JXG_OK) return 1;
   std::vector<jxg_ab_report> abs(ab_path ? n : 0);
-  if (ab_path && jxg_set_sweep_ab(ctx, base.data(), (uint32_t)n) != JXG_OK) return 1;
+  const std::string orig_name = std::filesystem::path(input).filename().string();
+  const uint32_t un = (uint32_t)n;
+  struct Rider {
+    const char *path, *what;
+    std::function<jxg_status()> set, fetch;
+    std::function<bool(const RowKey&, size_t)> write;
+  };
+  const Rider riders[] = {
+      {report_path, "report", [&] { return jxg_set_sweep_report(ctx, 1); },
+       [&] { return jxg_sweep_report(ctx, reps.data(), un); },
+       [&](const RowKey& k, size_t i) { return write_report_rows(report_path, k, reps[i], w, h); }},
+      {rates_path, "rates", [&] { return jxg_set_sweep_rates(ctx, 1); },
+       [&] { return jxg_sweep_rates(ctx, rates.data(), un); },
+       [&](const RowKey& k, size_t i) { return write_rate_rows(rates_path, k, rates[i]); }},
+      {ab_path, "A/B reports", [&] { return jxg_set_sweep_ab(ctx, base.data(), un); },
+       [&] { return jxg_sweep_ab(ctx, abs.data(), un); },
+       [&](const RowKey& k, size_t i) { return write_ab_rows(ab_path, k, abs[i], w, h); }},
+  };
+  for (const Rider& r : riders)
+    if (r.path && r.set() != JXG_OK) return 1;
   const auto t0 = std::chrono::steady_clock::now();
   const jxg_status st =
       jxg_sweep_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, pts.data(), (uint32_t)n,
@@ -375,18 +401,11 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
     std::fprintf(stderr, "sweep failed: %s\n", jxg_status_str(st));
     return 1;
   }
-  if (report_path && jxg_sweep_report(ctx, reps.data(), (uint32_t)n) != JXG_OK) {
-    std::fprintf(stderr, "sweep report failed\n");
-    return 1;
-  }
-  if (rates_path && jxg_sweep_rates(ctx, rates.data(), (uint32_t)n) != JXG_OK) {
-    std::fprintf(stderr, "sweep rates failed\n");
-    return 1;
-  }
-  if (ab_path && jxg_sweep_ab(ctx, abs.data(), (uint32_t)n) != JXG_OK) {
-    std::fprintf(stderr, "sweep A/B reports failed\n");
-    return 1;
-  }
+  for (const Rider& r : riders)
+    if (r.path && r.fetch() != JXG_OK) {
+      std::fprintf(stderr, "sweep %s failed\n", r.what);
+      return 1;
+    }
   std::error_code ec;
   std::filesystem::create_directories(outdir, ec);
   const std::string stem = std::filesystem::path(input).stem().string();
@@ -402,24 +421,12 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
     const std::string name =
         stem + "-" + rust_f64(l.distance) + "-" + std::to_string(l.effort) + ".jxl";
     const std::string path = (std::filesystem::path(outdir) / name).string();
-    if (report_path &&
-        !write_report_rows(report_path, std::filesystem::path(input).filename().string(), name,
-                           pts[i].distance, pts[i].effort, reps[i], w, h)) {
-      std::fprintf(stderr, "cannot write %s\n", report_path);
-      rc = 1;
-    }
-    if (rates_path &&
-        !write_rate_rows(rates_path, std::filesystem::path(input).filename().string(), name,
-                         pts[i].distance, pts[i].effort, rates[i])) {
-      std::fprintf(stderr, "cannot write %s\n", rates_path);
-      rc = 1;
-    }
-    if (ab_path &&
-        !write_ab_rows(ab_path, std::filesystem::path(input).filename().string(), name, name,
-                       pts[i].distance, pts[i].effort, abs[i], w, h)) {
-      std::fprintf(stderr, "cannot write %s\n", ab_path);
-      rc = 1;
-    }
+    const RowKey key{orig_name, name, pts[i].distance, pts[i].effort};
+    for (const Rider& r : riders)
+      if (r.path && !r.write(key, i)) {
+        std::fprintf(stderr, "cannot write %s\n", r.path);
+        rc = 1;
+      }
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f || std::fwrite(outs[i].data, 1, outs[i].size, f) != outs[i].size) {
       std::fprintf(stderr, "cannot write %s\n", path.c_str());
@@ -646,6 +653,8 @@ int main(int argc, char** argv) {
       return fail(1);
     }
   }
+  const RowKey key{std::filesystem::path(argv[1]).filename().string(),
+                   std::filesystem::path(argv[2]).filename().string(), p.distance, p.effort};
   if (report_path) {
     jxg_strategy_report rep{};
     st = jxg_strategy_report_rgb8(ctx, rgb.data(), (size_t)w * 3, &rep, nullptr);
@@ -653,9 +662,7 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "strategy report failed: %s\n", jxg_status_str(st));
       return fail(1);
     }
-    if (!write_report_rows(report_path, std::filesystem::path(argv[1]).filename().string(),
-                           std::filesystem::path(argv[2]).filename().string(), p.distance,
-                           p.effort, rep, w, h)) {
+    if (!write_report_rows(report_path, key, rep, w, h)) {
       std::fprintf(stderr, "cannot write %s\n", report_path);
       return fail(1);
     }
@@ -667,9 +674,7 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "rate report failed: %s\n", jxg_status_str(st));
       return fail(1);
     }
-    if (!write_rate_rows(rates_path, std::filesystem::path(argv[1]).filename().string(),
-                         std::filesystem::path(argv[2]).filename().string(), p.distance, p.effort,
-                         rates)) {
+    if (!write_rate_rows(rates_path, key, rates)) {
       std::fprintf(stderr, "cannot write %s\n", rates_path);
       return fail(1);
     }
@@ -687,9 +692,7 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "A/B report failed: %s\n", jxg_status_str(st));
       return fail(1);
     }
-    const std::string name = std::filesystem::path(argv[2]).filename().string();
-    if (!write_ab_rows(ab_path, std::filesystem::path(argv[1]).filename().string(), name, name,
-                       p.distance, p.effort, ab, w, h)) {
+    if (!write_ab_rows(ab_path, key, ab, w, h)) {
       std::fprintf(stderr, "cannot write %s\n", ab_path);
       return fail(1);
     }

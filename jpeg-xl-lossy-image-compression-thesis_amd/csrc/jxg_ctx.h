@@ -108,6 +108,18 @@ enum EncEvent : int {
 
 // (include/jxg.h: the report shares its name with the call that fills it)
 using RateReport = struct ::jxg_rate_report;
+// a sweep's riders: the optional per-point results of jxg_sweep_rgb8, each with
+// a switch (jxg_set_sweep_*), a getter (jxg_sweep_*) and a slot in Ctx::Sweep
+enum Rider { kRiderMsssim, kRiderReport, kRiderRates, kRiderAb, kRiders };
+// what differs between them besides their enqueue functions (kRiderRules,
+// jxg_sweep.cpp): a rider rides on sweeps of quality >= min_quality; a point
+// stages `words` pinned 8-byte words, which rider_convert turns into its public
+// struct of out_bytes
+struct RiderRule {
+  int min_quality;
+  size_t words, out_bytes;
+};
+extern const RiderRule kRiderRules[kRiders];
 struct Ctx;
 struct Job;
 struct Pipe;
@@ -243,43 +255,28 @@ struct Ctx : EncArenas {
     jxg_decode_batch_stats stats{};
   } decb;
   // sweep (jxg_sweep_rgb8; jxg_sweep.cpp): the host variant's device image,
-  // the points' pinned results [n][2] and events [n][3], the last call's stats.
-  // With jxg_set_sweep_msssim: the original's pyramid (built once per sweep on
-  // this context's stream, read by every lane after ev_pyr), the points' pinned
-  // window sums [n][10], the last sweep's results in point order
+  // the points' pinned results [n][2] and events [n][3], the last call's stats,
+  // and one slot per rider (the optional per-point results; kRiderRules).
+  // MS-SSIM's extras: the original's pyramid, built once per sweep on this
+  // context's stream and read by every lane after ev_pyr.  A/B's extras: the
+  // base index of every point (empty: off), one snapshot slot [kAbSnapBytes per
+  // block] and one event per distinct baseline of the call
   struct Sweep {
     DevBuf<uint8_t> rgb;
     PinBuf<uint64_t> h_q;
     std::vector<hipEvent_t> ev;
     jxg_sweep_stats stats{};
-    bool msssim = false;  // the switch
+    struct RiderSlot {
+      bool on = false;           // the switch (jxg_set_sweep_*)
+      PinBuf<uint64_t> h;        // the valid points' pinned words [nv][rule.words]
+      std::vector<uint8_t> out;  // the last sweep's public structs [n], in point order
+      bool have = false;         // the last sweep computed `out`
+    } rider[kRiders];
     DevBuf<float> pyr_o;
     hipEvent_t ev_pyr = nullptr;
-    PinBuf<double> h_ms;
-    std::vector<jxg_msssim> ms;
-    bool ms_have = false;  // the last sweep computed `ms`
-    // with jxg_set_sweep_report: the points' pinned tables [n][27 * 8], the
-    // last sweep's reports in point order
-    bool report = false;  // the switch
-    PinBuf<uint64_t> h_rep;
-    std::vector<jxg_strategy_report> rep;
-    bool rep_have = false;  // the last sweep computed `rep`
-    // with jxg_set_sweep_rates: the points' pinned results [n][kRateWords],
-    // the last sweep's rate reports in point order
-    bool rates = false;  // the switch
-    PinBuf<uint64_t> h_rate;
-    std::vector<RateReport> rate;
-    bool rate_have = false;  // the last sweep computed `rate`
-    // with jxg_set_sweep_ab: the base index of every point (empty: off), one
-    // snapshot slot [kAbSnapBytes per block] and one event per distinct
-    // baseline of the call, the comparing points' pinned tables [n][kAbWords],
-    // the last sweep's reports in point order
     std::vector<int32_t> ab_base;
     std::vector<std::unique_ptr<DevBuf<uint8_t>>> ab_snap;
     std::vector<hipEvent_t> ab_ev;
-    PinBuf<uint64_t> h_ab;
-    std::vector<jxg_ab_report> ab;
-    bool ab_have = false;  // the last sweep computed `ab`
   } sw;
   // the concat kernel's inputs (stage_concat / stage_concat_split, the shard
   // assemblers)
@@ -421,30 +418,24 @@ struct SweepReq {
   int quality = 0;         // 0 none, 1 sse, 2 also ssim
   uint64_t* h_q = nullptr;  // pinned [2]: sse, the SSIM sum's bits
   hipEvent_t* ev = nullptr;  // [3]: chain start, chain end, metrics end
-  // MS-SSIM behind the SSIM kernels (quality 2 with the switch on, frames of
-  // kMsMinEdge and more): pinned [10] window sums, the original's pyramid and
-  // the event it is complete after
-  double* h_ms = nullptr;
+  // the riders' pinned slices, null where a rider does not run on this point:
+  // [10] window sums behind the SSIM kernels, the [kReportCells] table behind
+  // the metrics, [kRateWords] behind the emission, the [kAbWords] table of a
+  // comparing point
+  uint64_t* h[kRiders] = {};
+  // MS-SSIM: the original's pyramid and the event it is complete after
   const float* pyr_o = nullptr;
   hipEvent_t ev_pyr = nullptr;
-  // strategy report behind the metrics (quality 1 / 2 with the switch on):
-  // pinned [kReportCells] table
-  uint64_t* h_rep = nullptr;
-  // rate report behind the emission (any quality, with the switch on): pinned
-  // [kRateWords], the table and the four scalars of jxg_rate_report
-  uint64_t* h_rate = nullptr;
-  // A/B report (quality 1 / 2 with jxg_set_sweep_ab; jxg_ab.cpp).  ab: the
-  // point is a baseline or compares -- its chain writes the block error map and
-  // its rate kernel the cost map, whatever the two switches above say.  A
-  // baseline copies its triple to ab_snap and records ab_ev_snap; a comparing
-  // point waits for ab_ev_base, reduces ab_base against its own triple and
-  // copies the table to the pinned h_ab [kAbWords]
+  // A/B report (jxg_ab.cpp).  ab: the point is a baseline or compares -- its
+  // chain writes the block error map and its rate kernel the cost map, whatever
+  // the report and rate switches say.  A baseline copies its triple to ab_snap
+  // and records ab_ev_snap; a comparing point waits for ab_ev_base and reduces
+  // ab_base against its own triple
   bool ab = false;
   uint8_t* ab_snap = nullptr;
   hipEvent_t ab_ev_snap = nullptr;
   const uint8_t* ab_base = nullptr;
   hipEvent_t ab_ev_base = nullptr;
-  uint64_t* h_ab = nullptr;
 };
 jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                        size_t stride, uint32_t rank = 0, uint32_t world = 1, bool shard = false,
@@ -561,7 +552,7 @@ void rate_note(Ctx* c, const Job& J);
 // the kernel alone, enqueued on c's stream: c->rt.table (cleared first) and,
 // when d_block_cost is not null, the map of the w x h frame c encoded last
 jxg_status rate_enqueue(Ctx* c, uint32_t w, uint32_t h, uint32_t* d_block_cost);
-// a sweep's point on its lane: the kernel, the table's copy to rq.h_rate and
+// a sweep's point on its lane: the kernel, the table's copy to rq.h[kRiderRates] and
 // the scalars beside it
 jxg_status sweep_rate_enqueue(Ctx* lane, const SweepReq& rq, uint32_t w, uint32_t h);
 // the device map of the host variant and of an A/B report's prepare step

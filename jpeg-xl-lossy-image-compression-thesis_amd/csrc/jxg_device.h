@@ -275,4 +275,48 @@ struct BitSink {
   __device__ __forceinline__ void finish() { flush_word((uint32_t)acc, n); }
 };
 
+// ---- integer reductions of the report kernels (jxg_report / jxg_rate / jxg_ab.hip) ----
+// the sum of v over the wave's 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// A wave's sums by key (blocks of 1-D workgroups of whole waves; every lane
+// calls it).  Neighbouring lanes mostly share a key, so the wave takes the key
+// of its first lane with `todo`, sums the N values over the lanes of that key
+// and has that lane call f(key, sums); then the next key still present.  The
+// caller sees to it that a wave's sums fit u32.
+template <int N, class F>
+__device__ __forceinline__ void wave_sum_by_key(bool todo, uint32_t key, const uint32_t (&v)[N],
+                                                F f) {
+  const int lane = (int)(threadIdx.x & 63);
+  while (true) {
+    const unsigned long long m = __ballot(todo);
+    if (!m) break;
+    const int src = __ffsll((long long)m) - 1;
+    const uint32_t key0 = (uint32_t)__shfl((int)key, src, 64);
+    const bool mine = todo && key == key0;
+    uint32_t s[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) s[i] = wave_sum(mine ? v[i] : 0u);
+    if (lane == src) f(key0, s);
+    if (mine) todo = false;
+  }
+}
+
+// a workgroup's table of 64-bit sums in LDS, THREADS lanes wide: cleared (a
+// barrier follows at the caller), and its non-empty cells added to the global one
+template <uint32_t THREADS>
+__device__ __forceinline__ void lds_table_zero(unsigned long long* sT, uint32_t cells) {
+  for (uint32_t i = threadIdx.x; i < cells; i += THREADS) sT[i] = 0;
+}
+template <uint32_t THREADS>
+__device__ __forceinline__ void lds_table_flush(const unsigned long long* sT,
+                                                unsigned long long* table, uint32_t cells) {
+  for (uint32_t i = threadIdx.x; i < cells; i += THREADS)
+    if (sT[i]) atomicAdd(table + i, sT[i]);
+}
+
 }  // namespace jxg

@@ -285,7 +285,7 @@ static jxg_status pipe_complete_oldest(Ctx* c) {
     // codestream's copy, under the other lanes' chains; nothing waited for here
     if (!st && fr.sweep && fr.rq.quality)
       st = sweep_quality_enqueue(fr.lane, fr.rq, fr.J.d_rgb, fr.J.stride, fr.J.w, fr.J.h);
-    else if (!st && fr.sweep && fr.rq.h_rate)  // (with quality: inside, ahead of the metrics' end)
+    else if (!st && fr.sweep && fr.rq.h[kRiderRates])  // (with quality: inside, ahead of ev[2])
       st = sweep_rate_enqueue(fr.lane, fr.rq, fr.J.w, fr.J.h);
     if (!st && hipEventRecord(p.evfree.back(), fr.lane->stream) != hipSuccess) st = JXG_ERR_HIP;
     if (st) {

@@ -89,13 +89,13 @@ jxg_status sweep_rate_enqueue(Ctx* S, const SweepReq& rq, uint32_t w, uint32_t h
   // runs the kernel whether or not the rate report is returned
   jxg_status st = rq.ab ? rate_map_ensure(S, w, h) : JXG_OK;
   if (!st) st = rate_enqueue(S, w, h, rq.ab ? S->rt.map.p : nullptr);
-  if (st || !rq.h_rate) return st;
-  JXG_HIP(hipMemcpyAsync(rq.h_rate, S->rt.table.p, kRateCells * sizeof(uint64_t),
+  if (st || !rq.h[kRiderRates]) return st;
+  JXG_HIP(hipMemcpyAsync(rq.h[kRiderRates], S->rt.table.p, kRateCells * sizeof(uint64_t),
                          hipMemcpyDeviceToHost, S->stream));
-  rq.h_rate[kRateCells] = S->rt.ac_bits;
-  rq.h_rate[kRateCells + 1] = S->rt.stream_bits;
-  rq.h_rate[kRateCells + 2] = S->rt.ans ? 1 : 0;
-  rq.h_rate[kRateCells + 3] = S->rt.groups;
+  rq.h[kRiderRates][kRateCells] = S->rt.ac_bits;
+  rq.h[kRiderRates][kRateCells + 1] = S->rt.stream_bits;
+  rq.h[kRiderRates][kRateCells + 2] = S->rt.ans ? 1 : 0;
+  rq.h[kRiderRates][kRateCells + 3] = S->rt.groups;
   return JXG_OK;
 }
 

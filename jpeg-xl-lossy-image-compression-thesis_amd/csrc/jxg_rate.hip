@@ -37,12 +37,6 @@ constexpr int kRateTok = 64;  // AC tokens are < 64 (jxg_ac.hip kAcTok)
 #endif
 constexpr int kRateBatch = JXG_RATE_BATCH;  // tasks whose record loads are in flight together
 
-__device__ __forceinline__ uint32_t rate_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int BR>
 __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
   constexpr int kBandBlocks = BR * 32, kWgBands = 32 / BR;
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
     sCost[i] = (uint16_t)cost;
   }
   for (int i = me; i < 3 * kBandBlocks; i += kBandBlocks) (&sCell[0][0])[i] = 0;
-  for (int i = me; i < (int)kRateCells; i += kBandBlocks) sT[i] = 0;
+  lds_table_zero<kBandBlocks>(sT, kRateCells);
   const SliceTask t = slice_task(a, G, y0);
   fill_slices(a, G, t, L, y0);
   __syncthreads();
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
         const uint32_t clu = min(r & 0xFFu, (uint32_t)kMaxClusters - 1);
         const uint32_t cost =
             (uint32_t)sCost[clu * kRateTok + ((r >> 8) & 63u)] + ((r >> 14) & 15u) * kRateUnit;
-        const uint32_t sum = rate_wave_sum(on8[u] ? cost : 0u);
+        const uint32_t sum = wave_sum(on8[u] ? cost : 0u);
         const int cell = __builtin_amdgcn_readlane(first, js[u]);
         if (lane == 0 && sum) atomicAdd(&sCell[c][cell], sum);
       }
@@ -151,29 +145,15 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
     for (int c = 0; c < 3; c++) vc[c] = sCell[c][me];
   }
   if (t.valid && ra.block_cost) ra.block_cost[t.gb] = vc[0] + vc[1] + vc[2];
-  bool todo = head && t.type < (int)kRateStrategies;
-  while (true) {
-    const unsigned long long m = __ballot(todo);
-    if (!m) break;
-    const int src = __ffsll((long long)m) - 1;
-    const int id0 = __shfl(t.type, src, 64);
-    const bool mine = todo && t.type == id0;
-    uint32_t s[6];
+  const uint32_t v[6] = {vtok[0], vtok[1], vtok[2], vc[0], vc[1], vc[2]};
+  wave_sum_by_key(head && t.type < (int)kRateStrategies, (uint32_t)t.type, v,
+                  [&](uint32_t id0, const uint32_t* s) {
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      s[c] = rate_wave_sum(mine ? vtok[c] : 0u);
-      s[3 + c] = rate_wave_sum(mine ? vc[c] : 0u);
-    }
-    if (lane == src) {
-#pragma unroll
-      for (int k = 0; k < 6; k++)
-        if (s[k]) atomicAdd(sT + id0 * kRateCols + k, (unsigned long long)s[k]);
-    }
-    if (mine) todo = false;
-  }
+                    for (int k = 0; k < 6; k++)
+                      if (s[k]) atomicAdd(sT + id0 * kRateCols + k, (unsigned long long)s[k]);
+                  });
   __syncthreads();
-  for (int i = me; i < (int)kRateCells; i += kBandBlocks)
-    if (sT[i]) atomicAdd(ra.table + i, sT[i]);
+  lds_table_flush<kBandBlocks>(sT, ra.table, kRateCells);
 }
 
 hipError_t launch_rate(const RateArgs& a, uint32_t ngroups, bool whole_group, hipStream_t s) {

@@ -21,6 +21,7 @@
 // Every sum is an integer: the table does not depend on the order of the adds.
 #include <algorithm>
 
+#include "jxg_device.h"
 #include "jxg_kernels.h"
 
 namespace jxg {
@@ -28,14 +29,9 @@ namespace jxg {
 constexpr uint32_t kRepChunk = 256;  // blocks per workgroup step
 constexpr uint32_t kRepGrid = 1024;  // workgroups, at most
 
-__device__ __forceinline__ uint32_t rep_wave_sum(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void strategy_report_kernel(ReportArgs a) {
   __shared__ unsigned long long sT[kReportCells];
-  for (uint32_t i = threadIdx.x; i < kReportCells; i += 256) sT[i] = 0;
+  lds_table_zero<256>(sT, kReportCells);
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t nchunks = (a.nb + kRepChunk - 1) / kRepChunk;
@@ -55,26 +51,16 @@ __global__ __launch_bounds__(256) void strategy_report_kernel(ReportArgs a) {
         q = (uint32_t)a.qf[b] + 1u;
         e = a.block_sse[b];
       }
-      bool todo = in && id < kReportStrategies;  // (other ids: not a stream this encoder writes)
-      while (true) {
-        const unsigned long long m = __ballot(todo);
-        if (!m) break;
-        const int src = __ffsll((long long)m) - 1;
-        const uint32_t id0 = (uint32_t)__shfl((int)id, src, 64);
-        const bool mine = todo && id == id0;
-        const uint32_t nf = rep_wave_sum(mine ? first : 0u), n = rep_wave_sum(mine ? 1u : 0u),
-                       np = rep_wave_sum(mine ? px : 0u), nq = rep_wave_sum(mine ? q : 0u),
-                       ne = rep_wave_sum(mine ? e : 0u);
-        if ((int)lane == src) {
-          unsigned long long* r = sT + id0 * kReportCols;
-          atomicAdd(r + 0, (unsigned long long)nf);
-          atomicAdd(r + 1, (unsigned long long)n);
-          atomicAdd(r + 2, (unsigned long long)np);
-          atomicAdd(r + 6, (unsigned long long)nq);
-          atomicAdd(r + 7, (unsigned long long)ne);
-        }
-        if (mine) todo = false;
-      }
+      // (other ids: not a stream this encoder writes)
+      const uint32_t v[5] = {first, 1u, px, q, e};
+      wave_sum_by_key(in && id < kReportStrategies, id, v, [&](uint32_t id0, const uint32_t* s) {
+        unsigned long long* r = sT + id0 * kReportCols;
+        atomicAdd(r + 0, (unsigned long long)s[0]);
+        atomicAdd(r + 1, (unsigned long long)s[1]);
+        atomicAdd(r + 2, (unsigned long long)s[2]);
+        atomicAdd(r + 6, (unsigned long long)s[3]);
+        atomicAdd(r + 7, (unsigned long long)s[4]);
+      });
     }
     // ---- coefficient pass: slices [b0 * 3, min(b0 + 256, nb) * 3) of 64 int16 ----
     {
@@ -100,8 +86,7 @@ __global__ __launch_bounds__(256) void strategy_report_kernel(ReportArgs a) {
     }
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < kReportCells; i += 256)
-    if (sT[i]) atomicAdd(a.table + i, sT[i]);
+  lds_table_flush<256>(sT, a.table, kReportCells);
 }
 
 hipError_t launch_strategy_report(const ReportArgs& a, hipStream_t s) {

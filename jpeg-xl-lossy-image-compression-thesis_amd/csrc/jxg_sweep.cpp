@@ -47,7 +47,7 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
     JXG_HIP(q.part.ensure(np));
     JXG_HIP(S->rc.rgb.ensure(row * h));
   }
-  const bool bmap = rq.h_rep || rq.ab;  // the block-map form of the chain's last kernel
+  const bool bmap = rq.h[kRiderReport] || rq.ab;  // the block-map form of the chain's last kernel
   if (bmap) JXG_HIP(q.bsse.ensure((size_t)((w + 7) / 8) * ((h + 7) / 8)));
   JXG_HIP(hipMemsetAsync(q.sse.p, 0, sizeof(uint64_t), s));
   JXG_HIP(hipEventRecord(rq.ev[0], s));
@@ -59,7 +59,7 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
   if (st) return st;
   JXG_HIP(hipEventRecord(rq.ev[1], s));
   rq.h_q[1] = 0;
-  const bool ms = ssim && rq.h_ms;
+  const bool ms = ssim && rq.h[kRiderMsssim];
   if (ssim && !ms) {
     const MetricArgs a{d_orig, S->rc.rgb.p, so, row, w, h, q.sse.p, q.part.p, q.ssim.p};
     launch_ssim(a, s);
@@ -79,17 +79,17 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
                    q.ms_out.p};
     launch_msssim(a, s);
     JXG_HIP(hipGetLastError());
-    JXG_HIP(hipMemcpyAsync(rq.h_ms, q.ms_out.p, 2 * kMsScales * sizeof(double),
+    JXG_HIP(hipMemcpyAsync(rq.h[kRiderMsssim], q.ms_out.p, 2 * kMsScales * sizeof(double),
                            hipMemcpyDeviceToHost, s));
     JXG_HIP(hipMemcpyAsync(rq.h_q + 1, q.ms_out.p, sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  if (rq.h_rep) {
+  if (rq.h[kRiderReport]) {
     const jxg_status sr = strategy_report_enqueue(S, w, h);
     if (sr) return sr;
-    JXG_HIP(hipMemcpyAsync(rq.h_rep, q.rep.p, kReportCells * sizeof(uint64_t),
+    JXG_HIP(hipMemcpyAsync(rq.h[kRiderReport], q.rep.p, kReportCells * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, s));
   }
-  if (rq.h_rate || rq.ab) {
+  if (rq.h[kRiderRates] || rq.ab) {
     const jxg_status sr = sweep_rate_enqueue(S, rq, w, h);
     if (sr) return sr;
   }
@@ -100,6 +100,30 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
   JXG_HIP(hipMemcpyAsync(rq.h_q, q.sse.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   JXG_HIP(hipEventRecord(rq.ev[2], s));
   return JXG_OK;
+}
+
+// the riders' rules (jxg_ctx.h), in the order of enum Rider
+static_assert(sizeof(jxg_strategy_report) == kReportCells * 8, "copied as it is staged");
+static_assert(sizeof(jxg_ab_report) == kAbWords * 8, "copied as it is staged");
+const RiderRule kRiderRules[kRiders] = {
+    {2, 2 * kMsScales, sizeof(jxg_msssim)},
+    {1, kReportCells, sizeof(jxg_strategy_report)},
+    {0, kRateWords, sizeof(RateReport)},
+    {1, kAbWords, sizeof(jxg_ab_report)},
+};
+// a point's staged words to its public struct (words null: MS-SSIM under kMsMinEdge)
+static void rider_convert(int r, uint32_t w, uint32_t h, const uint64_t* words, void* out) {
+  double sums[2 * kMsScales];  // (the window sums' bits, as h_q[1] carries the SSIM sum's)
+  switch (r) {
+    case kRiderMsssim:
+      if (!words) return msssim_nan(static_cast<jxg_msssim*>(out));
+      std::memcpy(sums, words, sizeof(sums));
+      return msssim_result(w, h, sums, static_cast<jxg_msssim*>(out));
+    case kRiderRates:
+      return rate_from_words(words, static_cast<RateReport*>(out));
+    default:
+      std::memcpy(out, words, kRiderRules[r].out_bytes);
+  }
 }
 
 static bool point_ok(const jxg_sweep_point& p) {  // as ctx_create checks its parameters
@@ -132,28 +156,18 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   const uint32_t nv = (uint32_t)valid.size();
   Ctx::Sweep& sw = c->sw;
   sw.stats = jxg_sweep_stats{};
-  // MS-SSIM rides on quality 2 (jxg_set_sweep_msssim); kernels only for frames
-  // it is defined for, NaN results otherwise
-  const bool ms = quality == 2 && sw.msssim;
-  const bool ms_run = ms && std::min(w, h) >= kMsMinEdge;
-  sw.ms_have = false;
-  sw.ms.clear();
-  if (ms) sw.ms.assign(n, jxg_msssim{});
-  // the strategy reports ride on quality 1 / 2 (jxg_set_sweep_report)
-  const bool report = quality != 0 && sw.report;
-  sw.rep_have = false;
-  sw.rep.clear();
-  if (report) sw.rep.assign(n, jxg_strategy_report{});
-  // the rate reports ride on every sweep (jxg_set_sweep_rates)
-  const bool rates = sw.rates;
-  sw.rate_have = false;
-  sw.rate.clear();
-  if (rates) sw.rate.assign(n, RateReport{});
-  // the A/B reports ride on quality 1 / 2 (jxg_set_sweep_ab)
-  const bool ab = quality != 0 && !sw.ab_base.empty();
-  sw.ab_have = false;
-  sw.ab.clear();
-  if (ab) sw.ab.assign(n, jxg_ab_report{});
+  // which riders ride on this quality (their results exist), and which run:
+  // MS-SSIM's kernels only for frames it is defined for, NaN results otherwise
+  bool rides[kRiders], runs[kRiders];
+  for (int r = 0; r < kRiders; r++) {
+    Ctx::Sweep::RiderSlot& sl = sw.rider[r];
+    rides[r] = runs[r] = sl.on && quality >= kRiderRules[r].min_quality;
+    sl.have = false;
+    sl.out.clear();
+    if (rides[r]) sl.out.assign((size_t)n * kRiderRules[r].out_bytes, 0);
+  }
+  const bool ab = rides[kRiderAb];
+  const bool ms_run = runs[kRiderMsssim] = rides[kRiderMsssim] && std::min(w, h) >= kMsMinEdge;
   // the context is lane 0 and encodes with its frames' points: its own
   // parameters are put back however the call ends
   const jxg_params saved = c->params;
@@ -172,10 +186,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       if (statuses) statuses[i] = e;
     }
     sw.stats.ms_call = ms_since(t0);
-    sw.ms.clear();
-    sw.rep.clear();
-    sw.rate.clear();
-    sw.ab.clear();
+    for (Ctx::Sweep::RiderSlot& sl : sw.rider) sl.out.clear();
     return e;
   };
   if (nv) {
@@ -198,9 +209,9 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         sw.ev.push_back(e);
       }
     }
-    if (report && sw.h_rep.ensure((size_t)nv * kReportCells) != hipSuccess)
-      return fail(JXG_ERR_OOM);
-    if (rates && sw.h_rate.ensure((size_t)nv * kRateWords) != hipSuccess) return fail(JXG_ERR_OOM);
+    for (int r = 0; r < kRiders; r++)
+      if (runs[r] && sw.rider[r].h.ensure((size_t)nv * kRiderRules[r].words) != hipSuccess)
+        return fail(JXG_ERR_OOM);
     // A/B: the comparisons whose two points are both valid, a snapshot slot and
     // an event per distinct baseline (by its position among the valid points)
     std::vector<int32_t> ab_of, ab_slot;  // per valid point: its baseline's position; its slot
@@ -225,12 +236,9 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         if (make_event(&e, hipEventDisableTiming) != hipSuccess) return fail(JXG_ERR_HIP);
         sw.ab_ev.push_back(e);
       }
-      if (sw.h_ab.ensure((size_t)nv * kAbWords) != hipSuccess) return fail(JXG_ERR_OOM);
     }
     if (ms_run) {  // the original's pyramid, once: every lane reads it after ev_pyr
-      if (sw.h_ms.ensure((size_t)nv * 2 * kMsScales) != hipSuccess ||
-          sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess)
-        return fail(JXG_ERR_OOM);
+      if (sw.pyr_o.ensure(ms_pyramid_floats(w, h)) != hipSuccess) return fail(JXG_ERR_OOM);
       if (!sw.ev_pyr && make_event(&sw.ev_pyr, hipEventDisableTiming) != hipSuccess)
         return fail(JXG_ERR_HIP);
       if (on_device) {
@@ -243,13 +251,22 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     }
     uint32_t got = 0;
     jxg_status e = JXG_OK;
+    // point k's slice of rider r's staging
+    auto slice = [&](int r, uint32_t k) {
+      return sw.rider[r].h.p + (size_t)k * kRiderRules[r].words;
+    };
     // point valid[got]'s codestream (its completion event covers the quality
-    // results) and its share of the timings
+    // and riders' results) and its share of the timings
     auto take = [&]() {
       const uint32_t k = got++, i = valid[k];
       if ((e = pipe_receive(c, &outs[i]))) return;
       sw.stats.ms_encode += c->stats.ms_total;
-      if (rates) rate_from_words(sw.h_rate.p + (size_t)k * kRateWords, &sw.rate[i]);
+      for (int r = 0; r < kRiders; r++) {
+        // (A/B: only a comparing point has a table; the others' reports stay zero)
+        if (!rides[r] || (r == kRiderAb && ab_of[k] < 0)) continue;
+        rider_convert(r, w, h, runs[r] ? slice(r, k) : nullptr,
+                      sw.rider[r].out.data() + (size_t)i * kRiderRules[r].out_bytes);
+      }
       if (!quality) return;
       const uint64_t sse = sw.h_q.p[2 * k];
       double ssum;
@@ -261,14 +278,6 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       o.mse = (double)sse / (double)o.samples;
       o.psnr = 10.0 * std::log10((255.0 * 255.0) / o.mse);
       o.ssim = ssim ? ssum / (3.0 * (double)(w - 10) * (double)(h - 10)) : NAN;
-      if (ms_run)
-        msssim_result(w, h, sw.h_ms.p + (size_t)k * 2 * kMsScales, &sw.ms[i]);
-      else if (ms)
-        msssim_nan(&sw.ms[i]);
-      if (report)
-        std::memcpy(&sw.rep[i], sw.h_rep.p + (size_t)k * kReportCells, sizeof(sw.rep[i]));
-      if (ab && ab_of[k] >= 0)
-        std::memcpy(&sw.ab[i], sw.h_ab.p + (size_t)k * kAbWords, sizeof(sw.ab[i]));
       sw.stats.ms_recon += elapsed(sw.ev[3 * k], sw.ev[3 * k + 1]);
       sw.stats.ms_metrics += elapsed(sw.ev[3 * k + 1], sw.ev[3 * k + 2]);
     };
@@ -284,13 +293,12 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.h_q = sw.h_q.p + 2 * (size_t)k;
         rq.ev = sw.ev.data() + 3 * (size_t)k;
       }
+      for (int r = 0; r < kRiders; r++)
+        if (runs[r] && (r != kRiderAb || ab_of[k] >= 0)) rq.h[r] = slice(r, k);
       if (ms_run) {
-        rq.h_ms = sw.h_ms.p + (size_t)k * 2 * kMsScales;
         rq.pyr_o = sw.pyr_o.p;
         rq.ev_pyr = sw.ev_pyr;
       }
-      if (report) rq.h_rep = sw.h_rep.p + (size_t)k * kReportCells;
-      if (rates) rq.h_rate = sw.h_rate.p + (size_t)k * kRateWords;
       if (ab && ab_slot[k] >= 0) {
         rq.ab = true;
         rq.ab_snap = sw.ab_snap[ab_slot[k]]->p;
@@ -300,7 +308,6 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.ab = true;
         rq.ab_base = sw.ab_snap[ab_slot[ab_of[k]]]->p;
         rq.ab_ev_base = sw.ab_ev[ab_slot[ab_of[k]]];
-        rq.h_ab = sw.h_ab.p + (size_t)k * kAbWords;
       }
       e = pipe_submit(c, d, true, w, h, stride, 0, 1, false, &rq);
       // completed points whose copies have landed (or when more than two wait)
@@ -313,10 +320,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
   sw.stats.points = nv;
   sw.stats.lanes = pipe_shape(f.ngroups, f.tiles_x * f.tiles_y, c->lane_cap, hw_queues()).lanes;
   if (statuses) std::copy(st.begin(), st.end(), statuses);
-  sw.ms_have = ms;
-  sw.rep_have = report;
-  sw.rate_have = rates;
-  sw.ab_have = ab;
+  for (int r = 0; r < kRiders; r++) sw.rider[r].have = rides[r];
   sw.stats.ms_call = ms_since(t0);
   return first;
 }

@@ -649,6 +649,20 @@ class Encoder:
                 pts.append(_SweepPoint(p[0], p[1], *(tuple(p[2:4]) + (0, 0))[:2]))
         return pts
 
+    # a sweep's riders, one row each: the keyword's name, its setter (called with
+    # the keyword's value to switch it on, with `off` in the end), its getter, the
+    # result type, and how a point's result enters its dict
+    _RIDERS = (
+        ("msssim", "jxg_set_sweep_msssim", (0,), "jxg_sweep_msssim", _Msssim,
+         lambda r: {"ms_ssim": float(r.ms_ssim), "cs": [float(v) for v in r.cs]}),
+        ("strategies", "jxg_set_sweep_report", (0,), "jxg_sweep_report", _StrategyReport,
+         lambda r: {"strategies": r.as_dict()}),
+        ("ab", "jxg_set_sweep_ab", (None, 0), "jxg_sweep_ab", _AbReport,
+         lambda r: {"ab": r.as_dict()}),
+        ("rates", "jxg_set_sweep_rates", (0,), "jxg_sweep_rates", _RateReport,
+         lambda r: {"rates": r.as_dict()}),
+    )
+
     def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False,
                     rates=False, ab=None):
         if quality not in self._QUALITY:
@@ -656,7 +670,6 @@ class Encoder:
         level = self._QUALITY[quality]
         if strategies and not level:
             raise ValueError("strategies ride on a sweep's quality chain: quality must not be None")
-        ms = quality == "msssim"
         pts = self._sweep_points(points)
         n = len(pts)
         if ab is not None:
@@ -669,50 +682,33 @@ class Encoder:
                 raise ValueError("ab: a base index is -1 or that of an earlier point")
         if n == 0:
             return []
+        # the setters' arguments of the riders that are asked for
+        on = {"msssim": (1,) if quality == "msssim" else None,
+              "strategies": (1,) if strategies else None,
+              "rates": (1,) if rates else None,
+              "ab": ((ctypes.c_int32 * n)(*ab), n) if ab is not None else None}
+        riders = [r for r in self._RIDERS if on[r[0]] is not None]
         c_pts = (_SweepPoint * n)(*pts)
         outs = (_Buffer * n)()
         qs = (_Quality * n)() if level else None
         st = (ctypes.c_int * n)()
-        mss = reps = rts = abs_ = None
-        if ms:
-            _check(load().jxg_set_sweep_msssim(self._ctx, 1))
+        got = {}  # by keyword: the results of a sweep that has them (a failed one has none)
+        lib = load()
         try:
-            if strategies:
-                _check(load().jxg_set_sweep_report(self._ctx, 1))
-            if rates:
-                _check(load().jxg_set_sweep_rates(self._ctx, 1))
-            if ab is not None:
-                _check(load().jxg_set_sweep_ab(self._ctx, (ctypes.c_int32 * n)(*ab), n))
+            for name, setter, _, _, _, _ in riders:
+                _check(getattr(lib, setter)(self._ctx, *on[name]))
             ret = fn(self._ctx, ptr, w, h, stride, c_pts, n, level, outs, qs, st)
-            if strategies:
-                r = (_StrategyReport * n)()
-                if load().jxg_sweep_report(self._ctx, r, n) == 0:
-                    reps = r
-            if rates:
-                r = (_RateReport * n)()
-                if load().jxg_sweep_rates(self._ctx, r, n) == 0:
-                    rts = r
-            if ab is not None:
-                r = (_AbReport * n)()
-                if load().jxg_sweep_ab(self._ctx, r, n) == 0:
-                    abs_ = r
-            if ms:  # (a sweep that failed as a whole has none: ret is raised below)
-                m = (_Msssim * n)()
-                if load().jxg_sweep_msssim(self._ctx, m, n) == 0:
-                    mss = m
+            for name, _, _, getter, ctype, _ in riders:
+                r = (ctype * n)()
+                if getattr(lib, getter)(self._ctx, r, n) == 0:
+                    got[name] = r
         finally:
-            if ms:
-                load().jxg_set_sweep_msssim(self._ctx, 0)
-            if strategies:
-                load().jxg_set_sweep_report(self._ctx, 0)
-            if rates:
-                load().jxg_set_sweep_rates(self._ctx, 0)
-            if ab is not None:
-                load().jxg_set_sweep_ab(self._ctx, None, 0)
+            for _, setter, off, _, _, _ in riders:
+                getattr(lib, setter)(self._ctx, *off)
         st = [int(v) for v in st]
         if ret != 0 and (strict or self._batch_call_failed(ret, st)):
             for i in range(n):
-                load().jxg_buffer_free(ctypes.byref(outs[i]))
+                lib.jxg_buffer_free(ctypes.byref(outs[i]))
             _check(ret)
         res = []
         for i in range(n):
@@ -722,15 +718,10 @@ class Encoder:
             q = None
             if level:
                 q = {k: getattr(qs[i], k) for k in ("sse", "samples", "mse", "psnr", "ssim")}
-                if mss is not None:
-                    q["ms_ssim"] = float(mss[i].ms_ssim)
-                    q["cs"] = [float(v) for v in mss[i].cs]
-                if reps is not None:
-                    q["strategies"] = reps[i].as_dict()
-                if abs_ is not None and ab[i] >= 0:
-                    q["ab"] = abs_[i].as_dict()
-            if rts is not None:
-                q = dict(q or {}, rates=rts[i].as_dict())
+            for name, _, _, _, _, put in riders:
+                # (quality None: rates alone, the others were refused above)
+                if name in got and (name != "ab" or ab[i] >= 0):
+                    q = dict(q or {}, **put(got[name][i]))
             res.append((self._take(outs[i]), q))
         return res
 

@@ -149,6 +149,39 @@ def file_size_ratio(orig: int, comp: int, denom: str) -> float:
     raise ValueError("Invalid denominator for file size ratio")
 
 
+class _StatRow:
+    """row() and parse() of a per-strategy CSV record from its dataclass fields:
+    names as they are, ``distance`` as f32, the fields of ``_FLOATS`` as f64,
+    every other one an integer."""
+    _FLOATS = ()
+
+    @classmethod
+    def _kind(cls, f):
+        if f.name == "distance":
+            return rust_f32, lambda v: float(np.float32(v))
+        if f.type in (str, "str"):
+            return str, str
+        return (rust_f64, float) if f.name in cls._FLOATS else (str, int)
+
+    def row(self):
+        return [self._kind(f)[0](getattr(self, f.name)) for f in fields(self)]
+
+    @classmethod
+    def parse(cls, rec):
+        return cls(*[cls._kind(f)[1](v) for f, v in zip(fields(cls), rec)])
+
+
+def _append_stats(rows, file_name: str, header) -> None:
+    write_csv_header(file_name, header)
+    write_csv(rows, file_name)
+
+
+def _read_stats(cls, file_name: str):
+    with open(file_name, newline="") as f:
+        rows = list(csv.reader(f))
+    return [cls.parse(r) for r in rows[1:] if r]
+
+
 STRATEGY_HEADER = [
     "Original Image Name", "Compressed Image Name", "Distance", "Effort", "Strategy", "Name",
     "Varblocks", "Blocks", "Pixels", "Area Share", "Nonzeros X", "Nonzeros Y", "Nonzeros B",
@@ -158,7 +191,7 @@ STRATEGY_DIFF_HEADER = STRATEGY_HEADER[:6] + ["Diff " + h for h in STRATEGY_HEAD
 
 
 @dataclass
-class StrategyStat:
+class StrategyStat(_StatRow):
     """One strategy of one encode: the report's row and what follows from it
     (area share = pixels / image pixels, mean quant field = qf_sum / blocks,
     MSE = SSE / (3 * pixels))."""
@@ -180,19 +213,6 @@ class StrategyStat:
     mse: float
 
     _FLOATS = ("area_share", "mean_quant_field", "mse")
-
-    def row(self):
-        return [self.orig_image_name, self.comp_image_name, rust_f32(self.distance),
-                str(self.effort), str(self.strategy), self.name] + [
-                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
-                    else str(getattr(self, f.name)) for f in fields(self)[6:]]
-
-    @classmethod
-    def parse(cls, rec):
-        vals = [float(v) if f.name in cls._FLOATS else int(v)
-                for f, v in zip(fields(cls)[6:], rec[6:16])]
-        return cls(rec[0], rec[1], float(np.float32(rec[2])), int(rec[3]), int(rec[4]), rec[5],
-                   *vals)
 
 
 @dataclass
@@ -231,14 +251,11 @@ def strategy_stats(orig_name: str, comp_name: str, distance: float, effort: int,
 
 
 def write_strategy_stats(rows, strategy_file: str) -> None:
-    write_csv_header(strategy_file, STRATEGY_HEADER)
-    write_csv(rows, strategy_file)
+    _append_stats(rows, strategy_file, STRATEGY_HEADER)
 
 
 def read_strategy_stats(file_name: str):
-    with open(file_name, newline="") as f:
-        rows = list(csv.reader(f))
-    return [StrategyStat.parse(r) for r in rows[1:] if r]
+    return _read_stats(StrategyStat, file_name)
 
 
 def compare_strategy_stats(file_1: str, file_2: str):
@@ -271,7 +288,7 @@ RATE_HEADER = [
 
 
 @dataclass
-class RateStat:
+class RateStat(_StatRow):
     """One strategy of one encode in the rate report (Encoder.rate_report,
     DESIGN.md 3.17): the tokens of its varblocks per channel and what they cost
     in the written AC streams, in bits (the report's cost / 256); beside them
@@ -293,19 +310,6 @@ class RateStat:
 
     _FLOATS = ("bits_x", "bits_y", "bits_b")
 
-    def row(self):
-        return [self.orig_image_name, self.comp_image_name, rust_f32(self.distance),
-                str(self.effort), str(self.strategy), self.name] + [
-                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
-                    else str(getattr(self, f.name)) for f in fields(self)[6:]]
-
-    @classmethod
-    def parse(cls, rec):
-        vals = [float(v) if f.name in cls._FLOATS else int(v)
-                for f, v in zip(fields(cls)[6:], rec[6:14])]
-        return cls(rec[0], rec[1], float(np.float32(rec[2])), int(rec[3]), int(rec[4]), rec[5],
-                   *vals)
-
 
 def rate_stats(orig_name: str, comp_name: str, distance: float, effort: int, report: dict):
     """The RateStat rows of one report (Encoder.rate_report / a sweep point's
@@ -323,14 +327,11 @@ def rate_stats(orig_name: str, comp_name: str, distance: float, effort: int, rep
 
 
 def write_rate_stats(rows, rate_file: str) -> None:
-    write_csv_header(rate_file, RATE_HEADER)
-    write_csv(rows, rate_file)
+    _append_stats(rows, rate_file, RATE_HEADER)
 
 
 def read_rate_stats(file_name: str):
-    with open(file_name, newline="") as f:
-        rows = list(csv.reader(f))
-    return [RateStat.parse(r) for r in rows[1:] if r]
+    return _read_stats(RateStat, file_name)
 
 
 AB_HEADER = [
@@ -341,7 +342,7 @@ AB_HEADER = [
 
 
 @dataclass
-class AbStat:
+class AbStat(_StatRow):
     """One non-empty cell of an A/B report (jxg.ab_report / a sweep point's
     ``"ab"``): the 8x8 blocks whose varblock has strategy
     ``from`` in encode A and ``to`` in encode B, their squared error and their
@@ -368,20 +369,6 @@ class AbStat:
 
     _FLOATS = ("area_share", "bits_a", "bits_b", "diff_bits")
 
-    def row(self):
-        return [self.orig_image_name, self.comp_image_name_a, self.comp_image_name_b,
-                rust_f32(self.distance), str(self.effort), str(self.from_strategy), self.from_name,
-                str(self.to_strategy), self.to_name] + [
-                    rust_f64(getattr(self, f.name)) if f.name in self._FLOATS
-                    else str(getattr(self, f.name)) for f in fields(self)[9:]]
-
-    @classmethod
-    def parse(cls, rec):
-        vals = [float(v) if f.name in cls._FLOATS else int(v)
-                for f, v in zip(fields(cls)[9:], rec[9:18])]
-        return cls(rec[0], rec[1], rec[2], float(np.float32(rec[3])), int(rec[4]), int(rec[5]),
-                   rec[6], int(rec[7]), rec[8], *vals)
-
 
 def ab_stats(orig_name: str, comp_name_a: str, comp_name_b: str, distance: float, effort: int,
              report: dict, width: int, height: int):
@@ -402,14 +389,11 @@ def ab_stats(orig_name: str, comp_name_a: str, comp_name_b: str, distance: float
 
 
 def write_ab_stats(rows, ab_file: str) -> None:
-    write_csv_header(ab_file, AB_HEADER)
-    write_csv(rows, ab_file)
+    _append_stats(rows, ab_file, AB_HEADER)
 
 
 def read_ab_stats(file_name: str):
-    with open(file_name, newline="") as f:
-        rows = list(csv.reader(f))
-    return [AbStat.parse(r) for r in rows[1:] if r]
+    return _read_stats(AbStat, file_name)
 
 
 _DIFF_FIELDS = [f.name for f in fields(ComparisonResult)[4:]]
@@ -571,22 +555,21 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     raw = w * h * 3
     datas, records = [], []
 
-    def name_of(p):
-        d, e = (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
-        return comp_image_name(stem, d, e)
+    def d_e(p):
+        return (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
 
+    names = [comp_image_name(stem, *d_e(p)) for p in points]
     for i, (p, (data, q)) in enumerate(zip(points, res)):
-        d, e = (p["distance"], p["effort"]) if isinstance(p, dict) else (p[0], p[1])
+        d, e = d_e(p)
         datas.append(data)
-        records.append(_record(orig_name, comp_image_name(stem, d, e), d, e, orig_file_size,
-                               len(data), raw, q, ssim, result_file))
+        records.append(_record(orig_name, names[i], d, e, orig_file_size, len(data), raw, q, ssim,
+                               result_file))
         if strategy_file is not None:
-            write_strategy_stats(strategy_stats(orig_name, comp_image_name(stem, d, e), d, e,
-                                                q["strategies"], w, h), strategy_file)
+            write_strategy_stats(strategy_stats(orig_name, names[i], d, e, q["strategies"], w, h),
+                                 strategy_file)
         if rate_file is not None:
-            write_rate_stats(rate_stats(orig_name, comp_image_name(stem, d, e), d, e, q["rates"]),
-                             rate_file)
+            write_rate_stats(rate_stats(orig_name, names[i], d, e, q["rates"]), rate_file)
         if ab_file is not None and ab_base[i] >= 0:
-            write_ab_stats(ab_stats(orig_name, name_of(points[ab_base[i]]), name_of(p), d, e,
-                                    q["ab"], w, h), ab_file)
+            write_ab_stats(ab_stats(orig_name, names[ab_base[i]], names[i], d, e, q["ab"], w, h),
+                           ab_file)
     return datas, records

@@ -5,19 +5,9 @@ import subprocess
 
 import pytest
 
+from sweep_cases import natural as _natural
+
 pytestmark = pytest.mark.gpu
-
-_cache = {}
-
-
-def _natural():
-    if "img" not in _cache:
-        from jxg.synth import natural_rgb8
-
-        _cache["img"] = natural_rgb8(200, 136, 5)
-        _cache["img"].setflags(write=False)
-    return _cache["img"]
-
 
 def _report(jxg, distance, effort, base, proposals):
     """(side B's codestream, A/B report) of two fresh encoders at cjxl's defaults"""

@@ -9,18 +9,16 @@ import numpy as np
 import pytest
 
 import ab_ref
+from sweep_cases import INVALID_ARG, natural as _natural, qbits, same
 from test_ab_ref import PAIRS, pair_image
 from test_recon_cases import case_flags, gradient_rgb8
 
 pytestmark = pytest.mark.gpu
 
-INVALID_ARG = -1
 KEYS = ("blocks", "pixels", "sse_a", "sse_b", "cost_a", "cost_b")
 
 
-def _same(a, b):
-    return all(np.array_equal(a[k], b[k]) and a[k].dtype == np.uint64 and a[k].shape == (27, 27)
-               for k in KEYS)
+_same = same(KEYS, lambda a, b, k: a[k].dtype == np.uint64 and a[k].shape == (27, 27))
 
 
 def _params(jxg, side):
@@ -221,15 +219,6 @@ def _points(jxg):
     ]
 
 
-def _natural():
-    if "img" not in _cache:
-        from jxg.synth import natural_rgb8
-
-        _cache["img"] = natural_rgb8(200, 136, 5)
-        _cache["img"].setflags(write=False)
-    return _cache["img"]
-
-
 def _fresh(jxg):
     """per point its codestream and, where BASE names one, the A/B report of
     fresh one-at-a-time encoders of the two points"""
@@ -250,8 +239,7 @@ def _fresh(jxg):
 
 
 def _qbits(q):
-    keys = [k for k in ("sse", "samples", "mse", "psnr", "ssim") if k in q]
-    return [np.float64(q[k]).tobytes() if isinstance(q[k], float) else q[k] for k in keys]
+    return qbits(q, ms=False)
 
 
 @pytest.mark.parametrize("quality", ["psnr", "ssim"])

@@ -15,11 +15,11 @@ import numpy as np
 import pytest
 
 import msssim_ref
+from sweep_cases import INVALID_ARG, qbits
 from test_gpu_metrics import _pair
 
 pytestmark = pytest.mark.gpu
 
-INVALID_ARG = -1
 
 
 @pytest.fixture(scope="module")
@@ -168,11 +168,8 @@ def _points(jxg):
     ]
 
 
-QKEYS = ("sse", "samples", "mse", "psnr", "ssim")
-
-
 def _qbits(q):
-    return [struct.pack("<d", q[k]) if isinstance(q[k], float) else q[k] for k in QKEYS]
+    return qbits(q, ms=False)
 
 
 _sweep_state = {}

@@ -10,16 +10,16 @@ import numpy as np
 import pytest
 
 from strategy_ref import FIELDS, reference_block_sse, reference_report
+from sweep_cases import INVALID_ARG, RefusedAndGood, cached, natural as _natural, poisoned
+from sweep_cases import points as _points, qbits as _qbits, same
 from test_recon_cases import CASES, case_flags, case_image
 
 pytestmark = pytest.mark.gpu
 
-INVALID_ARG = -1
 MERGED = set(range(4, 12)) | set(range(18, 27))
 
 
-def _same(a, b):
-    return all(np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype for k in FIELDS)
+_same = same(FIELDS, lambda a, b, k: a[k].dtype == b[k].dtype)
 
 
 def _check(jxg, enc, img, data):
@@ -93,30 +93,6 @@ def test_encoder_is_not_disturbed(jxg_mod):
 
 
 # ---- sweeps ----
-def _points(jxg):
-    d = jxg.FLAGS_CJXL_DEFAULTS
-    return [
-        dict(distance=1.0, effort=5, proposals=0, flags=d),
-        dict(distance=4.0, effort=5, proposals=0, flags=d & ~jxg.FLAG_ANS),   # prefix codes
-        dict(distance=1.0, effort=7, proposals=3, flags=d),                   # both hooks
-        dict(distance=4.0, effort=7, proposals=0, flags=d),
-        dict(distance=1.0, effort=8, proposals=0, flags=d),
-        dict(distance=4.0, effort=8, proposals=0, flags=d),
-    ]
-
-
-_cache = {}
-
-
-def _natural():
-    if "img" not in _cache:
-        from jxg.synth import natural_rgb8
-
-        _cache["img"] = natural_rgb8(200, 136, 5)
-        _cache["img"].setflags(write=False)
-    return _cache["img"]
-
-
 def _fresh(jxg, img, points):
     """[(bytes, report)] of fresh one-at-a-time contexts, through the device entry point"""
     import torch
@@ -132,15 +108,7 @@ def _fresh(jxg, img, points):
 
 
 def _natural_refs(jxg):
-    if "refs" not in _cache:
-        _cache["refs"] = _fresh(jxg, _natural(), _points(jxg))
-    return _cache["refs"]
-
-
-def _qbits(q):
-    keys = [k for k in ("sse", "samples", "mse", "psnr", "ssim", "ms_ssim") if k in q]
-    return [np.float64(q[k]).tobytes() if isinstance(q[k], float) else q[k] for k in keys] + [
-        np.array(q.get("cs", []), np.float64).tobytes()]
+    return cached("strategy refs", lambda: _fresh(jxg, _natural(), _points(jxg)))
 
 
 @pytest.mark.parametrize("quality", ["psnr", "ssim", "msssim"])
@@ -186,25 +154,11 @@ def test_sweep_refused_point_and_state(jxg_mod):
     lib = jxg_mod.load()
     img = np.array(_natural())
     good = _points(jxg_mod)[0]
-    pts = (jxg_mod._SweepPoint * 2)(
-        jxg_mod._SweepPoint(1.0, 0, 0, 0),   # effort 0: refused
-        jxg_mod._SweepPoint(good["distance"], good["effort"], good["proposals"], good["flags"]))
-    outs = (jxg_mod._Buffer * 2)()
-    qs = (jxg_mod._Quality * 2)()
-    st = (ctypes.c_int * 2)()
-    reps = (jxg_mod._StrategyReport * 2)()
-    for r in reps:
-        ctypes.memset(ctypes.byref(r), 0xA5, ctypes.sizeof(r))
-
-    def sweep(quality):
-        ret = lib.jxg_sweep_rgb8(enc._ctx, img.ctypes.data, 200, 136, 600, pts, 2, quality, outs,
-                                 qs if quality else None, st)
-        datas = [ctypes.string_at(o.data, o.size) if o.data else None for o in outs]
-        for o in outs:
-            lib.jxg_buffer_free(ctypes.byref(o))
-        return ret, datas
+    reps = poisoned(jxg_mod._StrategyReport, 2)
 
     with jxg_mod.Encoder() as enc:
+        sweep = RefusedAndGood(jxg_mod, enc, good)
+        st = sweep.st
         assert lib.jxg_sweep_report(enc._ctx, reps, 2) == INVALID_ARG, "no sweep yet"
         assert sweep(1)[0] == INVALID_ARG and list(st) == [INVALID_ARG, 0]
         assert lib.jxg_sweep_report(enc._ctx, reps, 2) == INVALID_ARG, "switch off"

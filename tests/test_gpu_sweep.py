@@ -4,16 +4,16 @@ comparison is against the library's own one-at-a-time path on a fresh
 for bit (encode -> reconstruct_device -> compare_device)."""
 import os
 import re
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+from sweep_cases import QKEYS, qbits
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QKEYS = ("sse", "samples", "mse", "psnr", "ssim")
 
 
 def _points(jxg):
@@ -64,12 +64,8 @@ def _image(name):
     raise KeyError(name)
 
 
-def _bits(v):
-    return struct.pack("<d", v) if isinstance(v, float) else v
-
-
 def _same_q(a, b):
-    return all(_bits(a[k]) == _bits(b[k]) for k in QKEYS)
+    return qbits(a, ms=False) == qbits(b, ms=False)
 
 
 def _one_at_a_time(jxg, img, point):
@@ -409,3 +405,59 @@ def test_call_level_refusals_on_a_live_context(jxg_mod):
             want = one.encode(img)
         for i in range(n):
             assert jxg_mod.Encoder._take(outs[i]) == want
+
+
+def _assert_same_dict(a, b, what):
+    assert a.keys() == b.keys(), what
+    for k in a:
+        if isinstance(a[k], np.ndarray):
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
+            assert a[k].tobytes() == b[k].tobytes(), (what, k)
+        else:
+            assert a[k] == b[k], (what, k)
+
+
+def test_every_rider_at_once(jxg_mod):
+    """MS-SSIM, strategy reports, rate reports and A/B reports in one sweep:
+    every result of every point is, bit for bit, what the same sweep gives with
+    that rider alone; a sweep with all of them off leaves no getter anything"""
+    import ctypes
+
+    from jxg.synth import natural_rgb8
+    from sweep_cases import INVALID_ARG, points
+
+    jxg = jxg_mod
+    img = natural_rgb8(256, 192, 11)
+    pts = points(jxg)[1:4]   # prefix codes; both hooks; another distance
+    base = [-1, 0, 0]
+    with jxg.Encoder() as enc:
+        full = enc.sweep(img, pts, quality="msssim", strategies=True, rates=True, ab=base)
+        alone = {
+            "msssim": enc.sweep(img, pts, quality="msssim"),
+            "strategies": enc.sweep(img, pts, quality="ssim", strategies=True),
+            "rates": enc.sweep(img, pts, quality="ssim", rates=True),
+            "ab": enc.sweep(img, pts, quality="ssim", ab=base),
+        }
+        off = enc.sweep(img, pts, quality="ssim")
+        lib = jxg.load()
+        for getter, ctype in (("jxg_sweep_report", jxg._StrategyReport),
+                              ("jxg_sweep_rates", jxg._RateReport),
+                              ("jxg_sweep_ab", jxg._AbReport), ("jxg_sweep_msssim", jxg._Msssim)):
+            assert getattr(lib, getter)(enc._ctx, (ctype * 3)(), 3) == INVALID_ARG, getter
+    for i, (data, q) in enumerate(full):
+        assert set(q) == set(QKEYS) | {"ms_ssim", "cs", "strategies", "rates"} | (
+            {"ab"} if base[i] >= 0 else set()), "point %d" % i
+        assert data == off[i][0] and _same_q(q, off[i][1]), "point %d: all off" % i
+        assert set(off[i][1]) == set(QKEYS)
+        for rider, res in alone.items():
+            adata, aq = res[i]
+            assert data == adata, "point %d: codestream with %s alone" % (i, rider)
+            assert _same_q(q, aq), "point %d: quality words with %s alone" % (i, rider)
+        assert qbits(q) == qbits(alone["msssim"][i][1]), "point %d: ms_ssim / cs" % i
+        assert 0.0 < q["ms_ssim"] < 1.0
+        for key in ("strategies", "rates") + (("ab",) if base[i] >= 0 else ()):
+            _assert_same_dict(q[key], alone[key][i][1][key], "point %d: %s" % (i, key))
+        assert ("ab" in alone["ab"][i][1]) == (base[i] >= 0)
+    assert full[1][1]["ab"]["blocks"].sum() == 32 * 24
+    assert full[1][1]["ab"]["sse_b"].tobytes() != full[2][1]["ab"]["sse_b"].tobytes()
+    assert full[0][1]["rates"]["ans"] == 0 and full[1][1]["rates"]["ans"] == 1
