@@ -147,6 +147,47 @@ jxg_status jxg_encode_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t xsize, uin
 /* device-resident RGB8 (same layout, device pointer) -> codestream */
 jxg_status jxg_encode_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsize,
                                   uint32_t ysize, size_t row_stride, jxg_buffer* out);
+/* Forced encode: the caller's AC-strategy map instead of the search
+ * (DESIGN.md 3.19).  `acs` is [ysize_blocks][xsize_blocks] u8 in the layout of
+ * jxg_stats.ac_strategy / jxg_decode_maps: a varblock's first block holds its
+ * raw id, every other block it covers 0x80 | id.  Accepted ids: the 8x8 class
+ * (0, 1, 2, 3, 12, 13) and the nine merged shapes up to 64 px (4, 5, 6, 7, 10,
+ * 11, 18, 19, 20); a merged varblock may sit at any block position inside one
+ * 64x64 tile and the frame's blocks (the decoder's tile rule), not only at the
+ * multiples of its size the search produces.
+ *
+ * jxg_check_strategy_map (host only, no context) says whether a map is
+ * accepted: JXG_ERR_UNSUPPORTED for a first block's id outside the 15 (AFV,
+ * 32X8 / 8X32, the 128 / 256 px kinds); JXG_ERR_INVALID_ARG for a null map, a
+ * size jxg_encode_rgb8 refuses, a varblock reaching past the frame's blocks or
+ * across a tile border, a covered byte that is not 0x80 | id of the varblock
+ * covering it, a covered byte no varblock covers, or overlap.  On refusal
+ * *bad_block (may be NULL) is the raster index of the first offending block
+ * in raster order.
+ *
+ * The encode calls validate the map before anything is uploaded or launched;
+ * a refused map returns the validator's status with *out = {NULL, 0} and
+ * leaves the context as it was (jxg_reconstruct_rgb8 still serves the encode
+ * before).  `qf` (or NULL) has the same geometry and holds raw - 1 per block
+ * as jxg_stats.quant_field; it replaces the adaptive quant field (NULL: the
+ * context's own, heuristic or masking).  A merged varblock takes the largest
+ * value of the blocks it covers.  Both maps are host memory in both variants.
+ * Everything that is not a choice (XYB, Gaborish, DC, chroma from luma, the
+ * coder, the filters signalled) is what an effort-7 encode of the context's
+ * distance and flags computes; the context's effort and proposals play no
+ * part and jxg_stats.homogeneity is NULL.  In every other respect this is
+ * jxg_encode_rgb8: JXG_FLAG_KEEP_MAPS, jxg_get_stats, jxg_reconstruct_rgb8 and
+ * the reports serve it alike; JXG_ERR_INVALID_ARG for null arguments, a stride
+ * under 3 * xsize or streamed frames pending.  There is no batch, streaming,
+ * sweep or sharded form. */
+jxg_status jxg_check_strategy_map(const uint8_t* acs, uint32_t xsize, uint32_t ysize,
+                                  uint32_t* bad_block);
+jxg_status jxg_encode_forced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t xsize,
+                                  uint32_t ysize, size_t row_stride, const uint8_t* acs,
+                                  const uint8_t* qf, jxg_buffer* out);
+jxg_status jxg_encode_forced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsize,
+                                         uint32_t ysize, size_t row_stride, const uint8_t* acs,
+                                         const uint8_t* qf, jxg_buffer* out);
 /* n frames of equal size (benchmark config 3: 64 x 1080p; the reference's
  * caller encodes every image at 10 distances x 5 efforts, benchmark.rs:
  * 637-642), through the streaming pipeline below (jxg_submit_rgb8 of every

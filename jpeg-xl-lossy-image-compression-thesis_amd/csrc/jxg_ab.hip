@@ -6,11 +6,12 @@
 //                    varblock's coded cost C (the first-block map of
 //                    rate_kernel), C / n + (k < C % n) for covered block k of
 //                    n in raster order inside the varblock.  Gather form: the
-//                    first block is at the block's position rounded down to
-//                    the varblock's size.  The encoder guarantees that
-//                    alignment for every shape: up to 64 px by the merge
-//                    stage's construction inside 64x64 tiles (jxg_actask.h,
-//                    slice_task relies on it), for the 128 / 256 px shapes by
+//                    first block is first_block's (jxg_actask.h): the block's
+//                    position rounded down to the varblock's size, which the
+//                    search guarantees for every shape -- up to 64 px by the
+//                    merge stage's construction inside 64x64 tiles (a forced
+//                    map's off-grid varblock is found from the map instead),
+//                    for the 128 / 256 px shapes by
 //                    big_region / big_cand (jxg_bigvb.hip): a region starts at
 //                    a multiple of 16 (32) blocks of a pass group that starts
 //                    at a multiple of 32, and a half candidate at the region's
@@ -45,7 +46,9 @@ __global__ __launch_bounds__(256) void ab_share_kernel(AbShareArgs a) {
   varblock_dims(a.acs[b] & 0x7F, lcb, cx, cy);
   const uint32_t bx = b % a.bxs, by = b / a.bxs;
   // (ox <= bx, oy <= by: the first block is inside the frame)
-  const uint32_t ox = bx & ~(uint32_t)(cx - 1), oy = by & ~(uint32_t)(cy - 1);
+  int fx, fy;
+  first_block(a.acs, a.bxs, a.acs[b] & 0x7F, lcb, cx, cy, (int)bx, (int)by, fx, fy);
+  const uint32_t ox = (uint32_t)fx, oy = (uint32_t)fy;
   const uint32_t C = a.block_cost[(size_t)oy * a.bxs + ox];
   const uint32_t k = (by - oy) * (uint32_t)cx + (bx - ox);
   a.share[b] = (C >> lcb) + (k < (C & ((1u << lcb) - 1u)) ? 1u : 0u);

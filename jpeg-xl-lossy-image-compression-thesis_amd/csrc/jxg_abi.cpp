@@ -79,6 +79,33 @@ jxg_status jxg_encode_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_
   return encode_one(c, rgb, false, w, h, stride, out, t0);
 }
 
+// forced encode: the map is validated (jxg_force.cpp) before the context is
+// touched -- a refused map leaves the previous encode's state in place
+static jxg_status encode_forced(jxg_ctx* ctx, const void* src, bool on_device, uint32_t w,
+                                uint32_t h, size_t stride, const uint8_t* acs, const uint8_t* qf,
+                                jxg_buffer* out) {
+  if (out) *out = jxg_buffer{nullptr, 0};
+  if (!ctx || !src || !acs || !out || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  const Clock::time_point t0 = Clock::now();
+  Ctx* c;
+  jxg_status st = ctx_enter(ctx, true, &c);
+  if (st) return st;
+  if ((st = jxg_check_strategy_map(acs, w, h, nullptr))) return st;
+  return encode_one(c, static_cast<const uint8_t*>(src), on_device, w, h, stride, out, t0, acs, qf);
+}
+
+jxg_status jxg_encode_forced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                  size_t stride, const uint8_t* acs, const uint8_t* qf,
+                                  jxg_buffer* out) {
+  return encode_forced(ctx, rgb, false, w, h, stride, acs, qf, out);
+}
+
+jxg_status jxg_encode_forced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                         size_t stride, const uint8_t* acs, const uint8_t* qf,
+                                         jxg_buffer* out) {
+  return encode_forced(ctx, d_rgb, true, w, h, stride, acs, qf, out);
+}
+
 jxg_status jxg_encode_batch_rgb8(jxg_ctx* ctx, const uint8_t* const* rgbs, uint32_t n, uint32_t w,
                                  uint32_t h, size_t stride, jxg_buffer* outs) {
   if (!ctx || !rgbs || !outs || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;

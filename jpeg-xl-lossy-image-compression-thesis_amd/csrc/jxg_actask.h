@@ -67,9 +67,31 @@ __device__ __forceinline__ void varblock_dims(int type, int& lcb, int& cx, int& 
   }
 }
 
+// The first block (ox, oy) of the varblock of strategy `type` that covers
+// frame block (bx, by).  The search places a varblock on its shape's own grid,
+// where masking the position finds it; a forced map (jxg_encode_forced_rgb8)
+// may place a shape of up to 64 px anywhere inside its 64x64 tile.  The masked
+// position lies inside every such varblock's reach, and a first block of this
+// id within reach covers the block (varblocks do not overlap), so: the masked
+// guess when its byte is the id -- one byte and one compare on the grid -- else
+// the one position within reach, inside the tile, whose byte is.
+__device__ __forceinline__ void first_block(const uint8_t* acs, uint32_t bxs, int type, int lcb,
+                                            int cx, int cy, int bx, int by, int& ox, int& oy) {
+  ox = bx & ~(cx - 1);
+  oy = by & ~(cy - 1);
+  if (lcb == 0 || lcb > 6 || acs[(size_t)oy * bxs + ox] == (uint8_t)type) return;
+  const int ylo = max(by - cy + 1, by & ~7), xlo = max(bx - cx + 1, bx & ~7);
+  for (int y = ylo; y <= by; y++)
+    for (int x = xlo; x <= bx; x++)
+      if (acs[(size_t)y * bxs + x] == (uint8_t)type) {
+        ox = x;
+        oy = y;
+      }
+}
+
 // ac_hist runs one 256-thread workgroup per BAND of a pass group: 8 block
 // rows (one row of 64x64 tiles) x 32 block columns.  Varblocks up to 64x64
-// are aligned to their size inside 64x64 tiles, so a band holds whole
+// lie inside one 64x64 tile, so a band holds whole
 // varblocks, and the group's token stream (varblocks by first block raster)
 // is the concatenation of its four bands' streams: band j writes its records
 // at [j * kBandTokStride, ...) of the group's record space and its token
@@ -97,7 +119,7 @@ __device__ __forceinline__ uint32_t rec_index(const uint32_t* bt, uint32_t k) {
 }
 
 // One thread per block of the band: slice `sl` of the varblock whose first
-// block is (obx, oby) (group-local rows; varblocks are aligned to their size).
+// block is (obx, oby) (group-local; first_block).
 struct SliceTask {
   bool valid;
   int bx, by, obx, oby, sl, lcb, cx, type;
@@ -115,8 +137,10 @@ __device__ __forceinline__ SliceTask slice_task(const AcArgs& a, const GroupGeom
   t.type = t.valid ? (a.acs[t.gb] & 0x7F) : 0;
   int cy;
   varblock_dims(t.type, t.lcb, t.cx, cy);
-  t.obx = t.bx & ~(t.cx - 1);
-  t.oby = t.by & ~(cy - 1);
+  // (a group's origin is a multiple of 32 blocks: masks and tiles agree with the frame's)
+  first_block(a.acs, a.bxs, t.type, t.lcb, t.cx, cy, G.bx0 + t.bx, G.by0 + t.by, t.obx, t.oby);
+  t.obx -= G.bx0;
+  t.oby -= G.by0;
   t.sl = (t.by - t.oby) * t.cx + (t.bx - t.obx);
   t.ogb = (size_t)(G.by0 + t.oby) * a.bxs + G.bx0 + t.obx;
   return t;

@@ -17,8 +17,16 @@
 // `--jxg_report=`, `--jxg_rates=` and `--jxg_ab=` (not cjxl options) append the
 // encode's strategy report, rate report and A/B report against the same encode
 // with other proposals as the CSV text of jxg/harness.py.
+//
+// `--jxg_strategy_in=MAP.pgm [--jxg_qf_in=MAP.pgm]` (not cjxl options) encode
+// with the file's AC-strategy map (and quant field) instead of the search
+// (jxg_encode_forced_rgb8); `--jxg_strategy_out=` / `--jxg_qf_out=` write the
+// maps of whatever was encoded.  One byte per block, binary PGM.  A map of the
+// wrong geometry or one the validator refuses: the reason and the block on
+// stderr, exit 1.  Not with --sweep.
 #include <zlib.h>
 
+#include <cctype>
 #include <charconv>
 #include <chrono>
 #include <cstdint>
@@ -443,6 +451,55 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   return rc;
 }
 
+// --jxg_strategy_in / _out, --jxg_qf_in / _out: a per-block map as a binary
+// PGM (P5, width = xsize_blocks, height = ysize_blocks, maxval 255)
+bool read_pgm(const char* path, std::vector<uint8_t>& map, uint32_t& bw, uint32_t& bh,
+              std::string& err) {
+  std::vector<uint8_t> d;
+  if (!read_file(path, d)) {
+    err = "cannot read the file";
+    return false;
+  }
+  size_t pos = 0;
+  auto token = [&](std::string& t) {  // whitespace- and #-comment-separated header tokens
+    t.clear();
+    while (pos < d.size()) {
+      if (d[pos] == '#') {
+        while (pos < d.size() && d[pos] != '\n') pos++;
+      } else if (std::isspace(d[pos])) {
+        pos++;
+      } else {
+        break;
+      }
+    }
+    while (pos < d.size() && !std::isspace(d[pos])) t.push_back((char)d[pos++]);
+    return !t.empty();
+  };
+  std::string magic, sw, sh, sm;
+  if (!token(magic) || magic != "P5" || !token(sw) || !token(sh) || !token(sm) || sm != "255" ||
+      sw.size() > 6 || sh.size() > 6 || sw.find_first_not_of("0123456789") != std::string::npos ||
+      sh.find_first_not_of("0123456789") != std::string::npos) {
+    err = "not a binary PGM (P5) of maxval 255";
+    return false;
+  }
+  bw = (uint32_t)std::atoi(sw.c_str());
+  bh = (uint32_t)std::atoi(sh.c_str());
+  pos++;  // the single whitespace after maxval
+  if (!bw || !bh || pos > d.size() || d.size() - pos != (size_t)bw * bh) {
+    err = "the PGM's data is not width x height bytes";
+    return false;
+  }
+  map.assign(d.begin() + (long)pos, d.end());
+  return true;
+}
+bool write_pgm(const char* path, const uint8_t* map, uint32_t bw, uint32_t bh) {
+  FILE* f = std::fopen(path, "wb");
+  const bool ok = f && map && std::fprintf(f, "P5\n%u %u\n255\n", bw, bh) > 0 &&
+                  std::fwrite(map, 1, (size_t)bw * bh, f) == (size_t)bw * bh;
+  if (f) std::fclose(f);
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -452,8 +509,10 @@ int main(int argc, char** argv) {
                  "[--proposals=none|P|F|PF] [--coder=ans|prefix] [--gaborish=1|0] "
                  "[--epf=-1|0] [--aq=masking|activity] [--device=N] [--jxg_recon=PATH] "
                  "[--jxg_report=FILE.csv] [--jxg_rates=FILE.csv] "
-                 "[--jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF]]\n"
-                 "       %s INPUT OUTDIR --sweep=LIST [the same flags]   "
+                 "[--jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF]] "
+                 "[--jxg_strategy_in=MAP.pgm [--jxg_qf_in=MAP.pgm]] "
+                 "[--jxg_strategy_out=MAP.pgm] [--jxg_qf_out=MAP.pgm]\n"
+                 "       %s INPUT OUTDIR --sweep=LIST [the same flags, no maps]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
                  argv[0], argv[0]);
@@ -479,6 +538,11 @@ int main(int argc, char** argv) {
   // --proposals) is appended; the codestreams written are unchanged
   const char* ab_path = nullptr;
   uint32_t ab_base = 0;
+  // --jxg_strategy_in=MAP.pgm [--jxg_qf_in=MAP.pgm] (not cjxl options): the
+  // forced encode (jxg_encode_forced_rgb8) with the file's AC-strategy map and
+  // quant field; --jxg_strategy_out= / --jxg_qf_out=: the maps of whatever was
+  // encoded.  Binary PGMs of xsize_blocks x ysize_blocks, one byte per block
+  const char *acs_in = nullptr, *qf_in = nullptr, *acs_out = nullptr, *qf_out = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -531,11 +595,32 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(a, "--jxg_ab_base=", 14)) {
       const char* v = a + 14;
       ab_base = (std::strchr(v, 'P') ? JXG_PROPOSAL_P : 0u) | (std::strchr(v, 'F') ? JXG_PROPOSAL_F : 0u);
-    } else {
+    } else if (!std::strncmp(a, "--jxg_strategy_in=", 18))
+      acs_in = a + 18;
+    else if (!std::strncmp(a, "--jxg_qf_in=", 12))
+      qf_in = a + 12;
+    else if (!std::strncmp(a, "--jxg_strategy_out=", 19))
+      acs_out = a + 19;
+    else if (!std::strncmp(a, "--jxg_qf_out=", 13))
+      qf_out = a + 13;
+    else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
     }
   }
+  if ((acs_in || qf_in) && sweep_path) {
+    std::fprintf(stderr, "--jxg_strategy_in / --jxg_qf_in: not with --sweep\n");
+    return 1;
+  }
+  if ((acs_out || qf_out) && sweep_path) {
+    std::fprintf(stderr, "--jxg_strategy_out / --jxg_qf_out: not with --sweep\n");
+    return 1;
+  }
+  if (qf_in && !acs_in) {
+    std::fprintf(stderr, "--jxg_qf_in needs --jxg_strategy_in (the forced encode)\n");
+    return 1;
+  }
+  if (acs_out || qf_out) p.flags |= JXG_FLAG_KEEP_MAPS;  // (the codestream is the same)
   // JXG_CJXL_TIMING=1: the phases of this call as one JSON line on stderr
   // (bench.py's single_image probe: where a per-image process spends its time)
   using Clk = std::chrono::steady_clock;
@@ -618,9 +703,39 @@ int main(int argc, char** argv) {
     std::fflush(nullptr);
     std::_Exit(rc);  // (as below: no exit-time teardown)
   }
+  // the forced encode's maps: the frame's geometry, then the validator's verdict
+  const uint32_t mbw = (w + 7) / 8, mbh = (h + 7) / 8;
+  std::vector<uint8_t> acs_map, qf_map;
+  for (int k = 0; k < 2; k++) {
+    const char* path = k ? qf_in : acs_in;
+    if (!path) continue;
+    uint32_t bw = 0, bh = 0;
+    std::string perr;
+    if (!read_pgm(path, k ? qf_map : acs_map, bw, bh, perr)) {
+      std::fprintf(stderr, "%s: %s\n", path, perr.c_str());
+      return fail(1);
+    }
+    if (bw != mbw || bh != mbh) {
+      std::fprintf(stderr, "%s: %u x %u blocks, the image has %u x %u\n", path, bw, bh, mbw, mbh);
+      return fail(1);
+    }
+  }
+  if (acs_in) {
+    uint32_t bad = 0;
+    const jxg_status vs = jxg_check_strategy_map(acs_map.data(), w, h, &bad);
+    if (vs != JXG_OK) {
+      std::fprintf(stderr, "%s: strategy map refused (%s) at block %u (row %u, column %u)\n", acs_in,
+                   vs == JXG_ERR_UNSUPPORTED ? "a strategy the forced encode does not take"
+                                             : "not the varblocks of one frame",
+                   bad, bad / mbw, bad % mbw);
+      return fail(1);
+    }
+  }
   jxg_buffer out{};
   const auto t0 = std::chrono::steady_clock::now();
-  st = jxg_encode_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, &out);
+  st = acs_in ? jxg_encode_forced_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, acs_map.data(),
+                                       qf_in ? qf_map.data() : nullptr, &out)
+              : jxg_encode_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, &out);
   const auto t_enc = Clk::now();
   const double sec = std::chrono::duration<double>(t_enc - t0).count();
   if (st != JXG_OK) {
@@ -637,6 +752,22 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::fclose(f);
+  if (acs_out || qf_out) {
+    jxg_stats stats{};
+    st = jxg_get_stats(ctx, &stats);
+    if (st != JXG_OK || !stats.ac_strategy || !stats.quant_field) {
+      std::fprintf(stderr, "no maps to write: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    if (acs_out && !write_pgm(acs_out, stats.ac_strategy, mbw, mbh)) {
+      std::fprintf(stderr, "cannot write %s\n", acs_out);
+      return fail(1);
+    }
+    if (qf_out && !write_pgm(qf_out, stats.quant_field, mbw, mbh)) {
+      std::fprintf(stderr, "cannot write %s\n", qf_out);
+      return fail(1);
+    }
+  }
   if (recon_path) {
     std::vector<uint8_t> rec((size_t)w * h * 3);
     st = jxg_reconstruct_rgb8(ctx, rec.data(), (size_t)w * 3);

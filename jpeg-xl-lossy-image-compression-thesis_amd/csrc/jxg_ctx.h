@@ -142,6 +142,7 @@ struct Ctx : EncArenas {
   bool constants_ready = false;
   // device
   DevBuf<uint8_t> rgb, acs, qf, aqf;  // aqf: masking quant field (JXG_FLAG_AQ_MASKING)
+  DevBuf<uint8_t> force_acs, force_qf;  // a forced encode's uploaded maps
   DevBuf<float> lut;                   // sRGB8 -> linear (the AQ kernel)
   DevBuf<int8_t> cmap;  // [2][tiles] chroma from luma (front kernel)
   DevBuf<uint16_t> nz, mnat;
@@ -326,6 +327,11 @@ struct Job {
   const uint8_t* d_rgb = nullptr;
   int max_s = 0;
   bool homog = false;
+  // forced encode (jxg_encode_forced_rgb8): the caller's validated strategy
+  // map on the device, and its quant field or null (the context's own); the
+  // job runs as effort 7 without proposals, never in a batch
+  const uint8_t* d_force = nullptr;
+  const uint8_t* d_force_qf = nullptr;
   bool ans = false;  // ANS instead of prefix codes for the AC stream
   uint32_t lf = 0;   // frame header loop-filter code (lf_code: Gaborish / EPF)
   uint32_t nhist_ans = 0, max_tokens = 0;
@@ -402,8 +408,11 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out, Clock::time_p
 // one frame through the one-at-a-time path, with the bookkeeping of what
 // jxg_reconstruct_rgb8 may read afterwards (src: host memory, or device memory
 // ordered after the caller's input stream)
+// force_acs: a forced encode -- the caller's strategy map (host memory,
+// validated by jxg_check_strategy_map) and its quant field or null
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
-                      size_t stride, jxg_buffer* out, Clock::time_point t_call);
+                      size_t stride, jxg_buffer* out, Clock::time_point t_call,
+                      const uint8_t* force_acs = nullptr, const uint8_t* force_qf = nullptr);
 jxg_status warmup(Ctx* c, uint32_t w, uint32_t h);
 
 // ---- jxg_pipe.cpp: the streaming pipeline ----

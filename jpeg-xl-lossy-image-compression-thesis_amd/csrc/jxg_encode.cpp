@@ -70,7 +70,9 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
   const jxg_params& P = c->params;
   const Frame& f = J.f;
   const size_t nb = (size_t)f.bxs * f.bys;
-  J.homog = (P.proposals & 3u) != 0;
+  // a forced job computes what an effort-7 encode without proposals computes
+  const int effort = J.d_force ? 7 : P.effort;
+  J.homog = !J.d_force && (P.proposals & 3u) != 0;
   J.ans = (P.flags & JXG_FLAG_ANS) != 0;
   J.lf = lf_code(P.flags, P.distance);
   jxg_status st = init_constants(c);
@@ -81,7 +83,7 @@ jxg_status stage_alloc(Ctx* c, Job& J) {
   JXG_HIP(c->dc.ensure(nb * 3));
   JXG_HIP(c->ac.ensure(nb * 192));
   if (J.homog) JXG_HIP(c->homog.ensure(nb * 3));
-  J.max_s = P.effort >= 6 ? 8 : (P.effort >= 5 ? 4 : 0);  // merge levels
+  J.max_s = effort >= 6 ? 8 : (effort >= 5 ? 4 : 0);  // merge levels
   const uint32_t ntiles = f.tiles_x * f.tiles_y;
   JXG_HIP(c->cmap.ensure((size_t)ntiles * 2));
   if (J.max_s) {
@@ -214,8 +216,8 @@ jxg_status build_front(Ctx* c, Job& J) {
   fa.yp = f.yp;
   fa.tiles_x = f.tiles_x;
   fa.distance = P.distance;
-  fa.effort = P.effort;
-  fa.proposals = P.proposals;
+  fa.effort = J.d_force ? 7 : P.effort;
+  fa.proposals = J.d_force ? 0u : P.proposals;
   fa.h1_int = (P.flags & JXG_FLAG_H1_INT_ABS) ? 1 : 0;
   fa.gab = (P.flags & JXG_FLAG_GABORISH) ? 1 : 0;
   fa.qf_base = f.qf_base;
@@ -231,7 +233,8 @@ jxg_status build_front(Ctx* c, Job& J) {
   fa.ac = c->ac.p;
   fa.nz = c->nz.p;
   fa.homog = J.homog ? c->homog.p : nullptr;
-  fa.ent = J.max_s ? c->ent.p : nullptr;
+  fa.ent = J.max_s && !J.d_force ? c->ent.p : nullptr;  // (forced: force_list_kernel writes it)
+  fa.force = J.d_force;
   fa.xyb_out = J.max_s ? c->xyb_tiles.p : nullptr;
   const bool listed = !J.plan.tiles.empty();
   fa.tile_list = listed ? c->tile_list.p : nullptr;
@@ -241,7 +244,11 @@ jxg_status build_front(Ctx* c, Job& J) {
   // kernel's workgroups: no memset launch
   fa.zero = reinterpret_cast<uint4*>(c->stat.p);
   fa.zero_quads = (uint32_t)(c->stat_bytes / 16);
-  if (P.flags & JXG_FLAG_AQ_MASKING) {
+  if (J.d_force_qf) {
+    // a forced encode's quant field replaces the adaptive one: no aq_kernel
+    J.aq = false;
+    fa.qf_in = J.d_force_qf;
+  } else if (P.flags & JXG_FLAG_AQ_MASKING) {
     // the libjxl-shaped masking quant field of the plan's tiles, before the
     // front kernel (== oracle/aq.c jxo_aq_masking)
     JXG_HIP(c->aqf.ensure((size_t)f.bxs * f.bys));
@@ -282,7 +289,8 @@ jxg_status build_front(Ctx* c, Job& J) {
     ma.tiles_x = f.tiles_x;
     ma.ntiles = listed ? (uint32_t)J.plan.tiles.size() : (J.plan.world == 1 ? f.tiles_x * f.tiles_y : 0);
     ma.tile_list = listed ? c->tile_list.p : nullptr;
-    ma.proposals = P.proposals;
+    ma.proposals = fa.proposals;
+    ma.force = J.d_force;
     ma.max_s = J.max_s;
     ma.G = f.G;
     for (int i = 0; i < 3; i++) {
@@ -307,7 +315,7 @@ jxg_status build_front(Ctx* c, Job& J) {
     ma.nwrite = 256 * 3 * 4;  // CUs x resident workgroups (3) x 4 rounds
   }
   // effort >= 8: the 128 / 256 px levels over the plan's pass groups
-  J.big = J.max_s && P.effort >= 8;
+  J.big = J.max_s && P.effort >= 8 && !J.d_force;
   if (J.big) {
     if (!c->big_ready) {
       static const BigTables bt = build_big_tables();
@@ -397,6 +405,8 @@ static std::vector<A> gather(Job* const* js, uint32_t k, F f) {
 static bool batch_ok(Ctx* const* cs, Job* const* js, uint32_t k) {
   if (k < 1 || k > kMaxBatch) return false;
   const Job& A = *js[0];
+  for (uint32_t i = 0; i < k; i++)
+    if (js[i]->d_force && k > 1) return false;  // a forced job goes alone
   for (uint32_t i = 1; i < k; i++) {
     const Job& B = *js[i];
     if (cs[i]->stream != cs[0]->stream || B.w != A.w || B.h != A.h || B.plan.rank != A.plan.rank ||
@@ -429,7 +439,10 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontDone], s));  // front kernel alone
   if (J.max_s) {
     const auto ma = gather<MergeArgs>(js, k, [](Job& j) { return j.ma; });
-    JXG_HIP(launch_merge(ma.data(), k, s));
+    if (J.d_force)  // the caller's varblocks: no estimates, no resolve
+      JXG_HIP(launch_force_merge(J.ma, s));
+    else
+      JXG_HIP(launch_merge(ma.data(), k, s));
     if (J.big) {  // levels 128 / 256 px (effort >= 8)
       const auto ba = gather<BigArgs>(js, k, [](Job& j) { return j.ba; });
       JXG_HIP(launch_big(ba.data(), k, s));
@@ -932,11 +945,23 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out,
 
 
 static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h,
-                                size_t stride, jxg_buffer* out, Clock::time_point t_call) {
+                                size_t stride, jxg_buffer* out, Clock::time_point t_call,
+                                const uint8_t* force_acs, const uint8_t* force_qf) {
   // streamed frames in flight use this context as a lane (and its helper
   // threads its host state): one-at-a-time calls wait until they are received
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
   Job J;
+  if (force_acs) {  // the (validated) maps of a forced encode, ahead of the kernels on the stream
+    const size_t nb = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    JXG_HIP(c->force_acs.ensure(nb));
+    JXG_HIP(hipMemcpyAsync(c->force_acs.p, force_acs, nb, hipMemcpyHostToDevice, c->stream));
+    J.d_force = c->force_acs.p;
+    if (force_qf) {
+      JXG_HIP(c->force_qf.ensure(nb));
+      JXG_HIP(hipMemcpyAsync(c->force_qf.p, force_qf, nb, hipMemcpyHostToDevice, c->stream));
+      J.d_force_qf = c->force_qf.p;
+    }
+  }
   jxg_status st = enc_launch(c, J, d_rgb, w, h, stride);
   if (st) return st;
   // split assembly for a single context of a multi-group frame (single-group
@@ -947,7 +972,8 @@ static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32
 }
 
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
-                      size_t stride, jxg_buffer* out, Clock::time_point t_call) {
+                      size_t stride, jxg_buffer* out, Clock::time_point t_call,
+                      const uint8_t* force_acs, const uint8_t* force_qf) {
   c->rc.ok = false;
   if (on_device) {
     const jxg_status st = order_input(c, c);
@@ -959,7 +985,7 @@ jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, ui
       return JXG_ERR_HIP;
     src = c->rgb.p;
   }
-  const jxg_status st = encode_device(c, src, w, h, stride, out, t_call);
+  const jxg_status st = encode_device(c, src, w, h, stride, out, t_call, force_acs, force_qf);
   if (!st) {
     c->rc.ok = true;
     c->rc.w = w;

@@ -24,7 +24,25 @@
 #include "jxg_device.h"
 #include "jxg_kernels.h"
 
+// This file is compiled twice.  On its own it holds the two search
+// instantiations of front_kernel.  jxg_front_forced.hip includes it with
+// JXG_FRONT_FORCED_TU defined and instantiates the forced encode's kernel
+// (FORCED, below) alone, everything in namespace jxg::forced_tu with constant
+// tables of its own: instantiations of one template in one translation unit
+// change each other's code (a FORCED instantiation beside them cost the search
+// kernels 16-bit compares and two scalar instructions), and the search path
+// is to pay nothing for the forced one.
 namespace jxg {
+#ifdef JXG_FRONT_FORCED_TU
+namespace forced_tu {
+using jxg::group_lane;  // (overloaded below: jxg_device.h's stay visible)
+using jxg::xor_lane;
+#else
+namespace forced_tu {
+hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], hipStream_t s);
+}
+void launch_front_forced(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
+#endif
 
 __constant__ float c_lut[256];
 // per-lane quantization tables, built on the host from the weights
@@ -1094,7 +1112,16 @@ __device__ unsigned long long g_fprof[12];
 #ifndef JXG_FRONT_WPE  // (experiment builds override it: tools/build_variant.sh)
 #define JXG_FRONT_WPE 4
 #endif
-template <bool HOOKP>
+// FORCED (jxg_encode_forced_rgb8): no search -- phase C
+// evaluates, per wave, only the 8x8-class candidates the caller's map
+// (a.force, validated on the host) names for one of the wave's eight blocks,
+// and a block keeps exactly the candidate its byte names.  A block inside a
+// merged varblock keeps none: merge_write_kernel stores its coefficients,
+// non-zero counts and DC, force_list_kernel its strategy byte; what it needs
+// from here is its quant field (merge_write takes the varblock's maximum).
+// The search instantiations read nothing of this: every FORCED branch below
+// is a compile-time one.
+template <bool HOOKP, bool FORCED>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FRONT_WPE))) void front_kernel(Batch<FrontArgs> bt_) {
   const FrontArgs& a = bt_.a[blockIdx.z];  // the batch's frame
   __shared__ __attribute__((aligned(16))) float sPix[3 * kPlane];
@@ -1404,7 +1431,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
   const float inv_scale = 1.0f / scale;
   FPROF(7);  // DC + AQ
   // ---- phase C: strategy search (FindBest8x8Transform [ext] + hooks) ----
-  const int ncand = a.effort >= 5 ? 6 : 1;
+  // (FORCED: no scan -- one "candidate" makes every search step below a
+  // compile-time no-op, and HOOKP is off, so the rolled loop leaves at once)
+  const int ncand = FORCED ? 1 : (a.effort >= 5 ? 6 : 1);
   const bool hookF = (a.proposals & 2u) != 0 && ncand > 1;
 #ifndef JXG_FRONT_PRUNE  // (A/B builds: -DJXG_FRONT_PRUNE=0)
 #define JXG_FRONT_PRUNE 1
@@ -1447,7 +1476,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
     bi = 4;
     beste = e < FLT_MAX ? e : FLT_MAX;
   }
-  {
+  if constexpr (!FORCED) {
     CandAcc A;
     const Prune pr{ncand > 1 && prune && beste < FLT_MAX, beste, hookF, rh, rv, rd};
     float e = eval_cand<true>(G, kDCT8, scale, inv_scale, A, rty, rtxb, pr);
@@ -1486,6 +1515,40 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
       beste = e;
     }
   }
+  if constexpr (FORCED) {
+    // this block's forced 8x8-class id; -1 inside a merged varblock (first
+    // block or covered): no candidate, zero coefficients and counts
+    const int fv = (int)a.force[gblock()];
+    const bool c8 = fv == kDCT8 || fv == kIDENTITY || fv == kDCT2X2 || fv == kDCT4X4 ||
+                    fv == kDCT4X8 || fv == kDCT8X4;
+    const int ft = c8 ? fv : -1;
+    bt = c8 ? fv : kDCT8;
+#pragma unroll
+    for (int i = 0; i < 12; i++) best.w[i] = 0u;
+    best.nz = 0u;
+    // the candidates in the search's order, each evaluated in full (no
+    // pruning: nothing competes) when any block of the wave asks for it --
+    // the vote is wave-uniform, as a candidate's evaluation must be
+    const Prune pr{false, FLT_MAX, false, 0.0f, 0.0f, 0.0f};
+    if (__any(ft == kDCT8X4)) {
+      CandAcc A;
+      (void)eval_cand<true>(G, kDCT8X4, scale, inv_scale, A, rty, rtxb, pr);
+      copy_q(best, A.q, ft == kDCT8X4);
+    }
+    if (__any(ft == kDCT8)) {
+      CandAcc A;
+      (void)eval_cand<true>(G, kDCT8, scale, inv_scale, A, rty, rtxb, pr);
+      copy_q(best, A.q, ft == kDCT8);
+    }
+#pragma unroll 1
+    for (int idx = 0; idx < 4; idx++) {
+      const int T = idx == 0 ? kDCT4X4 : (idx == 1 ? kDCT4X8 : (idx == 2 ? kDCT2X2 : kIDENTITY));
+      if (!__any(ft == T)) continue;
+      CandAcc A;
+      (void)eval_cand<false>(G, T, scale, inv_scale, A, nullptr, nullptr, pr);
+      copy_q(best, A.q, ft == T);
+    }
+  }
   gb = gblock();
   if (r == 0) {
     a.acs[gb] = (uint8_t)bt;
@@ -1517,6 +1580,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
 }
 
 
+#ifndef JXG_FRONT_FORCED_TU
 // standalone thesis selector over a given XYB frame (parity entry point)
 __global__ __launch_bounds__(kThreads) void homog_kernel(HomogArgs a) {
   __shared__ float sPix[3 * kPlane];
@@ -1560,6 +1624,7 @@ __global__ __launch_bounds__(kThreads) void homog_kernel(HomogArgs a) {
     a.type[b] = partition_of(rh, rv, rd, a.distance);
   }
 }
+#endif  // !JXG_FRONT_FORCED_TU
 
 #ifdef JXG_FRONT_PROFILE
 void dump_front_profile() {
@@ -1635,28 +1700,50 @@ hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], 
     e = hipMemcpyToSymbolAsync(HIP_SYMBOL(c_zz), zz, sizeof(zz), 0, hipMemcpyHostToDevice, s);
   // the static host tables must outlive the copies
   const hipError_t e2 = hipStreamSynchronize(s);
+#ifndef JXG_FRONT_FORCED_TU
+  // the forced kernel's translation unit has tables of its own
+  if (e == hipSuccess && e2 == hipSuccess) return forced_tu::set_front_constants(lut, wts, s);
+#endif
   return e != hipSuccess ? e : e2;
 }
+#ifdef JXG_FRONT_FORCED_TU
+}  // namespace forced_tu
+// one frame of a forced job, every tile (launch_front hands it over)
+void launch_front_forced(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
+  const uint32_t nwg = 8 * ((tiles_x * tiles_y + 7) / 8);  // XCD-aware order (front_kernel)
+  hipLaunchKernelGGL((forced_tu::front_kernel<false, true>), dim3(nwg, 1, 1),
+                     dim3(forced_tu::kThreads), 0, s, make_batch(&a, 1));
+}
+#else
 // (the frames of a batch share their size and parameters)
 void launch_front(const FrontArgs* a, uint32_t k, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
   if (!k) return;
+  if (a[0].force) {  // a forced job: always k = 1, never batched with a search job
+    launch_front_forced(a[0], tiles_x, tiles_y, s);
+    return;
+  }
   const Batch<FrontArgs> b = make_batch(a, k);
   const uint32_t nwg = 8 * ((tiles_x * tiles_y + 7) / 8);  // XCD-aware order (front_kernel)
   if (a[0].proposals & 1u)
-    hipLaunchKernelGGL(front_kernel<true>, dim3(nwg, 1, k), dim3(kThreads), 0, s, b);
+    hipLaunchKernelGGL((front_kernel<true, false>), dim3(nwg, 1, k), dim3(kThreads), 0, s, b);
   else
-    hipLaunchKernelGGL(front_kernel<false>, dim3(nwg, 1, k), dim3(kThreads), 0, s, b);
+    hipLaunchKernelGGL((front_kernel<false, false>), dim3(nwg, 1, k), dim3(kThreads), 0, s, b);
 }
 void launch_front_list(const FrontArgs* a, uint32_t k, uint32_t ntiles, hipStream_t s) {
   if (!ntiles || !k) return;
+  if (a[0].force) {  // a forced job is a whole frame (no sharded form): nothing is launched
+    std::fprintf(stderr, "jxg: launch_front_list: a forced job has no tile list\n");
+    return;
+  }
   const Batch<FrontArgs> b = make_batch(a, k);
   if (a[0].proposals & 1u)
-    hipLaunchKernelGGL(front_kernel<true>, dim3(ntiles, 1, k), dim3(kThreads), 0, s, b);
+    hipLaunchKernelGGL((front_kernel<true, false>), dim3(ntiles, 1, k), dim3(kThreads), 0, s, b);
   else
-    hipLaunchKernelGGL(front_kernel<false>, dim3(ntiles, 1, k), dim3(kThreads), 0, s, b);
+    hipLaunchKernelGGL((front_kernel<false, false>), dim3(ntiles, 1, k), dim3(kThreads), 0, s, b);
 }
 void launch_homog(const HomogArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
   hipLaunchKernelGGL(homog_kernel, dim3(tiles_x, tiles_y), dim3(kThreads), 0, s, a);
 }
+#endif  // JXG_FRONT_FORCED_TU
 
 }  // namespace jxg

@@ -53,8 +53,10 @@ struct FrontArgs {
   uint32_t ntiles_all;  // tiles_x * tiles_y (cmap plane stride)
   uint4* zero;          // the frame's statistics arena, zeroed by the workgroups (or null)
   uint32_t zero_quads;  //   its size in 16-byte units
-  const uint8_t* qf_in; // [nb] raw - 1 of the masking quant field (jxg_aq.hip), or null:
-                        //   the activity heuristic
+  const uint8_t* qf_in; // [nb] raw - 1 of the masking quant field (jxg_aq.hip) or of a forced
+                        //   encode's caller, or null: the activity heuristic
+  const uint8_t* force; // [nb] forced encode: the caller's validated strategy map (the
+                        //   FORCED instantiation alone reads it), or null
 };
 // libjxl-shaped masking quant field (jxg_aq.hip, oracle/aq.c)
 struct AqArgs {
@@ -113,6 +115,8 @@ struct MergeArgs {
   uint32_t nwrite;      // merge_write workgroups (persistent loop over the dense passes)
   const int8_t* cmap;   // [2][tiles_all] chroma from luma (front kernel)
   uint32_t ntiles_all;
+  const uint8_t* force; // [nb] forced encode: the caller's validated strategy map
+                        //   (force_list_kernel in the place of eval + resolve), or null
 };
 // merge levels 128 / 256 px (effort >= 8; jxg_bigvb.hip): kinds 64x128,
 // 128x128, 128x256, 256x256 (stored orientation rows <= cols), and the
@@ -313,6 +317,8 @@ hipError_t set_cluster_table(const uint8_t* tab, hipStream_t s);
 hipError_t set_merge_constants(const float* llf_p /*[4][8]*/, const float* llf_ib /*[4][8][8]*/,
                          hipStream_t s);
 hipError_t launch_merge(const MergeArgs* a, uint32_t k, hipStream_t s);
+// forced encode (one frame): the lists from a.force, then merge_write
+hipError_t launch_force_merge(const MergeArgs& a, hipStream_t s);
 void dump_merge_profile();  // JXG_MERGE_PROFILE experiment builds; no-op otherwise
 void dump_front_profile();  // JXG_FRONT_PROFILE experiment builds; no-op otherwise
 void dump_hist_profile();   // (the same builds: ac_hist's phase clock)

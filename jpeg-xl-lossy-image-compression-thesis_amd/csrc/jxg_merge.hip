@@ -1062,6 +1062,63 @@ __global__ __launch_bounds__(64 * kResolveWaves) void merge_resolve_kernel(Batch
     a.work[merge_list_off(my, a.ntiles) + sCnt[wv][my] + rank] = (uint32_t)tile << 6 | (uint32_t)t;
 }
 
+// Forced encode (jxg_encode_forced_rgb8): the second producer
+// of merge_write's lists, in the place of merge_eval + merge_resolve.  One wave
+// per tile, one lane per block: the bytes of the caller's map (a.force,
+// validated on the host: every merged varblock lies inside its tile and the
+// frame, none overlap) that belong to merged varblocks go into a.acs -- the
+// front kernel wrote the 8x8-class ones -- and every merged first block is
+// appended to its shape's list by resolve's scheme (a ballot per shape, one
+// global atomic per workgroup and shape).  A tile holds at most 64 / blocks
+// varblocks of a shape at any placement, which is the lists' capacity.  The
+// nine counts are zeroed by the launch (launch_force_merge), not here: a
+// workgroup cannot clear what another may already have added to.
+__global__ __launch_bounds__(64 * kResolveWaves) void force_list_kernel(MergeArgs a) {
+  __shared__ uint32_t sCnt[kResolveWaves][kNumShapes];
+  const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const int idx = blockIdx.x * kResolveWaves + wv;
+  int my = -1;  // shape of the forced varblock whose first block is this lane's
+  int tile = 0;
+  if (idx < (int)a.ntiles) {
+    tile = a.tile_list ? (int)a.tile_list[idx] : idx;
+    const int tx = tile % (int)a.tiles_x, ty = tile / (int)a.tiles_x;
+    const int nbx = min(8, (int)a.bxs - tx * 8), nby = min(8, (int)a.bys - ty * 8);
+    const int lbx = t & 7, lby = t >> 3;
+    if (lbx < nbx && lby < nby) {
+      const size_t gb = (size_t)(ty * 8 + lby) * a.bxs + tx * 8 + lbx;
+      const uint8_t v = a.force[gb];
+      int sh = -1;
+#pragma unroll
+      for (int si = 0; si < kNumShapes; si++) sh = (v & 0x7F) == kShapes[si].type ? si : sh;
+      if (sh >= 0) a.acs[gb] = v;
+      if (!(v & 0x80)) my = sh;
+      a.ent[gb] = 0.0f;
+    }
+  }
+  uint32_t rank = 0;
+#pragma unroll
+  for (int si = 0; si < kNumShapes; si++) {
+    const uint64_t bal = __ballot(my == si);
+    if (t == 0) sCnt[wv][si] = (uint32_t)__popcll(bal);
+    if (my == si) rank = (uint32_t)__popcll(bal & ((1ull << t) - 1ull));
+  }
+  __syncthreads();
+  if (threadIdx.x < kNumShapes) {
+    const int si = threadIdx.x;
+    uint32_t tot = 0;
+    for (int w = 0; w < kResolveWaves; w++) tot += sCnt[w][si];
+    uint32_t base = tot ? atomicAdd(a.work + si, tot) : 0u;
+    for (int w = 0; w < kResolveWaves; w++) {  // count -> the wave's first slot
+      const uint32_t n = sCnt[w][si];
+      sCnt[w][si] = base;
+      base += n;
+    }
+  }
+  __syncthreads();
+  if (my >= 0)
+    a.work[merge_list_off(my, a.ntiles) + sCnt[wv][my] + rank] = (uint32_t)tile << 6 | (uint32_t)t;
+}
+
 // one dense pass: entries first .. first + n - 1 of shape si's list, entry k
 // in slot k of the image; returns after its last LDS use
 __device__ __forceinline__ void write_pass(const MergeArgs& a, int si, uint32_t first, uint32_t n,
@@ -1275,6 +1332,17 @@ hipError_t launch_merge(const MergeArgs* a, uint32_t k, hipStream_t s) {
   // the persistent write workgroups: nwrite over the whole launch
   const uint32_t nw = max(1u, min(a[0].nwrite / k, ntiles * (uint32_t)kNumShapes));
   hipLaunchKernelGGL(merge_write_kernel, dim3(nw, 1, k), dim3(kMThreads), 0, s, b);
+  return hipGetLastError();
+}
+// forced encode: the lists from the caller's map, then merge_write as above
+hipError_t launch_force_merge(const MergeArgs& a, hipStream_t s) {
+  if (!a.ntiles || !a.force) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(a.work, 0, kMergeWorkHead * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(force_list_kernel, dim3((a.ntiles + kResolveWaves - 1) / kResolveWaves),
+                     dim3(64 * kResolveWaves), 0, s, a);
+  const uint32_t nw = max(1u, min(a.nwrite, a.ntiles * (uint32_t)kNumShapes));
+  hipLaunchKernelGGL(merge_write_kernel, dim3(nw, 1, 1), dim3(kMThreads), 0, s, make_batch(&a, 1));
   return hipGetLastError();
 }
 void launch_vb_list(const VbArgs* a, uint32_t k, uint32_t nlf, hipStream_t s) {

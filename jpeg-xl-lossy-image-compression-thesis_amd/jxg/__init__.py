@@ -207,6 +207,7 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_set_sweep_rates", "jxg_sweep_rates",
            "jxg_ab_report_rgb8", "jxg_ab_report_rgb8_device",
            "jxg_set_sweep_ab", "jxg_sweep_ab",
+           "jxg_check_strategy_map", "jxg_encode_forced_rgb8", "jxg_encode_forced_rgb8_device",
 )
 
 _lib = None
@@ -320,6 +321,12 @@ def load():
     lib.jxg_ab_report_rgb8_device.argtypes = ab_args
     lib.jxg_set_sweep_ab.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32]
     lib.jxg_sweep_ab.argtypes = [vp, ctypes.POINTER(_AbReport), ctypes.c_uint32]
+    lib.jxg_check_strategy_map.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32,
+                                           ctypes.POINTER(ctypes.c_uint32)]
+    forced_args = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, vp, vp,
+                   ctypes.POINTER(_Buffer)]
+    lib.jxg_encode_forced_rgb8.argtypes = forced_args
+    lib.jxg_encode_forced_rgb8_device.argtypes = forced_args
     _lib = lib
     return lib
 
@@ -400,6 +407,57 @@ class Encoder:
         buf = _Buffer()
         _check(load().jxg_encode_rgb8(self._ctx, rgb.ctypes.data, w, h, w * 3, ctypes.byref(buf)))
         self._last_wh = (w, h)
+        return self._take(buf)
+
+    @staticmethod
+    def _forced_maps(strategy, quant_field, w, h):
+        """the two maps as contiguous uint8 (bys, bxs) arrays (quant_field may be None)"""
+        shp = ((h + 7) // 8, (w + 7) // 8)
+        maps = []
+        for name, m in (("strategy", strategy), ("quant_field", quant_field)):
+            if m is None:
+                maps.append(None)
+                continue
+            m = np.ascontiguousarray(m, dtype=np.uint8)
+            if m.shape != shp:
+                raise ValueError("%s must be uint8 %r for a %d x %d frame, got %r"
+                                 % (name, shp, w, h, m.shape))
+            maps.append(m)
+        return maps
+
+    def encode_forced(self, rgb: np.ndarray, strategy: np.ndarray,
+                      quant_field: "np.ndarray | None" = None) -> bytes:
+        """Host (H, W, 3) uint8 -> codestream bytes with the caller's AC-strategy
+        map instead of the search (jxg_encode_forced_rgb8).  `strategy` is uint8
+        (ysize_blocks, xsize_blocks) in the layout of ``stats()["acs"]`` (see
+        :func:`make_strategy_map`), `quant_field` (optional) the same shape,
+        raw - 1 per block as ``stats()["qf"]``.  A map the validator refuses
+        raises JxgError and leaves the context as it was (:func:`check_strategy_map`
+        names the block)."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        h, w, c = rgb.shape
+        if c != 3:
+            raise ValueError("expected (H, W, 3) uint8")
+        acs, qf = self._forced_maps(strategy, quant_field, w, h)
+        buf = _Buffer()
+        _check(load().jxg_encode_forced_rgb8(self._ctx, rgb.ctypes.data, w, h, w * 3,
+                                             acs.ctypes.data,
+                                             qf.ctypes.data if qf is not None else None,
+                                             ctypes.byref(buf)))
+        self._last_wh = (w, h)
+        return self._take(buf)
+
+    def encode_forced_device(self, ptr: int, width: int, height: int, strategy: np.ndarray,
+                             quant_field: "np.ndarray | None" = None,
+                             row_stride: "int | None" = None) -> bytes:
+        """:meth:`encode_forced` of a device-resident frame (the maps stay host arrays)."""
+        acs, qf = self._forced_maps(strategy, quant_field, width, height)
+        buf = _Buffer()
+        _check(load().jxg_encode_forced_rgb8_device(
+            self._ctx, ctypes.c_void_p(ptr), width, height,
+            row_stride if row_stride is not None else width * 3, acs.ctypes.data,
+            qf.ctypes.data if qf is not None else None, ctypes.byref(buf)))
+        self._last_wh = (width, height)
         return self._take(buf)
 
     def reconstruct(self) -> np.ndarray:
@@ -1064,6 +1122,56 @@ def ab_report_device(enc_a: Encoder, enc_b: Encoder, ptr: int, row_stride: int |
         enc_a._ctx, enc_b._ctx, ctypes.c_void_p(ptr), row_stride or w * 3, ctypes.byref(rep),
         ctypes.c_void_p(block_delta_ptr) if block_delta_ptr else None))
     return rep.as_dict()
+
+
+# ---------------------------------------------------------------------------
+# forced encode (Encoder.encode_forced): maps and their validator (host side)
+# ---------------------------------------------------------------------------
+# the ids a strategy map may hold at a varblock's first block -> (blocks down,
+# blocks across)
+FORCED_SHAPES = {0: (1, 1), 1: (1, 1), 2: (1, 1), 3: (1, 1), 12: (1, 1), 13: (1, 1),
+                 6: (2, 1), 7: (1, 2), 4: (2, 2), 10: (4, 2), 11: (2, 4), 5: (4, 4),
+                 19: (8, 4), 20: (4, 8), 18: (8, 8)}
+
+
+def check_strategy_map(strategy: np.ndarray, xsize: int, ysize: int):
+    """jxg_check_strategy_map (host only): (status, bad_block) -- status 0 when
+    :meth:`Encoder.encode_forced` accepts the map for an xsize x ysize frame,
+    else the jxg_status it would return and the raster index of the first
+    offending block.  A map of another shape than (ysize_blocks, xsize_blocks)
+    raises ValueError."""
+    acs = np.ascontiguousarray(strategy, dtype=np.uint8)
+    if xsize > 0 and ysize > 0 and acs.shape != ((ysize + 7) // 8, (xsize + 7) // 8):
+        raise ValueError("strategy must be uint8 (%d, %d), got %r"
+                         % ((ysize + 7) // 8, (xsize + 7) // 8, acs.shape))
+    bad = ctypes.c_uint32(0)
+    st = load().jxg_check_strategy_map(acs.ctypes.data, xsize, ysize, ctypes.byref(bad))
+    return int(st), int(bad.value)
+
+
+def make_strategy_map(bys: int, bxs: int, varblocks=(), fill: int = 0) -> np.ndarray:
+    """uint8 (bys, bxs) strategy map for :meth:`Encoder.encode_forced`: every
+    (id, block row, block column) of `varblocks` gets its first block's id and
+    0x80 | id on the other blocks it covers, every block left over is the
+    8x8-class id `fill`.  Raises ValueError for an id outside FORCED_SHAPES, a
+    varblock reaching past the map, or overlap (the tile rule is
+    :func:`check_strategy_map`'s to judge)."""
+    if fill not in FORCED_SHAPES or FORCED_SHAPES[fill] != (1, 1):
+        raise ValueError("fill must be an 8x8-class id, got %r" % (fill,))
+    acs = np.full((bys, bxs), fill, np.uint8)
+    used = np.zeros((bys, bxs), bool)
+    for t, by, bx in varblocks:
+        if t not in FORCED_SHAPES:
+            raise ValueError("id %r is not one a forced encode accepts" % (t,))
+        cy, cx = FORCED_SHAPES[t]
+        if by < 0 or bx < 0 or by + cy > bys or bx + cx > bxs:
+            raise ValueError("varblock %r reaches past the map" % ((t, by, bx),))
+        if used[by:by + cy, bx:bx + cx].any():
+            raise ValueError("varblock %r overlaps another" % ((t, by, bx),))
+        used[by:by + cy, bx:bx + cx] = True
+        acs[by:by + cy, bx:bx + cx] = t | 0x80
+        acs[by, bx] = t
+    return acs
 
 
 # ---------------------------------------------------------------------------

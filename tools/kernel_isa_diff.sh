@@ -1,0 +1,50 @@
+#!/bin/bash
+# Compare the gfx950 code of kernels in two builds of one HIP translation unit:
+# per kernel the VGPR / SGPR / scratch figures of both objects and the number
+# of differing lines between their mnemonic sequences (operands dropped: a
+# kernel argument block that grew changes offsets, not instructions).
+#
+#   tools/kernel_isa_diff.sh OLD.hip.o NEW.hip.o [NAME-SUBSTRING ...]
+#
+# e.g. after a change to csrc/jxg_front.hip, against an object kept from the
+# commit before (the search instantiations of front_kernel must
+# not change when the forced one does):
+#   tools/kernel_isa_diff.sh old/jxg_front.hip.o build/jxg_front.hip.o front_kernelILb1 front_kernelILb0
+# A template's mangled name changes with its parameter list (front_kernelILb1EEE
+# became front_kernelILb1ELb0EEE): substrings are matched, first match per object.
+# Without names every kernel of OLD is compared with the kernel of the same name.
+set -euo pipefail
+LLVM=${LLVM:-/opt/rocm/llvm/bin}
+ARCH=${ARCH:-gfx950}
+[ $# -ge 2 ] || { sed -n 2,16p "$0"; exit 2; }
+old=$1; new=$2; shift 2
+tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
+for v in old new; do
+  o=${!v}
+  "$LLVM/llvm-objcopy" --dump-section .hip_fatbin="$tmp/$v.fat" "$o"
+  "$LLVM/clang-offload-bundler" --unbundle --type=o --input="$tmp/$v.fat" \
+    --targets=hipv4-amdgcn-amd-amdhsa--$ARCH --output="$tmp/$v.co"
+  "$LLVM/llvm-objdump" -d "$tmp/$v.co" > "$tmp/$v.s"
+  "$LLVM/llvm-readelf" --notes "$tmp/$v.co" |
+    grep -E "\.name:|\.vgpr_count|\.sgpr_count|\.private_segment_fixed_size" | paste - - - - |
+    sed -E 's/[[:space:]]+/ /g' > "$tmp/$v.res"
+done
+mnemonics() {  # file, symbol
+  awk -v n="$2" '/^[0-9a-f]+ <.*>:/{p=($0 ~ "<" n ">:")} p' "$1" | grep -v '^[0-9a-f]* <' |
+    sed -E 's/^[[:space:]]+//' | awk 'NF{print $1}'
+}
+symbol() { grep -oE "^[0-9a-f]+ <[^>]*$2[^>]*>:" "$1" | head -1 | sed -E 's/^[0-9a-f]+ <(.*)>:/\1/'; }
+[ $# -gt 0 ] || set -- $(grep -oE '^[0-9a-f]+ <[^>]+>:' "$tmp/old.s" | sed -E 's/^[0-9a-f]+ <(.*)>:/\1/')
+rc=0
+for name in "$@"; do
+  so=$(symbol "$tmp/old.s" "$name"); sn=$(symbol "$tmp/new.s" "$name")
+  if [ -z "$so" ] || [ -z "$sn" ]; then echo "$name: not in both objects"; rc=1; continue; fi
+  mnemonics "$tmp/old.s" "$so" > "$tmp/a"; mnemonics "$tmp/new.s" "$sn" > "$tmp/b"
+  d=$(diff "$tmp/a" "$tmp/b" | grep -c '^[<>]' || true)
+  echo "$so -> $sn"
+  echo "  old:$(grep -F " $so " "$tmp/old.res" | sed -E 's/ \.name: [^ ]+//')  instructions $(wc -l < "$tmp/a")"
+  echo "  new:$(grep -F " $sn " "$tmp/new.res" | sed -E 's/ \.name: [^ ]+//')  instructions $(wc -l < "$tmp/b")"
+  echo "  differing mnemonic lines: $d"
+  [ "$d" = 0 ] || rc=1
+done
+exit $rc
