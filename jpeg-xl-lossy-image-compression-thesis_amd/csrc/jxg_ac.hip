@@ -462,7 +462,7 @@ __global__ __launch_bounds__(kAcThreads) void ac_emit_kernel(AcArgs a) {
 // diagonal form: 64 x 68 KB).  20.5 KB of the CU's 160 KB stay free beside a
 // chain workgroup: ans_sums (12.1 KB), ans_emit (14.8 KB), lf_code (17.3 KB),
 // lf_hist, vb_list, merge_resolve and concat workgroups fit there; front (79
-// KB), aq (46 KB), merge_eval / merge_write (37 KB) and ac_hist (31 KB) do not,
+// KB), aq (46 KB), merge_eval (53 KB), merge_write (37 KB) and ac_hist (31 KB) do not,
 // so the 8 CUs of a frame's chains are lost to the transform kernels of the
 // frames behind it.  The chain wave runs at the highest wave priority.
 // Workgroup shape: ONE chain wave per workgroup, not one per SIMD sharing the

@@ -4,23 +4,34 @@
 //
 // Three launches over the 64x64 tiles (the unit of libjxl's ProcessRectACS,
 // combined.diff:346 context):
-//   merge_eval    one 256-thread workgroup per (tile, candidate shape): the
-//                 shape's varblocks tile the 64x64 area, so every workgroup
-//                 does the same amount of work whatever the shape -- no idle
-//                 lanes at barriers.  The tile's XYB planes (written once by
-//                 the front kernel) are copied into an LDS coefficient image
-//                 (48 KB, 3 workgroups per CU) and transformed in place:
-//                   rows    lane = (channel, varblock, row), C-point DCT in
-//                           registers (64-point: two lanes, Lee's even / odd
-//                           halves, wave-uniform);
-//                   columns lane = (channel, varblock, column), same;
+//   merge_eval    one 256-thread workgroup per (tile, width family): the
+//                 candidate shapes whose rows are equally wide (16x8 | 8x16,
+//                 16x16, 32x16 | 16x32, 32x32, 64x32 | 32x64, 64x64).  A
+//                 shape's varblocks tile the 64x64 area, so every shape is
+//                 the same amount of work -- no idle lanes at barriers -- and
+//                 the row DCTs of the tile are the same for every shape of a
+//                 width, so the workgroup runs them once:
+//                   rows    lane = (channel, image row, C-wide segment),
+//                           C-point DCT in registers (64-point: two lanes,
+//                           Lee's even / odd halves, wave-uniform), read from
+//                           the tile's XYB planes (written once by the front
+//                           kernel); Y and X stay in 32 registers per thread,
+//                           B goes to plane 2 of the LDS image (three planes,
+//                           53.7 KB, 3 workgroups per CU);
+//                 then per shape of the family that is searched and fits:
+//                   write   the held Y / X rows -> planes 0 / 1 (the shape's
+//                           valid varblocks);
+//                   columns lane = (channel, band, column pair), in place
+//                           (B: from plane 2 into plane 1 once X is done);
 //                   quant   lane = (channel, 16-row chunk, varblock, column):
 //                           Y first (its dequantized values replace its
 //                           coefficients for the B residual), then X and B;
 //                   reduce  lane = (varblock, column): chunk partials,
 //                           (Y + X) + B, C-lane XOR tree -> estimate (+hook F).
-//                 The nine shape workgroups of a tile get workgroup ids
-//                 congruent mod 8, so they land on one XCD and share its L2.
+//                 The grid keeps a slot per (tile, shape); the four family
+//                 workgroups of a tile are the slots of each family's first
+//                 shape, with ids congruent mod 8, so they land on one XCD
+//                 and share its L2.
 //   merge_resolve one wave per tile: per level (16, 32, 64 px) and region,
 //                 keep / full / two tall / two wide halves with the
 //                 TryMergeAcs comparison (`candidate >= current` keeps: NaN
@@ -55,7 +66,10 @@ __constant__ float c_llf_ib[4 * 64]; // [log2 M][n][k]
 
 constexpr int kMThreads = 256;
 #ifndef JXG_MERGE_WPE
-#define JXG_MERGE_WPE 4  // waves per SIMD the eval kernel is register-capped for (4 WGs / CU)
+// eval: 3 waves / SIMD (168 VGPRs): a family workgroup holds the row-transformed
+// Y and X of its tile in 32 registers per thread, and its three-plane LDS
+// image (EvalLds) admits three workgroups per CU
+#define JXG_MERGE_WPE 3
 #endif
 #ifndef JXG_MERGE_WRITE_WPE
 // write: 3 waves / SIMD (168 VGPRs, 8 B of scratch since round 6's column
@@ -143,20 +157,21 @@ __device__ __forceinline__ void dct64_rest(T* t, int h, Out out) {
 }
 
 // JXG_MERGE_PROFILE (experiment builds only): per (shape, phase) cycle sums
-// of thread 0 of every eval workgroup, printed by dump_merge_profile()
+// of thread 0 of every eval workgroup, printed by dump_merge_profile(); a
+// family's row phase is booked under its first shape
 #ifdef JXG_MERGE_PROFILE
 __device__ unsigned long long g_mprof[16][8];
-#define MPROF_MARK(k)                                                 \
+#define MPROF_MARK(si, k)                                             \
   do {                                                                \
-    if (!WRITE && threadIdx.x == 0) {                                 \
+    if (threadIdx.x == 0) {                                           \
       const unsigned long long now_ = __builtin_readcyclecounter();   \
-      if ((k) > 0) atomicAdd(&g_mprof[P.si][(k)], now_ - mprof_t0);   \
+      if ((k) > 0) atomicAdd(&g_mprof[(si)][(k)], now_ - mprof_t0);   \
       mprof_t0 = now_;                                                \
     }                                                                 \
   } while (0)
 #else
-#define MPROF_MARK(k) \
-  do {                \
+#define MPROF_MARK(si, k) \
+  do {                    \
   } while (0)
 #endif
 // quant_pass's zero votes: counted once per wave and vote in profile builds
@@ -189,11 +204,13 @@ constexpr ShapeDesc kShapes[kNumShapes] = {
 
 __device__ __forceinline__ int bitlen_u(uint32_t v) { return 32 - __clz(v); }
 
-// Two coefficient planes (37.9 KB: four workgroups per CU -- gfx950
-// allocates LDS in 1280-byte granules, 31 granules = 39680 B is the most that
-// fits four; three planes, 53.7 KB, allowed three): plane 0 holds Y (its
-// dequantized values after the Y quantization, for the X / B residuals),
-// plane 1 X, then B -- B is transformed into plane 1 once X is quantized.
+// Two working coefficient planes: plane 0 holds Y (its dequantized values
+// after the Y quantization, for the X / B residuals), plane 1 X, then B -- B
+// is transformed into plane 1 once X is quantized.  gfx950 allocates LDS in
+// 1280-byte granules: merge_write's two planes (38.3 KB) leave room for its
+// three workgroups per CU; the eval kernel's image (EvalLds below) has a third
+// plane, the row-transformed B of the tile, which every shape of the family
+// reads: 53 696 B, 42 granules, three workgroups per CU.
 struct MergeLds {
   float co[2 * kMPlane];  // coefficient image of the tile's varblocks
   float llf[3][64];       // write mode: the LLF of covered block b, per channel
@@ -215,6 +232,20 @@ struct WriteLds : MergeLds {
   uint32_t sgb[32];   // frame block index of its first block
   float skc[2][32];   // its tile's chroma-from-luma factors: X, B
 };
+// merge_eval: three planes (plane 2 = the tile's row-transformed B, written
+// once per workgroup), no LLF
+struct EvalLds {
+  float co[3 * kMPlane];
+  float qsum[3][4][32];
+  float btab[256];
+  float vr3[32][3];
+  int vbits[32];
+  int vnz[32][3];
+  int vraw[32];
+  int valid[32];
+  uint8_t braw[64];
+};
+static_assert(sizeof(EvalLds) <= 42 * 1280, "three eval workgroups per CU: 42 LDS granules each");
 template <class L>
 constexpr bool kIsWrite = std::is_same<L, WriteLds>::value;
 __device__ __forceinline__ float& llf_at(MergeLds& S, int c, int b) { return S.llf[c][b]; }
@@ -255,6 +286,10 @@ struct Pass {
 // find the tiles in L2), at the same merge-stage time (1.81 ms;
 // chunk 16: 435 MB, 1.84 ms -- profiles/r04p/merge_chunk).
 // (a shard's tiles come through a list: tile = list[index])
+// Since the family workgroups (merge_eval_kernel) a tile's slots 0, 1, 4 and 7
+// -- the first shape of each row width -- do the work of their family and the
+// other five leave at once: shape-major slots are family-major workgroups, and
+// a chunk's tiles are read by four workgroups each instead of nine.
 #ifndef JXG_MERGE_CHUNK
 #define JXG_MERGE_CHUNK 32
 #endif
@@ -409,14 +444,19 @@ __device__ __forceinline__ void row_pass(const MergeArgs& a, const Pass& P, L& S
 // lanes; any two columns of a band have the same length, whatever varblocks
 // they belong to): the two LDS reads of a pair are one ds_read2 and the 32
 // lanes of a band read 64 consecutive columns.  64-point: item = (pair, h).
-template <int R, int NCH>
-__device__ __forceinline__ void col_pass(const Pass& P, MergeLds& S, int pass) {
+// B2 (eval, NCH = 1): out of place, from the row-transformed B in plane 2 to
+// plane 1 -- plane 2 stays as it is for the family's next shape, and the
+// two-lane form needs no barrier between its reads and its writes.
+template <int R, int NCH, bool B2 = false, class L>
+__device__ __forceinline__ void col_pass(const Pass& P, L& S, int pass) {
+  static_assert(!B2 || NCH == 1, "the out-of-place form is B's");
   constexpr int lR = ilog2c<R>(), nb = 64 / R, lnb = 6 - lR;
   constexpr int npairs = NCH * nb * 32;  // (channel, band, X)
+  constexpr int dst = B2 ? -kMPlane : 0;  // store offset from the load's
   const int lGX = P.lGX(), lC = P.lC();
   auto col_of = [&](int pidx, int& off, bool& okA, bool& okB) {
     const int X = pidx & 31, band = (pidx >> 5) & (nb - 1), c = pidx >> (5 + lnb);
-    off = pass_plane(pass, c) * kMPlane + band * R * kMS + X;
+    off = (B2 ? 2 : pass_plane(pass, c)) * kMPlane + band * R * kMS + X;
     okA = S.valid[(band << lGX) | (X >> lC)];
     okB = S.valid[(band << lGX) | ((X + 32) >> lC)];
   };
@@ -446,12 +486,12 @@ __device__ __forceinline__ void col_pass(const Pass& P, MergeLds& S, int pass) {
                                f2{q0[(R - 1 - j) * kMS], q0[(R - 1 - j) * kMS + 32]}, j, h);
         dctN_rest<R>(t, h, [&](int k, f2 u) { o[k] = u; });
       }
-      __syncthreads();
+      if constexpr (!B2) __syncthreads();
       if (act) {
 #pragma unroll
         for (int k = 0; k < H; k++) {
-          if (okA) S.co[off + (2 * k + h) * kMS] = o[k].x;
-          if (okB) S.co[off + 32 + (2 * k + h) * kMS] = o[k].y;
+          if (okA) S.co[off + dst + (2 * k + h) * kMS] = o[k].x;
+          if (okB) S.co[off + dst + 32 + (2 * k + h) * kMS] = o[k].y;
         }
       }
     }
@@ -469,8 +509,8 @@ __device__ __forceinline__ void col_pass(const Pass& P, MergeLds& S, int pass) {
 #pragma unroll
       for (int k = 0; k < R; k++) {
         const f2 u = o[k] * kLeeS[lR][k];
-        if (okA) col[k * kMS] = u.x;
-        if (okB) col[k * kMS + 32] = u.y;
+        if (okA) col[dst + k * kMS] = u.x;
+        if (okB) col[dst + k * kMS + 32] = u.y;
       }
     }
   }
@@ -624,9 +664,11 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L&
     auto scaled = [&](int kk) {
       const int ky = ch * RPC + kk;
       const f2 coef = f2{cplane[ky * kMS], cplane[(ky + 1) * kMS]};
-      if (WRITE && llf_col) {
-        if (kk < P.cy()) llf_at(S, CH, (by0 + ky) * 8 + bx0 + x) = coef.x;
-        if (kk + 1 < P.cy()) llf_at(S, CH, (by0 + ky + 1) * 8 + bx0 + x) = coef.y;
+      if constexpr (WRITE) {
+        if (llf_col) {
+          if (kk < P.cy()) llf_at(S, CH, (by0 + ky) * 8 + bx0 + x) = coef.x;
+          if (kk + 1 < P.cy()) llf_at(S, CH, (by0 + ky + 1) * 8 + bx0 + x) = coef.y;
+        }
       }
       f2 rv = coef;
       if (CH != 1) rv = rv - f2{kc, kc} * f2{yd[ky * kMS], yd[(ky + 1) * kMS]};
@@ -733,14 +775,12 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L&
   }
 }
 
-// transform + quantize every valid varblock of the pass; leaves per-varblock
-// bits / non-zeros and the chunk sums in LDS
+// merge_write: transform + quantize every valid varblock of the pass; leaves
+// per-varblock bits / non-zeros and the chunk sums in LDS.  (merge_eval runs
+// the same lee / col_pass / quant_pass bodies from merge_eval_kernel below,
+// with the row pass shared by the shapes of a width: family_rows.)
 template <bool WRITE, class L>
 __device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& P, L& S) {
-#ifdef JXG_MERGE_PROFILE
-  unsigned long long mprof_t0 = 0;
-#endif
-  MPROF_MARK(0);
   auto transform = [&](auto nch_tag, int pass) {
     constexpr int NCH = decltype(nch_tag)::value;
     switch (P.lcx) {
@@ -758,7 +798,6 @@ __device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& 
     }
   };
   transform(std::integral_constant<int, 2>(), 0);  // Y -> plane 0, X -> plane 1
-  MPROF_MARK(1);
   // Y first: its dequantized values replace its coefficients (X / B
   // residuals); then X; then B is transformed into X's plane.  Every pass's
   // tables are in flight across the barrier before it.  A lane's X / B items
@@ -769,7 +808,6 @@ __device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& 
       QTab<RPC> ty;
       load_qtab<RPC, WRITE, 1>(a, P, ty);
       __syncthreads();
-      MPROF_MARK(2);
       quant_pass<RPC, WRITE, 1>(a, P, S, ty);
     }
     QTab<RPC> tx;
@@ -786,16 +824,14 @@ __device__ __forceinline__ void transform_quant(const MergeArgs& a, const Pass& 
   if (P.lcy == 0) quant_yx(std::integral_constant<int, 8>());
   else quant_yx(std::integral_constant<int, 16>());
   __syncthreads();  // plane 1 (X) fully read
-  MPROF_MARK(3);
   transform(std::integral_constant<int, 1>(), 1);  // B -> plane 1
   if (P.lcy == 0) quant_b(std::integral_constant<int, 8>());
   else quant_b(std::integral_constant<int, 16>());
   __syncthreads();
-  MPROF_MARK(4);
 }
 
 // distortion of varblock v: chunk sums in order per channel, (Y + X) + B
-__device__ __forceinline__ float varblock_dist(const Pass& P, const MergeLds& S, int v) {
+__device__ __forceinline__ float varblock_dist(const Pass& P, const EvalLds& S, int v) {
   const int nch = P.lcy == 0 ? 1 : P.R() >> 4;
   float pc[3];
 #pragma unroll
@@ -809,23 +845,31 @@ __device__ __forceinline__ float varblock_dist(const Pass& P, const MergeLds& S,
 
 // AdjustQuantBias of q: 0 -> 0, 1 -> 1 - 0.0700..., else q - 0.145 / q (the
 // per-coefficient expression, tabulated)
-__device__ __forceinline__ void fill_btab(MergeLds& S) {
+template <class L>
+__device__ __forceinline__ void fill_btab(L& S) {
   for (int i = threadIdx.x; i < 256; i += kMThreads)
     S.btab[i] = i == 0 ? 0.0f : (i == 1 ? 1.0f - 0.07005449891748593f : (float)i - 0.145f / (float)i);
 }
-// eval: per-varblock setup, before the tile-load barrier: validity (the
-// level region lies inside the frame's blocks), hook-F indices, sums reset;
-// the blocks' quant field goes to LDS (the varblock maxima are taken after
-// the barrier: vraw_pass)
-__device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& P, MergeLds& S,
-                                                int nbx, int nby) {
+// eval, once per workgroup: the blocks' quant field and the bias table go to
+// LDS (read after the first shape's setup barrier)
+__device__ __forceinline__ void setup_tile(const MergeArgs& a, EvalLds& S, int tx, int ty, int nbx,
+                                           int nby) {
   const int t = threadIdx.x;
   if (t < 64) {
     const int lbx = t & 7, lby = t >> 3;
     const bool in = lbx < nbx && lby < nby;
-    const size_t gb = (size_t)(P.ty * 8 + lby) * a.bxs + P.tx * 8 + lbx;
+    const size_t gb = (size_t)(ty * 8 + lby) * a.bxs + tx * 8 + lbx;
     S.braw[t] = in ? a.qf[gb] : 0;
   }
+  fill_btab(S);
+}
+// eval, per shape, before the barrier that precedes the write-out: validity
+// (the level region lies inside the frame's blocks), hook-F indices, sums
+// reset (the varblock maxima are taken after the barrier: vraw_pass).  Thread
+// v alone touched these words in the previous shape's estimate.
+__device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& P, EvalLds& S,
+                                                int nbx, int nby) {
+  const int t = threadIdx.x;
   if (t < 32) {
     const int v = t;
     bool ok = false;
@@ -844,14 +888,13 @@ __device__ __forceinline__ void setup_varblocks(const MergeArgs& a, const Pass& 
     S.vbits[v] = 0;
     S.vnz[v][0] = S.vnz[v][1] = S.vnz[v][2] = 0;
   }
-  fill_btab(S);
 }
 // varblock quant field = max raw over its covered blocks (after a barrier):
 // one thread per block, an LDS atomic max into its varblock (round 6: one
 // thread per varblock walked up to 64 blocks in a row of dependent LDS reads
 // while its wave's row pass waited; max is order-free, so the result is the
 // same); visible to the quantization after the row pass's barrier
-__device__ __forceinline__ void vraw_pass(const MergeArgs& a, const Pass& P, MergeLds& S) {
+__device__ __forceinline__ void vraw_pass(const MergeArgs& a, const Pass& P, EvalLds& S) {
   (void)a;
   const int b = threadIdx.x;
   if (b < 64) {
@@ -911,35 +954,282 @@ __device__ __forceinline__ int max_level(const MergeArgs& a) {
   return a.max_s >= 8 ? 3 : (a.max_s >= 4 ? 2 : 1);
 }
 
+// ---------------------------------------------------------------------------
+// merge_eval: one workgroup per (tile, width family).  Family f holds the
+// shapes whose rows are C = 8 << f wide: 16x8 | 8x16, 16x16, 32x16 | 16x32,
+// 32x32, 64x32 | 32x64, 64x64.  A C-point row DCT depends on the row segment
+// alone -- its channel, image row Y and segment gx -- not on the height of the
+// varblock it lies in, so the workgroup transforms the tile's rows once:
+//   Y, X  32 scaled outputs per thread, held in registers (hv) for the whole
+//         workgroup and written to planes 0 / 1 at the start of every shape
+//         (only into the varblocks valid for that shape);
+//   B     to plane 2, where it stays; every shape's B column pass reads it
+//         and writes plane 1 (col_pass<R, 1, true>).
+// The float ops of a row are those of row_pass<C>: the same lee<C> on row
+// pairs (f2) for C < 64, and for C = 64 the two-lane form with one row per
+// lane pair instead of two (dct64_first / dct64_rest on float; 256 items of
+// 32 outputs, so that a thread holds 32 values for every C).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int family_first(int f) { return f ? 3 * f - 2 : 0; }  // 0, 1, 4, 7
+__device__ __forceinline__ int family_count(int f) { return f == 0 ? 1 : (f == 3 ? 2 : 3); }
+
+template <int LCX>
+__device__ __forceinline__ void family_rows(const MergeArgs& a, int tile, EvalLds& S, int nbx,
+                                            int nby, float (&hv)[32]) {
+  constexpr int C = 8 << LCX;
+  // A segment is needed if some shape of the family has a valid varblock over
+  // it: validity at a level implies validity at the levels below, so the
+  // family's lowest level (16 px for C <= 16, else C) decides.
+  constexpr int LM = LCX ? LCX : 1;
+  auto need = [&](int Y, int gx) {
+    const int bx0 = gx << LCX, by = Y >> 3;
+    return (((bx0 >> LM) + 1) << LM) <= nbx && (((by >> LM) + 1) << LM) <= nby;
+  };
+  const float* tsrc = a.xyb + (size_t)tile * (3 * 4096);
+  float* bdst = S.co + 2 * kMPlane;
+  if constexpr (C == 64) {
+    // item = (row, half h), h wave-uniform; waves 0 and 1 also take B's rows
+    const int i = threadIdx.x, h = (i >> 6) & 1, row = ((i >> 7) << 6) | (i & 63);
+    const int c = row >> 6, Y = row & 63;
+    auto half_row = [&](const float* src, float* t) {
+      const float4* s0 = reinterpret_cast<const float4*>(src);
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const float4 a0 = s0[q], b0 = s0[15 - q];
+        const float fa0[4] = {a0.x, a0.y, a0.z, a0.w}, fb0[4] = {b0.x, b0.y, b0.z, b0.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) t[4 * q + j] = dct64_first(fa0[j], fb0[3 - j], 4 * q + j, h);
+      }
+    };
+    if (!need(Y, 0)) return;
+    {
+      float t[32];
+      half_row(tsrc + pass_src(0, c) * 4096 + Y * 64, t);
+      dct64_rest(t, h, [&](int k, float o) { hv[k] = o; });
+    }
+    if (i < 128) {  // (row == Y, c == 0)
+      float t[32];
+      half_row(tsrc + 2 * 4096 + Y * 64, t);
+      dct64_rest(t, h, [&](int k, float o) { bdst[Y * kMS + 2 * k + h] = o; });
+    }
+  } else {
+    constexpr int l = ilog2c<C>(), lgx = 3 - LCX, lch = 9 - LCX;  // 1 << lch segments per channel
+    constexpr int PER = (2 << lch) / kMThreads;                   // Y and X: 4, 2, 1 per thread
+    constexpr int NB = 1 << lch, PB = (NB + kMThreads - 1) / kMThreads;  // B: 2, 1, 1 (C = 32: half the threads)
+    // segment r of a pass: gx is the fastest index, so a wave reads whole
+    // 256-byte tile rows
+    auto seg_of = [&](int r, int& c, int& Y, int& gx) {
+      c = r >> lch;
+      const int i = r & (NB - 1);
+      gx = i & ((1 << lgx) - 1);
+      Y = i >> lgx;
+    };
+    float buf[PER][C], bb[PB][C];
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      int c, Y, gx;
+      seg_of(threadIdx.x + k * kMThreads, c, Y, gx);
+      load_row<C>(tsrc + pass_src(0, c) * 4096 + Y * 64 + gx * C, buf[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < PB; k++) {
+      const int r = threadIdx.x + k * kMThreads;
+      if (r < NB) {
+        int c, Y, gx;
+        seg_of(r, c, Y, gx);
+        load_row<C>(tsrc + 2 * 4096 + Y * 64 + gx * C, bb[k]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < C; q++) bb[k][q] = 0.0f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PER; k += 2) {
+      int c0, Y0, gx0, c1 = 0, Y1 = 0, gx1 = 0;
+      seg_of(threadIdx.x + k * kMThreads, c0, Y0, gx0);
+      if (k + 1 < PER) seg_of(threadIdx.x + (k + 1) * kMThreads, c1, Y1, gx1);
+      const bool n0 = need(Y0, gx0), n1 = k + 1 < PER && need(Y1, gx1);
+      if (!n0 && !n1) continue;
+      if constexpr (PER >= 2) {
+        f2 x[C];
+#pragma unroll
+        for (int q = 0; q < C; q++) x[q] = f2{buf[k][q], buf[k + 1][q]};
+        lee<C>(x);
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+          const f2 o = x[q] * kLeeS[l][q];
+          hv[k * C + q] = o.x;
+          hv[(k + 1) * C + q] = o.y;
+        }
+      } else {
+        float* x = buf[k];
+        lee<C>(x);
+#pragma unroll
+        for (int q = 0; q < C; q++) hv[q] = x[q] * kLeeS[l][q];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PB; k += 2) {
+      const int r0 = threadIdx.x + k * kMThreads, r1 = r0 + kMThreads;
+      if (r0 >= NB) continue;
+      int c0, Y0, gx0, c1 = 0, Y1 = 0, gx1 = 0;
+      seg_of(r0, c0, Y0, gx0);
+      if (k + 1 < PB) seg_of(r1, c1, Y1, gx1);
+      const bool n0 = need(Y0, gx0), n1 = k + 1 < PB && r1 < NB && need(Y1, gx1);
+      if (!n0 && !n1) continue;
+      if constexpr (PB >= 2) {
+        f2 x[C];
+#pragma unroll
+        for (int q = 0; q < C; q++) x[q] = f2{bb[k][q], bb[k + 1][q]};
+        lee<C>(x);
+        float* d0 = bdst + Y0 * kMS + gx0 * C;
+        float* d1 = bdst + Y1 * kMS + gx1 * C;
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+          const f2 o = x[q] * kLeeS[l][q];
+          if (n0) d0[q] = o.x;
+          if (n1) d1[q] = o.y;
+        }
+      } else {
+        float* x = bb[k];
+        lee<C>(x);
+        float* d0 = bdst + Y0 * kMS + gx0 * C;
+#pragma unroll
+        for (int q = 0; q < C; q++) d0[q] = x[q] * kLeeS[l][q];
+      }
+    }
+  }
+}
+
+// the held Y / X rows -> planes 0 / 1, for the varblocks valid in this shape
+// (the thread <-> segment map of family_rows)
+template <int LCX>
+__device__ __forceinline__ void family_writeout(const Pass& P, EvalLds& S, const float (&hv)[32]) {
+  constexpr int C = 8 << LCX;
+  if constexpr (C == 64) {
+    const int i = threadIdx.x, h = (i >> 6) & 1, row = ((i >> 7) << 6) | (i & 63);
+    const int c = row >> 6, Y = row & 63;
+    if (!S.valid[Y >> P.lR()]) return;
+    float* d = S.co + pass_plane(0, c) * kMPlane + Y * kMS + h;
+#pragma unroll
+    for (int k = 0; k < 32; k++) d[2 * k] = hv[k];
+  } else {
+    constexpr int lgx = 3 - LCX, lch = 9 - LCX, PER = (2 << lch) / kMThreads;
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      const int r = threadIdx.x + k * kMThreads;
+      const int c = r >> lch, i = r & ((1 << lch) - 1), gx = i & ((1 << lgx) - 1), Y = i >> lgx;
+      if (!S.valid[((Y >> P.lR()) << lgx) | gx]) continue;
+      float* d = S.co + pass_plane(0, c) * kMPlane + Y * kMS + gx * C;
+#pragma unroll
+      for (int q = 0; q < C; q++) d[q] = hv[k * C + q];
+    }
+  }
+}
+
+// The grid keeps one slot per (tile, shape) (decode_wg); a family's workgroup
+// is the slot of its first shape, the other five slots of a tile leave at
+// once.  Shape-major slots are family-major workgroups.
 __global__ __launch_bounds__(kMThreads) __attribute__((amdgpu_waves_per_eu(JXG_MERGE_WPE)))
 void merge_eval_kernel(Batch<MergeArgs> bt_) {
   const MergeArgs& a = bt_.a[blockIdx.z];  // the batch's frame
-  __shared__ __attribute__((aligned(16))) MergeLds S;
+  __shared__ __attribute__((aligned(16))) EvalLds S;
   if (blockIdx.x == 0 && threadIdx.x < kNumShapes) a.work[threadIdx.x] = 0;  // merge_resolve's list counts
-  int tile, si;
-  if (!decode_wg(a, tile, si)) return;
-  const Pass P = make_pass(a, tile, si);
-  if (P.ls > max_level(a)) return;  // level not searched at this effort
-  const int nbx = min(8, (int)a.bxs - P.tx * 8), nby = min(8, (int)a.bys - P.ty * 8);
-  if ((1 << P.ls) > nbx || (1 << P.ls) > nby) return;  // no region of this level fits
+  int tile, si0;
+  if (!decode_wg(a, tile, si0)) return;
+  const int fam = kShapes[si0].lcx;
+  if (si0 != family_first(fam)) return;
+  // the family's lowest level: if it is not searched at this effort or no
+  // region of it fits the tile, none of the family's shapes has work
+  const int lm = max(fam, 1), maxl = max_level(a);
+  const int tx = tile % (int)a.tiles_x, ty = tile / (int)a.tiles_x;
+  const int nbx = min(8, (int)a.bxs - tx * 8), nby = min(8, (int)a.bys - ty * 8);
+  if (lm > maxl || (1 << lm) > nbx || (1 << lm) > nby) return;
 #ifdef JXG_MERGE_PROFILE
-  const unsigned long long t_setup = __builtin_readcyclecounter();
+  unsigned long long mprof_t0 = 0;
 #endif
-  setup_varblocks(a, P, S, nbx, nby);
-  __syncthreads();
-  vraw_pass(a, P, S);
-#ifdef JXG_MERGE_PROFILE
-  if (threadIdx.x == 0) atomicAdd(&g_mprof[P.si][5], __builtin_readcyclecounter() - t_setup);
-#endif
-  transform_quant<false>(a, P, S);
-  const int v = threadIdx.x;
-  if (v < P.NV() && S.valid[v]) {
-    const float dist = varblock_dist(P, S, v);
-    const int tb = bitlen_u((uint32_t)S.vnz[v][0]) + bitlen_u((uint32_t)S.vnz[v][1]) +
-                   bitlen_u((uint32_t)S.vnz[v][2]);
-    float e = ((float)(S.vbits[v] + tb) + 8.0f * dist) * P.tmul;
-    if (a.proposals & 2u) e = hook_f(e, S.vr3[v][0], S.vr3[v][1], S.vr3[v][2]);
-    a.cost[((size_t)tile * kNumShapes + si) * 32 + v] = e;
+  MPROF_MARK(si0, 0);
+  setup_tile(a, S, tx, ty, nbx, nby);
+  float hv[32];
+#pragma unroll
+  for (int q = 0; q < 32; q++) hv[q] = 0.0f;
+  switch (fam) {
+    case 0: family_rows<0>(a, tile, S, nbx, nby, hv); break;
+    case 1: family_rows<1>(a, tile, S, nbx, nby, hv); break;
+    case 2: family_rows<2>(a, tile, S, nbx, nby, hv); break;
+    default: family_rows<3>(a, tile, S, nbx, nby, hv); break;
+  }
+  MPROF_MARK(si0, 6);
+  for (int si = si0; si < si0 + family_count(fam); si++) {
+    const Pass P = make_pass(a, tile, si);
+    // level not searched at this effort, or no region of it fits
+    if (P.ls > maxl || (1 << P.ls) > nbx || (1 << P.ls) > nby) continue;
+    MPROF_MARK(si, 0);
+    setup_varblocks(a, P, S, nbx, nby);
+    __syncthreads();  // validity; the previous shape's reads of planes 0 / 1 are over
+    vraw_pass(a, P, S);
+    switch (fam) {
+      case 0: family_writeout<0>(P, S, hv); break;
+      case 1: family_writeout<1>(P, S, hv); break;
+      case 2: family_writeout<2>(P, S, hv); break;
+      default: family_writeout<3>(P, S, hv); break;
+    }
+    __syncthreads();
+    MPROF_MARK(si, 5);
+    switch (P.lcy) {
+      case 0: col_pass<8, 2>(P, S, 0); break;
+      case 1: col_pass<16, 2>(P, S, 0); break;
+      case 2: col_pass<32, 2>(P, S, 0); break;
+      default: col_pass<64, 2>(P, S, 0); break;
+    }
+    MPROF_MARK(si, 1);
+    // Y first: its dequantized values replace its coefficients (X / B
+    // residuals); then X; then B's columns go from plane 2 into X's plane.
+    // Every pass's tables are in flight across the barrier before it.  A
+    // lane's X / B items read the Y values its own Y item wrote.
+    auto quant_yx = [&](auto rpc_tag) {
+      constexpr int RPC = decltype(rpc_tag)::value;
+      {
+        QTab<RPC> ty_;
+        load_qtab<RPC, false, 1>(a, P, ty_);
+        __syncthreads();
+        MPROF_MARK(si, 2);
+        quant_pass<RPC, false, 1>(a, P, S, ty_);
+      }
+      QTab<RPC> tx_;
+      load_qtab<RPC, false, 0>(a, P, tx_);
+      quant_pass<RPC, false, 0>(a, P, S, tx_);
+    };
+    auto quant_b = [&](auto rpc_tag) {
+      constexpr int RPC = decltype(rpc_tag)::value;
+      QTab<RPC> tb;
+      load_qtab<RPC, false, 2>(a, P, tb);
+      __syncthreads();
+      quant_pass<RPC, false, 2>(a, P, S, tb);
+    };
+    if (P.lcy == 0) quant_yx(std::integral_constant<int, 8>());
+    else quant_yx(std::integral_constant<int, 16>());
+    __syncthreads();  // plane 1 (X) fully read
+    MPROF_MARK(si, 3);
+    switch (P.lcy) {
+      case 0: col_pass<8, 1, true>(P, S, 1); break;
+      case 1: col_pass<16, 1, true>(P, S, 1); break;
+      case 2: col_pass<32, 1, true>(P, S, 1); break;
+      default: col_pass<64, 1, true>(P, S, 1); break;
+    }
+    if (P.lcy == 0) quant_b(std::integral_constant<int, 8>());
+    else quant_b(std::integral_constant<int, 16>());
+    __syncthreads();
+    MPROF_MARK(si, 4);
+    const int v = threadIdx.x;
+    if (v < P.NV() && S.valid[v]) {
+      const float dist = varblock_dist(P, S, v);
+      const int tb = bitlen_u((uint32_t)S.vnz[v][0]) + bitlen_u((uint32_t)S.vnz[v][1]) +
+                     bitlen_u((uint32_t)S.vnz[v][2]);
+      float e = ((float)(S.vbits[v] + tb) + 8.0f * dist) * P.tmul;
+      if (a.proposals & 2u) e = hook_f(e, S.vr3[v][0], S.vr3[v][1], S.vr3[v][2]);
+      a.cost[((size_t)tile * kNumShapes + si) * 32 + v] = e;
+    }
   }
 }
 
@@ -1294,11 +1584,11 @@ __global__ __launch_bounds__(1024) void vb_list_kernel(Batch<VbArgs> bt_) {
 void dump_merge_profile() {
   unsigned long long h[16][8];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mprof), sizeof(h)) != hipSuccess) return;
-  std::fprintf(stderr, "merge_eval cycles (thread 0 sums, Mcycles): shape setup rows+cols(Y,X) "
-                       "qtab quantY+X B(rows,cols,quant)\n");
+  std::fprintf(stderr, "merge_eval cycles (thread 0 sums, Mcycles): shape rows(family) "
+                       "setup+writeout cols(Y,X) qtab quantY+X B(cols,quant)\n");
   for (int si = 0; si < kNumShapes; si++)
-    std::fprintf(stderr, "  %dx%d %8.1f %8.1f %8.1f %8.1f %8.1f\n", 8 << kShapes[si].lcy,
-                 8 << kShapes[si].lcx, h[si][5] / 1e6, h[si][1] / 1e6, h[si][2] / 1e6,
+    std::fprintf(stderr, "  %dx%d %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f\n", 8 << kShapes[si].lcy,
+                 8 << kShapes[si].lcx, h[si][6] / 1e6, h[si][5] / 1e6, h[si][1] / 1e6, h[si][2] / 1e6,
                  h[si][3] / 1e6, h[si][4] / 1e6);
   unsigned long long z[3][2];
   if (hipMemcpyFromSymbol(z, HIP_SYMBOL(g_mzero), sizeof(z)) != hipSuccess) return;
