@@ -22,12 +22,20 @@
 //                   write   the held Y / X rows -> planes 0 / 1 (the shape's
 //                           valid varblocks);
 //                   columns lane = (channel, band, column pair), in place
-//                           (B: from plane 2 into plane 1 once X is done);
+//                           (B: from plane 2 into plane 1 once X is done;
+//                           the family's last shape: see below);
 //                   quant   lane = (channel, 16-row chunk, varblock, column):
 //                           Y first (its dequantized values replace its
 //                           coefficients for the B residual), then X and B;
 //                   reduce  lane = (varblock, column): chunk partials,
 //                           (Y + X) + B, C-lane XOR tree -> estimate (+hook F).
+//                 The last shape a workgroup evaluates (family_last: 16x8,
+//                 32x16, 64x32, 64x64 on a full tile at efforts 6 - 7) has no
+//                 next shape to keep plane 2 for: one column pass over Y, X
+//                 and B, each in place in its own plane, one barrier, then
+//                 Y, X and B quantized back to back (B from plane 2) -- two
+//                 barriers, one table wait and the half-filled B column pass
+//                 fewer than the earlier shapes' path, same float ops.
 //                 The grid keeps a slot per (tile, shape); the four family
 //                 workgroups of a tile are the slots of each family's first
 //                 shape, with ids congruent mod 8, so they land on one XCD
@@ -158,9 +166,11 @@ __device__ __forceinline__ void dct64_rest(T* t, int h, Out out) {
 
 // JXG_MERGE_PROFILE (experiment builds only): per (shape, phase) cycle sums
 // of thread 0 of every eval workgroup, printed by dump_merge_profile(); a
-// family's row phase is booked under its first shape
+// family's row phase is booked under its first shape; B's section is split
+// into columns / tables + barrier / quantization + end barrier (a family's
+// last shape has only the third)
 #ifdef JXG_MERGE_PROFILE
-__device__ unsigned long long g_mprof[16][8];
+__device__ unsigned long long g_mprof[16][10];
 #define MPROF_MARK(si, k)                                             \
   do {                                                                \
     if (threadIdx.x == 0) {                                           \
@@ -233,7 +243,8 @@ struct WriteLds : MergeLds {
   float skc[2][32];   // its tile's chroma-from-luma factors: X, B
 };
 // merge_eval: three planes (plane 2 = the tile's row-transformed B, written
-// once per workgroup), no LLF
+// once per workgroup and consumed in place by the last shape it evaluates),
+// no LLF
 struct EvalLds {
   float co[3 * kMPlane];
   float qsum[3][4][32];
@@ -466,7 +477,13 @@ __device__ __forceinline__ void col_pass(const Pass& P, L& S, int pass) {
   // pairs: R = 32, and the B pass at R = 16) -- each lane then runs half the
   // transform, every thread busy; a barrier separates the column reads from
   // the in-place writes.
-  if constexpr (R == 64 || (R >= 16 && npairs <= kMThreads / 2)) {
+  // NCH = 3 (eval, a family's last shape): Y, X and B in place in planes 0, 1
+  // and 2 (pass_plane(0, c) == c).  R = 64: 96 pairs, 192 threads, one
+  // iteration.  R = 32: 192 pairs in two iterations of the two-lane form (Y
+  // and X, then B on half the threads, as the B pass had it), each with its
+  // own read -> write barrier; one lane per pair would hold 32 f2 values
+  // beside the family's 32 held rows.  R = 16: 384 pairs, one lane each.
+  if constexpr (R == 64 || (R >= 16 && npairs <= kMThreads / 2) || (NCH == 3 && R == 32)) {
     constexpr int H = R / 2;
     constexpr int n = ((npairs + 63) >> 6) << 7;
     for (int i0 = 0; i0 < n; i0 += kMThreads) {
@@ -608,7 +625,8 @@ __device__ __forceinline__ void group_all_reduce(float& cp, int& packed, int C) 
 }
 
 template <int RPC, bool WRITE, int CH, class L>
-__device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L& S, const QTab<RPC>& T) {
+__device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L& S, const QTab<RPC>& T,
+                                           int plane = chan_plane(CH)) {
   static_assert(WRITE == kIsWrite<L>, "the write kernel's LDS carries the per-slot arrays");
   constexpr int cidx = CH == 1 ? 0 : (CH == 0 ? 1 : 2);  // 0 Y, 1 X, 2 B
   // the wave-uniform zero path: the estimate's X and B passes (about 65 % and
@@ -631,7 +649,7 @@ __device__ __forceinline__ void quant_pass(const MergeArgs& a, const Pass& P, L&
     const int bx0 = P.bx0(v), by0 = P.by0(v);  // image position (the LLF's index)
     if constexpr (WRITE && CH != 1) kc = S.skc[CH == 0 ? 0 : 1][v];
     const float scale = (float)a.G * (float)S.vraw[v] / 65536.0f;
-    float* cplane = S.co + P.off(v, chan_plane(CH)) + x;
+    float* cplane = S.co + P.off(v, plane) + x;
     const float* yd = S.co + P.off(v, 0) + x;
     const float* w = T.w[it];
     const float* sd = T.sd[it];
@@ -964,7 +982,9 @@ __device__ __forceinline__ int max_level(const MergeArgs& a) {
 //         workgroup and written to planes 0 / 1 at the start of every shape
 //         (only into the varblocks valid for that shape);
 //   B     to plane 2, where it stays; every shape's B column pass reads it
-//         and writes plane 1 (col_pass<R, 1, true>).
+//         and writes plane 1 (col_pass<R, 1, true>) -- but for the last shape
+//         the workgroup evaluates, which transforms it in place with Y and X
+//         (col_pass<R, 3>) and quantizes B from plane 2.
 // The float ops of a row are those of row_pass<C>: the same lee<C> on row
 // pairs (f2) for C < 64, and for C = 64 the two-lane form with one row per
 // lane pair instead of two (dct64_first / dct64_rest on float; 256 items of
@@ -972,6 +992,24 @@ __device__ __forceinline__ int max_level(const MergeArgs& a) {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int family_first(int f) { return f ? 3 * f - 2 : 0; }  // 0, 1, 4, 7
 __device__ __forceinline__ int family_count(int f) { return f == 0 ? 1 : (f == 3 ? 2 : 3); }
+
+// The last shape of the family that the shape loop evaluates (its own test:
+// the level is searched at this effort and a region of it fits the tile);
+// wave-uniform.  Full tile at efforts 6 and 7: 16x8, 32x16, 64x32, 64x64; at
+// effort 5 or with 4 - 7 blocks: 16x8, 32x16, 32x32; with 2 - 3 blocks: 16x8,
+// 16x16.  Never 8x16 (16x16 is the same level), so its columns have 16 points
+// or more.  JXG_MERGE_LAST=0 (experiment builds): no shape takes the last form.
+#ifndef JXG_MERGE_LAST
+#define JXG_MERGE_LAST 1
+#endif
+__device__ __forceinline__ int family_last(int f, int si0, int maxl, int nbx, int nby) {
+  int last = -1;
+  for (int si = si0; si < si0 + family_count(f); si++) {
+    const int ls = max(kShapes[si].lcy, kShapes[si].lcx);
+    if (ls <= maxl && (1 << ls) <= nbx && (1 << ls) <= nby) last = si;
+  }
+  return JXG_MERGE_LAST && last >= 0 && kShapes[last].lcy >= 1 ? last : -1;
+}
 
 template <int LCX>
 __device__ __forceinline__ void family_rows(const MergeArgs& a, int tile, EvalLds& S, int nbx,
@@ -1160,6 +1198,7 @@ void merge_eval_kernel(Batch<MergeArgs> bt_) {
     default: family_rows<3>(a, tile, S, nbx, nby, hv); break;
   }
   MPROF_MARK(si0, 6);
+  const int si_last = family_last(fam, si0, maxl, nbx, nby);
   for (int si = si0; si < si0 + family_count(fam); si++) {
     const Pass P = make_pass(a, tile, si);
     // level not searched at this effort, or no region of it fits
@@ -1176,17 +1215,31 @@ void merge_eval_kernel(Batch<MergeArgs> bt_) {
     }
     __syncthreads();
     MPROF_MARK(si, 5);
-    switch (P.lcy) {
-      case 0: col_pass<8, 2>(P, S, 0); break;
-      case 1: col_pass<16, 2>(P, S, 0); break;
-      case 2: col_pass<32, 2>(P, S, 0); break;
-      default: col_pass<64, 2>(P, S, 0); break;
+    // The family's last shape has no next shape to keep plane 2 for: B's
+    // columns run with Y's and X's, in place, and B is quantized from plane 2
+    // right behind X -- no barrier until the estimate.
+    const bool last = JXG_MERGE_LAST && si == si_last;
+    if (last) {
+      switch (P.lcy) {  // (never 8 rows: family_last)
+        case 1: col_pass<16, 3>(P, S, 0); break;
+        case 2: col_pass<32, 3>(P, S, 0); break;
+        default: col_pass<64, 3>(P, S, 0); break;
+      }
+    } else {
+      switch (P.lcy) {
+        case 0: col_pass<8, 2>(P, S, 0); break;
+        case 1: col_pass<16, 2>(P, S, 0); break;
+        case 2: col_pass<32, 2>(P, S, 0); break;
+        default: col_pass<64, 2>(P, S, 0); break;
+      }
     }
     MPROF_MARK(si, 1);
     // Y first: its dequantized values replace its coefficients (X / B
-    // residuals); then X; then B's columns go from plane 2 into X's plane.
-    // Every pass's tables are in flight across the barrier before it.  A
-    // lane's X / B items read the Y values its own Y item wrote.
+    // residuals); then X; then, for a shape that is not the last, B's columns
+    // go from plane 2 into X's plane behind a barrier, and B's tables wait out
+    // a second one.  Every pass's tables are in flight across the barrier
+    // before it; the last shape's B tables are issued where X's die.  A lane's
+    // X / B items read the Y values its own Y item wrote.
     auto quant_yx = [&](auto rpc_tag) {
       constexpr int RPC = decltype(rpc_tag)::value;
       {
@@ -1204,18 +1257,26 @@ void merge_eval_kernel(Batch<MergeArgs> bt_) {
       constexpr int RPC = decltype(rpc_tag)::value;
       QTab<RPC> tb;
       load_qtab<RPC, false, 2>(a, P, tb);
-      __syncthreads();
-      quant_pass<RPC, false, 2>(a, P, S, tb);
+      if (!last) {
+        __syncthreads();
+        MPROF_MARK(si, 8);
+      }
+      quant_pass<RPC, false, 2>(a, P, S, tb, last ? 2 : 1);
     };
     if (P.lcy == 0) quant_yx(std::integral_constant<int, 8>());
     else quant_yx(std::integral_constant<int, 16>());
-    __syncthreads();  // plane 1 (X) fully read
-    MPROF_MARK(si, 3);
-    switch (P.lcy) {
-      case 0: col_pass<8, 1, true>(P, S, 1); break;
-      case 1: col_pass<16, 1, true>(P, S, 1); break;
-      case 2: col_pass<32, 1, true>(P, S, 1); break;
-      default: col_pass<64, 1, true>(P, S, 1); break;
+    if (!last) {
+      __syncthreads();  // plane 1 (X) fully read
+      MPROF_MARK(si, 3);
+      switch (P.lcy) {
+        case 0: col_pass<8, 1, true>(P, S, 1); break;
+        case 1: col_pass<16, 1, true>(P, S, 1); break;
+        case 2: col_pass<32, 1, true>(P, S, 1); break;
+        default: col_pass<64, 1, true>(P, S, 1); break;
+      }
+      MPROF_MARK(si, 7);
+    } else {
+      MPROF_MARK(si, 3);
     }
     if (P.lcy == 0) quant_b(std::integral_constant<int, 8>());
     else quant_b(std::integral_constant<int, 16>());
@@ -1582,14 +1643,14 @@ __global__ __launch_bounds__(1024) void vb_list_kernel(Batch<VbArgs> bt_) {
 
 #ifdef JXG_MERGE_PROFILE
 void dump_merge_profile() {
-  unsigned long long h[16][8];
+  unsigned long long h[16][10];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mprof), sizeof(h)) != hipSuccess) return;
   std::fprintf(stderr, "merge_eval cycles (thread 0 sums, Mcycles): shape rows(family) "
-                       "setup+writeout cols(Y,X) qtab quantY+X B(cols,quant)\n");
+                       "setup+writeout cols(Y,X) qtab quantY+X colsB qtabB quantB\n");
   for (int si = 0; si < kNumShapes; si++)
-    std::fprintf(stderr, "  %dx%d %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f\n", 8 << kShapes[si].lcy,
+    std::fprintf(stderr, "  %dx%d %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f\n", 8 << kShapes[si].lcy,
                  8 << kShapes[si].lcx, h[si][6] / 1e6, h[si][5] / 1e6, h[si][1] / 1e6, h[si][2] / 1e6,
-                 h[si][3] / 1e6, h[si][4] / 1e6);
+                 h[si][3] / 1e6, h[si][7] / 1e6, h[si][8] / 1e6, h[si][4] / 1e6);
   unsigned long long z[3][2];
   if (hipMemcpyFromSymbol(z, HIP_SYMBOL(g_mzero), sizeof(z)) != hipSuccess) return;
   for (int c = 0; c < 3; c++)
