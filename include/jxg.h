@@ -188,6 +188,82 @@ jxg_status jxg_encode_forced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t xsi
 jxg_status jxg_encode_forced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsize,
                                          uint32_t ysize, size_t row_stride, const uint8_t* acs,
                                          const uint8_t* qf, jxg_buffer* out);
+/* Traced encode: a search encode that keeps every estimate its AC-strategy
+ * search compared.  jxg_encode_traced_rgb8[_device] is
+ * jxg_encode_rgb8[_device] with the context's distance, effort, proposals and
+ * flags: the same bytes, jxg_get_stats maps, reconstruction and reports.
+ * Effort < 5 has no search: JXG_ERR_UNSUPPORTED, nothing touched (*out =
+ * {NULL, 0}; jxg_reconstruct_rgb8 still serves the encode before).
+ * JXG_ERR_INVALID_ARG wherever jxg_encode_rgb8 returns it and while streamed
+ * frames are pending.  There is no batch, streaming, sweep, sharded or forced
+ * form.
+ *
+ * jxg_search_trace copies the estimates out; either pointer may be NULL.  It
+ * is valid when the context's last use of its buffers was a traced encode,
+ * JXG_ERR_INVALID_ARG otherwise (a plain, forced, batch, streamed, sharded or
+ * warm-up encode, a decode, no encode at all, frames pending).  It changes
+ * nothing the encoder, jxg_reconstruct_rgb8 or the reports read; two calls
+ * give the same bits.
+ *
+ * jxg_trace_maps: caller-owned host planes over the block grid
+ * [ysize_blocks][xsize_blocks] (nb blocks), each may be NULL.
+ *   cand8_raw, cand8  f32 [6][nb]: the 8x8 scan's six estimates before hook F
+ *                     and as compared after it, in scan order DCT8, DCT4X4,
+ *                     DCT2X2, DCT4X8, DCT8X4, IDENTITY; every entry a full
+ *                     evaluation (a traced job does not prune); equal bit for
+ *                     bit without proposals bit 1 (hook F)
+ *   scan8             u8 [nb]: raw id of the scan's winner
+ *   front8            u8 [nb]: raw id the front kernel wrote (differs from
+ *                     scan8 only where hook P overrode a DCT8 win)
+ *   qf8               u8 [nb]: raw - 1 of the front kernel, before merged
+ *                     varblocks take their maxima
+ *   merged            f32 [9][nb], plane order ids 6, 7, 4, 10, 11, 5, 19, 20,
+ *                     18: a candidate varblock's estimate as compared (hook F
+ *                     applied) at its first block on the shape's own grid; NaN
+ *                     everywhere else (not a first block, a candidate that does
+ *                     not fit the frame's blocks, a level the effort does not
+ *                     search: effort 5 stops at 32 px)
+ *   big               f32 [6][nb], plane order ids 22, 23, 21, 25, 26, 24, the
+ *                     same rule; all NaN below effort 8; never +inf
+ *   chosen            f32 [nb]: the final estimate -- of the chosen varblock at
+ *                     its first block, 0 at covered blocks (under hook P the
+ *                     scan's best from before the override)
+ * jxg_trace_summary: exact integers reduced on the GPU; indices 0..5 are the
+ * scan order.
+ *   flip[r][s]        blocks by (winner of the scan replayed on cand8_raw,
+ *                     scan8): diagonal without hook F
+ *   hook_p[t]         overridden blocks by target
+ *   merged_over[s]    blocks by scan8 whose final strategy byte is not of the
+ *                     8x8 class
+ *   margin[s][n]      by scan8; best and second the two lowest of cand8 in the
+ *                     scan's order, n = the number of k in 0..6 with
+ *                     second >= best * (1.0f + 2^-k) in f32
+ *   margin_skipped[s] blocks left out of margin: best not below FLT_MAX, NaN,
+ *                     or <= 0 (hook F's factor may be negative) */
+typedef struct {
+  float* cand8_raw;
+  float* cand8;
+  uint8_t* scan8;
+  uint8_t* front8;
+  uint8_t* qf8;
+  float* merged;
+  float* big;
+  float* chosen;
+} jxg_trace_maps;
+typedef struct {
+  uint32_t blocks;
+  uint32_t max_px; /* largest level searched: 32 (e5), 64 (e6, e7), 256 (e8+) */
+  uint32_t flip[6][6];
+  uint32_t hook_p[6];
+  uint32_t merged_over[6];
+  uint32_t margin[6][8];
+  uint32_t margin_skipped[6];
+} jxg_trace_summary;
+jxg_status jxg_encode_traced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t xsize,
+                                  uint32_t ysize, size_t row_stride, jxg_buffer* out);
+jxg_status jxg_encode_traced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsize,
+                                         uint32_t ysize, size_t row_stride, jxg_buffer* out);
+jxg_status jxg_search_trace(jxg_ctx* ctx, jxg_trace_maps* maps, jxg_trace_summary* summary);
 /* n frames of equal size (benchmark config 3: 64 x 1080p; the reference's
  * caller encodes every image at 10 distances x 5 efforts, benchmark.rs:
  * 637-642), through the streaming pipeline below (jxg_submit_rgb8 of every

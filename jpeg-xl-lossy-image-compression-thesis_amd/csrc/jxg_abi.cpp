@@ -106,6 +106,38 @@ jxg_status jxg_encode_forced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32
   return encode_forced(ctx, d_rgb, true, w, h, stride, acs, qf, out);
 }
 
+// traced encode (jxg_trace.cpp): a search encode that keeps its estimates;
+// without a search (effort < 5) it is refused before the context is touched
+static jxg_status encode_traced(jxg_ctx* ctx, const void* src, bool on_device, uint32_t w,
+                                uint32_t h, size_t stride, jxg_buffer* out) {
+  if (out) *out = jxg_buffer{nullptr, 0};
+  if (!ctx || !src || !out || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;
+  const Clock::time_point t0 = Clock::now();
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  if (st) return st;
+  if (c->params.effort < 5) return JXG_ERR_UNSUPPORTED;
+  return encode_one(c, static_cast<const uint8_t*>(src), on_device, w, h, stride, out, t0, nullptr,
+                    nullptr, true);
+}
+
+jxg_status jxg_encode_traced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                  size_t stride, jxg_buffer* out) {
+  return encode_traced(ctx, rgb, false, w, h, stride, out);
+}
+
+jxg_status jxg_encode_traced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t w, uint32_t h,
+                                         size_t stride, jxg_buffer* out) {
+  return encode_traced(ctx, d_rgb, true, w, h, stride, out);
+}
+
+jxg_status jxg_search_trace(jxg_ctx* ctx, jxg_trace_maps* maps, jxg_trace_summary* summary) {
+  if (!ctx) return JXG_ERR_INVALID_ARG;
+  Ctx* c;
+  const jxg_status st = ctx_enter(ctx, true, &c);
+  return st ? st : search_trace(c, maps, summary);
+}
+
 jxg_status jxg_encode_batch_rgb8(jxg_ctx* ctx, const uint8_t* const* rgbs, uint32_t n, uint32_t w,
                                  uint32_t h, size_t stride, jxg_buffer* outs) {
   if (!ctx || !rgbs || !outs || !frame_args_ok(w, h, stride)) return JXG_ERR_INVALID_ARG;

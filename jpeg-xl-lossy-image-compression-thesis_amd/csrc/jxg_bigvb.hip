@@ -441,7 +441,10 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(4))) void b
     if (!big_region(b, L, gi, r, bx0, by0)) continue;  // (uniform)
     int bx, by;
     const BigShape& sh = big_cand(L, j, bx0, by0, bx, by);
-    const float e = vb_eval<false>(b, sh, bx, by, S, pl, b.cost[cur_index(gi, L, r)]);
+    // (a traced job keeps every estimate: NaN is vb_eval's no-prune path;
+    // big_resolve reads the real current sum)
+    const float cur = b.trace ? __builtin_nanf("") : b.cost[cur_index(gi, L, r)];
+    const float e = vb_eval<false>(b, sh, bx, by, S, pl, cur);
     if (threadIdx.x == 0) b.cost[(size_t)gi * kBigCost + (L == 0 ? r * 5 + j : 20 + j)] = e;
     __syncthreads();
   }

@@ -24,6 +24,10 @@
 // maps of whatever was encoded.  One byte per block, binary PGM.  A map of the
 // wrong geometry or one the validator refuses: the reason and the block on
 // stderr, exit 1.  Not with --sweep.
+//
+// `--jxg_trace=FILE.csv` (not a cjxl option) makes the encode a traced one
+// (jxg_encode_traced_rgb8: the same codestream) and appends the summary of its
+// search trace, one row per scan index.  Not with --sweep or --jxg_strategy_in.
 #include <zlib.h>
 
 #include <cctype>
@@ -302,6 +306,32 @@ bool write_rate_rows(const char* path, const RowKey& key, const struct jxg_rate_
   return std::fclose(f) == 0;
 }
 
+// --jxg_trace=FILE.csv: the summary of the encode's search trace
+// (jxg_search_trace), one row per scan index s: the blocks the 8x8 scan gave to
+// s, of them by the winner of the scan without hook F (flip[r][s]), the hook-P
+// overrides with target s, the blocks merged over, the margin histogram
+bool write_trace_rows(const char* path, const RowKey& key, const jxg_trace_summary& t) {
+  static const int kScanIds[6] = {0, 3, 2, 12, 13, 1};
+  FILE* f = open_csv(path,
+                     "Original Image Name,Compressed Image Name,Distance,Effort,Scan Index,Strategy,"
+                     "Name,Blocks,Max Px,Scan Wins,Raw DCT8,Raw DCT4X4,Raw DCT2X2,Raw DCT4X8,"
+                     "Raw DCT8X4,Raw IDENTITY,Hook P,Merged Over,Margin 0,Margin 1,Margin 2,"
+                     "Margin 3,Margin 4,Margin 5,Margin 6,Margin 7,Margin Skipped\n");
+  if (!f) return false;
+  const std::string lead = key.lead();
+  for (int s = 0; s < 6; s++) {
+    unsigned long long wins = 0;
+    for (int r = 0; r < 6; r++) wins += t.flip[r][s];
+    std::fprintf(f, "%s,%d,%d,%s,%u,%u,%llu", lead.c_str(), s, kScanIds[s],
+                 kStrategyNames[kScanIds[s]], t.blocks, t.max_px, wins);
+    for (int r = 0; r < 6; r++) std::fprintf(f, ",%u", t.flip[r][s]);
+    std::fprintf(f, ",%u,%u", t.hook_p[s], t.merged_over[s]);
+    for (int k = 0; k < 8; k++) std::fprintf(f, ",%u", t.margin[s][k]);
+    std::fprintf(f, ",%u\n", t.margin_skipped[s]);
+  }
+  return std::fclose(f) == 0;
+}
+
 // --jxg_ab=FILE.csv: the rows of jxg/harness.py ab_stats / write_ab_stats for
 // one pair of encodes -- one per non-empty cell of the A/B report
 bool write_ab_rows(const char* path, const RowKey& key, const jxg_ab_report& rep, uint32_t w,
@@ -511,7 +541,7 @@ int main(int argc, char** argv) {
                  "[--jxg_report=FILE.csv] [--jxg_rates=FILE.csv] "
                  "[--jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF]] "
                  "[--jxg_strategy_in=MAP.pgm [--jxg_qf_in=MAP.pgm]] "
-                 "[--jxg_strategy_out=MAP.pgm] [--jxg_qf_out=MAP.pgm]\n"
+                 "[--jxg_strategy_out=MAP.pgm] [--jxg_qf_out=MAP.pgm] [--jxg_trace=FILE.csv]\n"
                  "       %s INPUT OUTDIR --sweep=LIST [the same flags, no maps]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
@@ -543,6 +573,10 @@ int main(int argc, char** argv) {
   // quant field; --jxg_strategy_out= / --jxg_qf_out=: the maps of whatever was
   // encoded.  Binary PGMs of xsize_blocks x ysize_blocks, one byte per block
   const char *acs_in = nullptr, *qf_in = nullptr, *acs_out = nullptr, *qf_out = nullptr;
+  // --jxg_trace=FILE.csv (not a cjxl option): the encode is a traced one
+  // (jxg_encode_traced_rgb8, the same codestream) and its search trace's summary
+  // is appended, one row per scan index; not with --sweep or --jxg_strategy_in
+  const char* trace_path = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -603,6 +637,8 @@ int main(int argc, char** argv) {
       acs_out = a + 19;
     else if (!std::strncmp(a, "--jxg_qf_out=", 13))
       qf_out = a + 13;
+    else if (!std::strncmp(a, "--jxg_trace=", 12))
+      trace_path = a + 12;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -614,6 +650,11 @@ int main(int argc, char** argv) {
   }
   if ((acs_out || qf_out) && sweep_path) {
     std::fprintf(stderr, "--jxg_strategy_out / --jxg_qf_out: not with --sweep\n");
+    return 1;
+  }
+  if (trace_path && (sweep_path || acs_in)) {
+    std::fprintf(stderr, "--jxg_trace: not with %s (a traced encode is one search encode)\n",
+                 sweep_path ? "--sweep" : "--jxg_strategy_in");
     return 1;
   }
   if (qf_in && !acs_in) {
@@ -735,7 +776,8 @@ int main(int argc, char** argv) {
   const auto t0 = std::chrono::steady_clock::now();
   st = acs_in ? jxg_encode_forced_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, acs_map.data(),
                                        qf_in ? qf_map.data() : nullptr, &out)
-              : jxg_encode_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, &out);
+       : trace_path ? jxg_encode_traced_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, &out)
+                    : jxg_encode_rgb8(ctx, rgb.data(), w, h, (size_t)w * 3, &out);
   const auto t_enc = Clk::now();
   const double sec = std::chrono::duration<double>(t_enc - t0).count();
   if (st != JXG_OK) {
@@ -786,6 +828,18 @@ int main(int argc, char** argv) {
   }
   const RowKey key{std::filesystem::path(argv[1]).filename().string(),
                    std::filesystem::path(argv[2]).filename().string(), p.distance, p.effort};
+  if (trace_path) {
+    jxg_trace_summary ts{};
+    st = jxg_search_trace(ctx, nullptr, &ts);
+    if (st != JXG_OK) {
+      std::fprintf(stderr, "search trace failed: %s\n", jxg_status_str(st));
+      return fail(1);
+    }
+    if (!write_trace_rows(trace_path, key, ts)) {
+      std::fprintf(stderr, "cannot write %s\n", trace_path);
+      return fail(1);
+    }
+  }
   if (report_path) {
     jxg_strategy_report rep{};
     st = jxg_strategy_report_rgb8(ctx, rgb.data(), (size_t)w * 3, &rep, nullptr);

@@ -231,6 +231,18 @@ struct Ctx : EncArenas {
     DevBuf<int32_t> delta;
     hipEvent_t ev = nullptr;
   } ab;
+  // search trace (jxg_encode_traced_rgb8 / jxg_search_trace; jxg_trace.cpp),
+  // allocated by the first traced encode: the f32 planes [cand8_raw 6 | cand8 6
+  // | merged 9 | big 6 | chosen 1][nb], the u8 planes [scan8 | front8 | qf8][nb]
+  // and the summary words.  have: the last one-at-a-time encode was a traced
+  // one of a w x h frame (valid as long as rc.ok)
+  struct Trace {
+    DevBuf<float> f;
+    DevBuf<uint8_t> b;
+    DevBuf<uint32_t> sum;
+    bool have = false;
+    uint32_t w = 0, h = 0;
+  } tr;
   // decoder (jxg_decode_rgb8; jxg_decode_dev.cpp), allocated by its first
   // call: the codestream's words, the pass groups' section bounds, the AC
   // stream's decode tables [ctxmap | histograms | prefix or alias tables], the
@@ -332,6 +344,10 @@ struct Job {
   // job runs as effort 7 without proposals, never in a batch
   const uint8_t* d_force = nullptr;
   const uint8_t* d_force_qf = nullptr;
+  // traced encode (jxg_encode_traced_rgb8): a search job whose front kernel,
+  // merge stage and 128 / 256 px levels keep every estimate (c->tr); never in
+  // a batch
+  bool trace = false;
   bool ans = false;  // ANS instead of prefix codes for the AC stream
   uint32_t lf = 0;   // frame header loop-filter code (lf_code: Gaborish / EPF)
   uint32_t nhist_ans = 0, max_tokens = 0;
@@ -412,7 +428,8 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out, Clock::time_p
 // validated by jxg_check_strategy_map) and its quant field or null
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                       size_t stride, jxg_buffer* out, Clock::time_point t_call,
-                      const uint8_t* force_acs = nullptr, const uint8_t* force_qf = nullptr);
+                      const uint8_t* force_acs = nullptr, const uint8_t* force_qf = nullptr,
+                      bool trace = false);
 jxg_status warmup(Ctx* c, uint32_t w, uint32_t h);
 
 // ---- jxg_pipe.cpp: the streaming pipeline ----
@@ -582,6 +599,19 @@ jxg_status ab_share_enqueue(Ctx* c, uint32_t w, uint32_t h);
 jxg_status sweep_ab_enqueue(Ctx* lane, const SweepReq& rq, uint32_t w, uint32_t h);
 jxg_status ab_report_pair(Ctx* a, Ctx* b, const uint8_t* orig, size_t orig_stride, bool on_device,
                           jxg_ab_report* out, int32_t* block_delta);
+
+// ---- jxg_trace.cpp: search trace of a traced encode ----
+constexpr size_t kTracePlanes = 28, kTraceRaw = 0, kTraceCmp = 6, kTraceMerged = 12,
+                 kTraceBig = 21, kTraceChosen = 27;  // f32 planes of Ctx::Trace::f
+// the buffers of a w x h frame (before the job's argument blocks are built)
+jxg_status trace_alloc(Ctx* c, uint32_t w, uint32_t h);
+// the front kernel's trace pointers
+void trace_front_args(Ctx* c, FrontArgs& fa);
+// on the job's stream: the front kernel's quant field, between it and the merge stage
+jxg_status trace_copy_qf(Ctx* c, const Job& J);
+// on the job's stream behind the merge stage: the planes and the summary
+jxg_status trace_enqueue(Ctx* c, const Job& J);
+jxg_status search_trace(Ctx* c, jxg_trace_maps* maps, jxg_trace_summary* summary);
 
 // ---- jxg_decode_dev.cpp ----
 jxg_status decode_rgb8(Ctx* c, const uint8_t* data, size_t size, uint8_t* rgb, size_t row_stride,

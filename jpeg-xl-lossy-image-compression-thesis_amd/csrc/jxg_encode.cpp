@@ -235,6 +235,7 @@ jxg_status build_front(Ctx* c, Job& J) {
   fa.homog = J.homog ? c->homog.p : nullptr;
   fa.ent = J.max_s && !J.d_force ? c->ent.p : nullptr;  // (forced: force_list_kernel writes it)
   fa.force = J.d_force;
+  if (J.trace) trace_front_args(c, fa);
   fa.xyb_out = J.max_s ? c->xyb_tiles.p : nullptr;
   const bool listed = !J.plan.tiles.empty();
   fa.tile_list = listed ? c->tile_list.p : nullptr;
@@ -347,6 +348,7 @@ jxg_status build_front(Ctx* c, Job& J) {
     ba.g0 = J.plan.g0();
     ba.ng = J.plan.ng();
     ba.gxs = f.gxs;
+    ba.trace = J.trace ? 1 : 0;
   }
   J.va = VbArgs{c->acs.p, f.bxs, f.bys, f.lfxs, J.plan.world > 1 ? c->lf_mine.p : nullptr, c->vb.p,
                 c->vcount.d};
@@ -406,7 +408,7 @@ static bool batch_ok(Ctx* const* cs, Job* const* js, uint32_t k) {
   if (k < 1 || k > kMaxBatch) return false;
   const Job& A = *js[0];
   for (uint32_t i = 0; i < k; i++)
-    if (js[i]->d_force && k > 1) return false;  // a forced job goes alone
+    if ((js[i]->d_force || js[i]->trace) && k > 1) return false;  // a forced or traced job goes alone
   for (uint32_t i = 1; i < k; i++) {
     const Job& B = *js[i];
     if (cs[i]->stream != cs[0]->stream || B.w != A.w || B.h != A.h || B.plan.rank != A.plan.rank ||
@@ -437,6 +439,10 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
     launch_front(fa.data(), k, f.tiles_x, f.tiles_y, s);
   JXG_HIP(hipGetLastError());
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontDone], s));  // front kernel alone
+  if (J.trace) {  // the front kernel's quant field, before merged varblocks take their maxima
+    const jxg_status st = trace_copy_qf(cs[0], J);
+    if (st) return st;
+  }
   if (J.max_s) {
     const auto ma = gather<MergeArgs>(js, k, [](Job& j) { return j.ma; });
     if (J.d_force)  // the caller's varblocks: no estimates, no resolve
@@ -460,6 +466,10 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
     }
   }
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvMerged], s));
+  if (J.trace) {  // the trace's planes and summary, while mcost / big_cost are this encode's
+    const jxg_status st = trace_enqueue(cs[0], J);
+    if (st) return st;
+  }
   // (the statistics arenas were zeroed by the front kernel)
   const auto aa = gather<AcArgs>(js, k, [](Job& j) { return j.aa; });
   launch_ac_hist(aa.data(), k, J.plan.ng(), s, J.big);
@@ -946,7 +956,7 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out,
 
 static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h,
                                 size_t stride, jxg_buffer* out, Clock::time_point t_call,
-                                const uint8_t* force_acs, const uint8_t* force_qf) {
+                                const uint8_t* force_acs, const uint8_t* force_qf, bool trace) {
   // streamed frames in flight use this context as a lane (and its helper
   // threads its host state): one-at-a-time calls wait until they are received
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
@@ -962,8 +972,12 @@ static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32
       J.d_force_qf = c->force_qf.p;
     }
   }
-  jxg_status st = enc_launch(c, J, d_rgb, w, h, stride);
-  if (st) return st;
+  jxg_status st;
+  if (trace) {  // the trace's buffers, before the argument blocks point into them
+    if ((st = trace_alloc(c, w, h))) return st;
+    J.trace = true;
+  }
+  if ((st = enc_launch(c, J, d_rgb, w, h, stride))) return st;
   // split assembly for a single context of a multi-group frame (single-group
   // frames are one section; several contexts keep the one-stream assembly)
   const bool split = J.f.ngroups > 1 && lone_context();
@@ -973,8 +987,9 @@ static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32
 
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                       size_t stride, jxg_buffer* out, Clock::time_point t_call,
-                      const uint8_t* force_acs, const uint8_t* force_qf) {
+                      const uint8_t* force_acs, const uint8_t* force_qf, bool trace) {
   c->rc.ok = false;
+  c->tr.have = false;
   if (on_device) {
     const jxg_status st = order_input(c, c);
     if (st) return st;
@@ -985,11 +1000,15 @@ jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, ui
       return JXG_ERR_HIP;
     src = c->rgb.p;
   }
-  const jxg_status st = encode_device(c, src, w, h, stride, out, t_call, force_acs, force_qf);
+  const jxg_status st =
+      encode_device(c, src, w, h, stride, out, t_call, force_acs, force_qf, trace);
   if (!st) {
     c->rc.ok = true;
     c->rc.w = w;
     c->rc.h = h;
+    c->tr.have = trace;
+    c->tr.w = w;
+    c->tr.h = h;
   }
   return st;
 }

@@ -24,7 +24,7 @@
 #include "jxg_device.h"
 #include "jxg_kernels.h"
 
-// This file is compiled twice.  On its own it holds the two search
+// This file is compiled three times.  On its own it holds the two search
 // instantiations of front_kernel.  jxg_front_forced.hip includes it with
 // JXG_FRONT_FORCED_TU defined and instantiates the forced encode's kernel
 // (FORCED, below) alone, everything in namespace jxg::forced_tu with constant
@@ -32,16 +32,37 @@
 // change each other's code (a FORCED instantiation beside them cost the search
 // kernels 16-bit compares and two scalar instructions), and the search path
 // is to pay nothing for the forced one.
+// jxg_front_trace.hip does the same with JXG_FRONT_TRACE_TU for the traced
+// encode (kTrace, below): the two search instantiations once
+// more, in namespace jxg::trace_tu, without pruning and with the stores of
+// every candidate's estimate.
+#if defined(JXG_FRONT_FORCED_TU) || defined(JXG_FRONT_TRACE_TU)
+#define JXG_FRONT_SUB_TU 1
+#endif
+#ifdef JXG_FRONT_TRACE_TU
+#define JXG_FRONT_PRUNE 0  // every entry of a trace is a full evaluation
+#endif
 namespace jxg {
-#ifdef JXG_FRONT_FORCED_TU
+#if defined(JXG_FRONT_FORCED_TU)
 namespace forced_tu {
 using jxg::group_lane;  // (overloaded below: jxg_device.h's stay visible)
 using jxg::xor_lane;
+constexpr bool kTrace = false;
+#elif defined(JXG_FRONT_TRACE_TU)
+namespace trace_tu {
+using jxg::group_lane;
+using jxg::xor_lane;
+constexpr bool kTrace = true;
 #else
 namespace forced_tu {
 hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], hipStream_t s);
 }
+namespace trace_tu {
+hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], hipStream_t s);
+}
 void launch_front_forced(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
+void launch_front_trace(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
+constexpr bool kTrace = false;
 #endif
 
 __constant__ float c_lut[256];
@@ -1470,7 +1491,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
     CandAcc A;
     const Prune pr{false, beste, hookF, rh, rv, rd};
     float e = eval_cand<true>(G, kDCT8X4, scale, inv_scale, A, rty, rtxb, pr);
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[4 * nb + gblock()] = e;
+    }
     if (hookF) e = hook_f(e, rh, rv, rd);
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[10 * nb + gblock()] = e;
+    }
     copy_q(best, A.q, true);
     bt = kDCT8X4;
     bi = 4;
@@ -1480,7 +1507,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
     CandAcc A;
     const Prune pr{ncand > 1 && prune && beste < FLT_MAX, beste, hookF, rh, rv, rd};
     float e = eval_cand<true>(G, kDCT8, scale, inv_scale, A, rty, rtxb, pr);
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[gblock()] = e;
+    }
     if (hookF) e = hook_f(e, rh, rv, rd);
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[6 * nb + gblock()] = e;
+    }
     if (ncand == 1 || beats(e, 0, beste, bi)) {
       copy_q(best, A.q, true);
       bt = kDCT8;
@@ -1496,6 +1529,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
 #pragma unroll 1
   for (int idx = 0;; idx++) {
     const bool over = idx == n1;  // past the scan: hook P's override, if any
+    if constexpr (kTrace) {  // the scan's winner, before the override
+      if (over && r == 0) a.tr_ids[gblock()] = (uint8_t)bt;
+    }
     if (over && !(HOOKP && bt == kDCT8 && pt != kDCT8)) break;
     const int T = over ? pt : (idx == 0 ? kDCT4X4 : (idx == 1 ? kDCT4X8 : (idx == 2 ? kDCT2X2 : kIDENTITY)));
     const int si = idx == 0 ? 1 : (idx == 1 ? 3 : (idx == 2 ? 2 : 5));
@@ -1507,7 +1543,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
       copy_q(best, A.q, true);
       break;
     }
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[(size_t)si * nb + gblock()] = e;
+    }
     if (hookF) e = hook_f(e, rh, rv, rd);
+    if constexpr (kTrace) {
+      if (r == 0) a.tr_est[(size_t)(6 + si) * nb + gblock()] = e;
+    }
     if (beats(e, si, beste, bi)) {
       copy_q(best, A.q, true);
       bt = T;
@@ -1550,6 +1592,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
     }
   }
   gb = gblock();
+  if constexpr (kTrace) {
+    if (r == 0) a.tr_ids[nb + gb] = (uint8_t)bt;
+  }
   if (r == 0) {
     a.acs[gb] = (uint8_t)bt;
     // estimate summed by the merge stage: the search's best, stored before
@@ -1580,7 +1625,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JXG_FR
 }
 
 
-#ifndef JXG_FRONT_FORCED_TU
+#ifndef JXG_FRONT_SUB_TU
 // standalone thesis selector over a given XYB frame (parity entry point)
 __global__ __launch_bounds__(kThreads) void homog_kernel(HomogArgs a) {
   __shared__ float sPix[3 * kPlane];
@@ -1624,7 +1669,7 @@ __global__ __launch_bounds__(kThreads) void homog_kernel(HomogArgs a) {
     a.type[b] = partition_of(rh, rv, rd, a.distance);
   }
 }
-#endif  // !JXG_FRONT_FORCED_TU
+#endif  // !JXG_FRONT_SUB_TU
 
 #ifdef JXG_FRONT_PROFILE
 void dump_front_profile() {
@@ -1700,13 +1745,29 @@ hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], 
     e = hipMemcpyToSymbolAsync(HIP_SYMBOL(c_zz), zz, sizeof(zz), 0, hipMemcpyHostToDevice, s);
   // the static host tables must outlive the copies
   const hipError_t e2 = hipStreamSynchronize(s);
-#ifndef JXG_FRONT_FORCED_TU
-  // the forced kernel's translation unit has tables of its own
-  if (e == hipSuccess && e2 == hipSuccess) return forced_tu::set_front_constants(lut, wts, s);
+#ifndef JXG_FRONT_SUB_TU
+  // the forced and the trace kernels' translation units have tables of their own
+  if (e == hipSuccess && e2 == hipSuccess) {
+    const hipError_t e3 = forced_tu::set_front_constants(lut, wts, s);
+    return e3 != hipSuccess ? e3 : trace_tu::set_front_constants(lut, wts, s);
+  }
 #endif
   return e != hipSuccess ? e : e2;
 }
-#ifdef JXG_FRONT_FORCED_TU
+#if defined(JXG_FRONT_TRACE_TU)
+}  // namespace trace_tu
+// one frame of a traced job, every tile (launch_front hands it over)
+void launch_front_trace(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
+  const uint32_t nwg = 8 * ((tiles_x * tiles_y + 7) / 8);  // XCD-aware order (front_kernel)
+  const Batch<FrontArgs> b = make_batch(&a, 1);
+  if (a.proposals & 1u)
+    hipLaunchKernelGGL((trace_tu::front_kernel<true, false>), dim3(nwg, 1, 1),
+                       dim3(trace_tu::kThreads), 0, s, b);
+  else
+    hipLaunchKernelGGL((trace_tu::front_kernel<false, false>), dim3(nwg, 1, 1),
+                       dim3(trace_tu::kThreads), 0, s, b);
+}
+#elif defined(JXG_FRONT_FORCED_TU)
 }  // namespace forced_tu
 // one frame of a forced job, every tile (launch_front hands it over)
 void launch_front_forced(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
@@ -1722,6 +1783,10 @@ void launch_front(const FrontArgs* a, uint32_t k, uint32_t tiles_x, uint32_t til
     launch_front_forced(a[0], tiles_x, tiles_y, s);
     return;
   }
+  if (a[0].tr_est) {  // a traced job: always k = 1, as a forced one
+    launch_front_trace(a[0], tiles_x, tiles_y, s);
+    return;
+  }
   const Batch<FrontArgs> b = make_batch(a, k);
   const uint32_t nwg = 8 * ((tiles_x * tiles_y + 7) / 8);  // XCD-aware order (front_kernel)
   if (a[0].proposals & 1u)
@@ -1731,8 +1796,8 @@ void launch_front(const FrontArgs* a, uint32_t k, uint32_t tiles_x, uint32_t til
 }
 void launch_front_list(const FrontArgs* a, uint32_t k, uint32_t ntiles, hipStream_t s) {
   if (!ntiles || !k) return;
-  if (a[0].force) {  // a forced job is a whole frame (no sharded form): nothing is launched
-    std::fprintf(stderr, "jxg: launch_front_list: a forced job has no tile list\n");
+  if (a[0].force || a[0].tr_est) {  // a forced or traced job is a whole frame (no sharded form): nothing is launched
+    std::fprintf(stderr, "jxg: launch_front_list: a forced or traced job has no tile list\n");
     return;
   }
   const Batch<FrontArgs> b = make_batch(a, k);
@@ -1744,6 +1809,6 @@ void launch_front_list(const FrontArgs* a, uint32_t k, uint32_t ntiles, hipStrea
 void launch_homog(const HomogArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s) {
   hipLaunchKernelGGL(homog_kernel, dim3(tiles_x, tiles_y), dim3(kThreads), 0, s, a);
 }
-#endif  // JXG_FRONT_FORCED_TU
+#endif  // JXG_FRONT_SUB_TU
 
 }  // namespace jxg

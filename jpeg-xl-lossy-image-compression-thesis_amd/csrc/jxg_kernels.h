@@ -57,6 +57,12 @@ struct FrontArgs {
                         //   encode's caller, or null: the activity heuristic
   const uint8_t* force; // [nb] forced encode: the caller's validated strategy map (the
                         //   FORCED instantiation alone reads it), or null
+  // traced encode (jxg_encode_traced_rgb8; the trace instantiations alone write them), or null:
+  // (two pointers, not four: a 256-byte block would turn the batch index's
+  // multiply into a shift in the search kernels)
+  float* tr_est;        // [2][6 scan index][nb] every candidate's estimate before hook F,
+                        //   then the same as compared (after hook F)
+  uint8_t* tr_ids;      // [2][nb] raw id of the scan's winner, then after hook P's override
 };
 // libjxl-shaped masking quant field (jxg_aq.hip, oracle/aq.c)
 struct AqArgs {
@@ -141,8 +147,30 @@ struct BigArgs {
   uint32_t* kinds;         // [4] varblocks chosen per big kind (statistics arena; the host writes the used kinds' quant tables)
   const uint32_t* glist;   // the plan's pass groups: glist[i], or g0 + i
   uint32_t g0, ng, gxs;
+  int trace;               // traced encode: big_eval evaluates every candidate in full (no +inf)
 };
 hipError_t launch_big(const BigArgs* a, uint32_t k, hipStream_t s);
+// search trace (jxg_trace.hip), behind a traced encode's merge
+// stage.  The planes are over the block grid, nb = bxs * bys.
+constexpr uint32_t kTraceSummaryWords = 2 + 36 + 6 + 6 + 48 + 6;  // jxg_trace_summary as u32 words
+struct TraceArgs {
+  const float* mcost;      // [tiles][9][32] (merge_eval), or null: no merge stage ran
+  const float* big_cost;   // [ng][30] (big_eval), or null: effort < 8
+  const float* ent;        // [nb] the final estimates
+  const uint8_t* acs;      // [nb] the final strategy bytes
+  uint32_t bxs, bys, tiles_x, gxs, ngroups;
+  int max_s;               // largest merged square searched by merge_eval, in blocks (4 or 8)
+  uint32_t max_px;         // largest level searched (summary)
+  const float* cand8;      // [6][nb] (front kernel, trace mode), as compared
+  const float* cand8_raw;  // [6][nb] before hook F
+  const uint8_t* scan8;    // [nb]
+  const uint8_t* front8;   // [nb]
+  float* merged;           // [9][nb] out
+  float* big;              // [6][nb] out
+  float* chosen;           // [nb] out
+  uint32_t* summary;       // [kTraceSummaryWords] out (pre-zeroed)
+};
+hipError_t launch_trace(const TraceArgs& a, hipStream_t s);
 
 // per-LF-group varblock lists (AC metadata channel)
 struct VbArgs {

@@ -166,6 +166,36 @@ class _AbReport(ctypes.Structure):
         return out
 
 
+# search trace (jxg_search_trace): plane orders and the two structures
+TRACE_SCAN_IDS = (0, 3, 2, 12, 13, 1)   # DCT8, DCT4X4, DCT2X2, DCT4X8, DCT8X4, IDENTITY
+TRACE_MERGED_IDS = (6, 7, 4, 10, 11, 5, 19, 20, 18)
+TRACE_BIG_IDS = (22, 23, 21, 25, 26, 24)
+# name -> (planes, dtype) of jxg_trace_maps, in the structure's order
+_TRACE_PLANES = (("cand8_raw", 6, np.float32), ("cand8", 6, np.float32), ("scan8", 0, np.uint8),
+                 ("front8", 0, np.uint8), ("qf8", 0, np.uint8), ("merged", 9, np.float32),
+                 ("big", 6, np.float32), ("chosen", 0, np.float32))
+
+
+class _TraceMaps(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k, _, _ in _TRACE_PLANES]
+
+
+class _TraceSummary(ctypes.Structure):
+    _fields_ = [("blocks", ctypes.c_uint32), ("max_px", ctypes.c_uint32),
+                ("flip", ctypes.c_uint32 * 36), ("hook_p", ctypes.c_uint32 * 6),
+                ("merged_over", ctypes.c_uint32 * 6), ("margin", ctypes.c_uint32 * 48),
+                ("margin_skipped", ctypes.c_uint32 * 6)]
+
+    def as_dict(self) -> dict:
+        """blocks, max_px and the uint32 arrays flip [6, 6], hook_p [6],
+        merged_over [6], margin [6, 8], margin_skipped [6]"""
+        arr = lambda a, *shape: np.array(a, dtype=np.uint32).reshape(shape)  # noqa: E731
+        return {"blocks": int(self.blocks), "max_px": int(self.max_px),
+                "flip": arr(self.flip, 6, 6), "hook_p": arr(self.hook_p, 6),
+                "merged_over": arr(self.merged_over, 6), "margin": arr(self.margin, 6, 8),
+                "margin_skipped": arr(self.margin_skipped, 6)}
+
+
 def rate_symbol_cost(f: int) -> int:
     """jxg_rate_symbol_cost: an ANS symbol of normalised frequency f in 1 / 256 bit"""
     return int(load().jxg_rate_symbol_cost(f))
@@ -208,6 +238,7 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_ab_report_rgb8", "jxg_ab_report_rgb8_device",
            "jxg_set_sweep_ab", "jxg_sweep_ab",
            "jxg_check_strategy_map", "jxg_encode_forced_rgb8", "jxg_encode_forced_rgb8_device",
+           "jxg_encode_traced_rgb8", "jxg_encode_traced_rgb8_device", "jxg_search_trace",
 )
 
 _lib = None
@@ -327,6 +358,12 @@ def load():
                    ctypes.POINTER(_Buffer)]
     lib.jxg_encode_forced_rgb8.argtypes = forced_args
     lib.jxg_encode_forced_rgb8_device.argtypes = forced_args
+    traced_args = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t,
+                   ctypes.POINTER(_Buffer)]
+    lib.jxg_encode_traced_rgb8.argtypes = traced_args
+    lib.jxg_encode_traced_rgb8_device.argtypes = traced_args
+    lib.jxg_search_trace.argtypes = [vp, ctypes.POINTER(_TraceMaps),
+                                     ctypes.POINTER(_TraceSummary)]
     _lib = lib
     return lib
 
@@ -459,6 +496,54 @@ class Encoder:
             qf.ctypes.data if qf is not None else None, ctypes.byref(buf)))
         self._last_wh = (width, height)
         return self._take(buf)
+
+    def encode_traced(self, rgb: np.ndarray) -> bytes:
+        """:meth:`encode` that also keeps, on the device, every estimate the
+        AC-strategy search compared (jxg_encode_traced_rgb8): the same bytes,
+        maps, reconstruction and reports; :meth:`search_trace` fetches the
+        estimates.  Effort < 5 has no search and raises JxgError."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        h, w, c = rgb.shape
+        if c != 3:
+            raise ValueError("expected (H, W, 3) uint8")
+        buf = _Buffer()
+        _check(load().jxg_encode_traced_rgb8(self._ctx, rgb.ctypes.data, w, h, w * 3,
+                                             ctypes.byref(buf)))
+        self._last_wh = (w, h)
+        return self._take(buf)
+
+    def encode_traced_device(self, ptr: int, width: int, height: int,
+                             row_stride: "int | None" = None) -> bytes:
+        """:meth:`encode_traced` of a device-resident frame."""
+        buf = _Buffer()
+        _check(load().jxg_encode_traced_rgb8_device(
+            self._ctx, ctypes.c_void_p(ptr), width, height,
+            row_stride if row_stride is not None else width * 3, ctypes.byref(buf)))
+        self._last_wh = (width, height)
+        return self._take(buf)
+
+    def search_trace(self, maps: bool = True) -> dict:
+        """The trace of the last :meth:`encode_traced` (jxg_search_trace): the
+        summary (``blocks``, ``max_px``, ``flip``, ``hook_p``, ``merged_over``,
+        ``margin``, ``margin_skipped``) and, with `maps`, the planes over the
+        block grid: ``cand8_raw`` / ``cand8`` float32 (6, bys, bxs) in
+        TRACE_SCAN_IDS order, ``scan8`` / ``front8`` / ``qf8`` uint8 (bys, bxs),
+        ``merged`` float32 (9, bys, bxs) in TRACE_MERGED_IDS order, ``big``
+        float32 (6, bys, bxs) in TRACE_BIG_IDS order, ``chosen`` float32
+        (bys, bxs).  Raises JxgError unless the context's last use was a
+        traced encode."""
+        w, h = self._last_wh or (1, 1)
+        bxs, bys = (w + 7) // 8, (h + 7) // 8
+        out, m = {}, _TraceMaps()
+        if maps:
+            for name, planes, dt in _TRACE_PLANES:
+                out[name] = np.empty((planes, bys, bxs) if planes else (bys, bxs), dt)
+                setattr(m, name, out[name].ctypes.data)
+        s = _TraceSummary()
+        _check(load().jxg_search_trace(self._ctx, ctypes.byref(m) if maps else None,
+                                       ctypes.byref(s)))
+        out.update(s.as_dict())
+        return out
 
     def reconstruct(self) -> np.ndarray:
         """(H, W, 3) uint8: the decoded image of the frame last encoded with
