@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "jxg_front_tables.h"
 #include "jxg_tables.h"
 
 namespace jxg {
@@ -115,9 +116,16 @@ jxg_status init_constants(Ctx* c) {
   std::lock_guard<std::mutex> lock(g_const_mu);
   float lut[256];
   srgb_lut(lut);
-  static float wts[5][3][64];
-  quant_weights(wts);
-  JXG_HIP(set_front_constants(lut, wts, c->stream));
+  // front_kernel's tables, to each of its three translation units (the static
+  // host tables outlive the copies: one synchronisation, below)
+  static const FrontTables ft = [&lut] {
+    float wts[5][3][64];
+    quant_weights(wts);
+    return build_front_tables(lut, wts);
+  }();
+  JXG_HIP(upload_front_tables_search(ft, c->stream));
+  JXG_HIP(upload_front_tables_forced(ft, c->stream));
+  JXG_HIP(upload_front_tables_trace(ft, c->stream));
   JXG_HIP(c->lut.ensure(256));
   JXG_HIP(hipMemcpyAsync(c->lut.p, lut, sizeof(lut), hipMemcpyHostToDevice, c->stream));
   uint8_t tab[kAcCtx];

@@ -10,14 +10,9 @@
 #include <stdint.h>
 
 #include "jxg_acmodel.h"
+#include "jxg_coeff.h"
 
 namespace jxg {
-
-// raw AcStrategy ids returned by the thesis selector
-// (proposals/combined.diff:227-233)
-enum : int { kDCT8 = 0, kDCT4X4 = 3, kDCT4X8 = 12, kDCT8X4 = 13 };
-// the two Haar-type 8x8 candidates of the strategy search [ext AcStrategy]
-enum : int { kIDENTITY = 1, kDCT2X2 = 2 };
 
 // opsin absorbance [ext libjxl opsin_params.h]
 constexpr float kM00 = 0.30f, kM01 = 0.622f, kM02 = 0.078f;
@@ -162,63 +157,7 @@ __host__ __device__ __forceinline__ void hybrid420(uint32_t v, uint32_t& tok, ui
   bits = v & ((1u << nb) - 1u);
 }
 
-// natural coefficient order of an 8x8 varblock [ext coeff_order.cc]:
-// zigzag index -> raster position, computable at compile time
-struct Order64 {
-  uint8_t v[64];
-};
-__host__ __device__ constexpr Order64 make_order64() {
-  Order64 o{};
-  int cur = 1;
-  o.v[0] = 0;
-  for (int i = 0; i < 8; i++)
-    for (int j = 0; j <= i; j++) {
-      int x = j, y = i - j;
-      if (i & 1) {
-        int t = x;
-        x = y;
-        y = t;
-      }
-      if (x == 0 && y == 0) continue;
-      o.v[cur++] = (uint8_t)(y * 8 + x);
-    }
-  for (int ip = 7; ip > 0; ip--) {
-    int i = ip - 1;
-    for (int j = 0; j <= i; j++) {
-      int x = 7 - (i - j), y = 7 - j;
-      if (i & 1) {
-        int t = x;
-        x = y;
-        y = t;
-      }
-      o.v[cur++] = (uint8_t)(y * 8 + x);
-    }
-  }
-  return o;
-}
-__host__ __device__ constexpr int c_order_h(int j) { return make_order64().v[j]; }
-__host__ __device__ constexpr int c_inv_order_h(int k) {
-  const Order64 o = make_order64();
-  for (int j = 0; j < 64; j++)
-    if (o.v[j] == k) return j;
-  return 0;
-}
-// transform working-array element (prow, pcol) -> raster position in the
-// 8x8 coefficient layout of strategy T (oracle/front.c co_index); only
-// (0, 0) maps to the DC slot
-__host__ __device__ __forceinline__ int co_index_rt(int T, int prow, int pcol) {
-  if (T == kDCT8) return prow * 8 + pcol;
-  // IDENTITY / DCT2X2: lane pcol's value prow (front kernel haar_lane)
-  if (T == kIDENTITY) return ((pcol >> 2) + 2 * (pcol & 3)) * 8 + (prow >> 2) + 2 * (prow & 3);
-  if (T == kDCT2X2) {
-    const int q = pcol >> 1;
-    const int row = (pcol & 1) ? 4 + q : (prow >= 4 ? q : ((q & 1) ? 2 + (q >> 1) : (q >> 1)));
-    return row * 8 + prow;
-  }
-  if (T == kDCT4X4) return ((prow >> 2) + 2 * (prow & 3)) * 8 + (pcol >> 2) + 2 * (pcol & 3);
-  if (T == kDCT8X4) return ((prow >> 2) + 2 * (prow & 3)) * 8 + pcol;
-  return ((pcol >> 2) + 2 * (pcol & 3)) * 8 + prow;  // kDCT4X8
-}
+// (the strategy ids, the natural order and co_index_rt: jxg_coeff.h)
 
 __device__ __forceinline__ int nz_bucket(int n) {
   if (n >= 64) n = 64;

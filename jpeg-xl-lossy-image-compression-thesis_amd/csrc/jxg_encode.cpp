@@ -425,6 +425,8 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
   const Job& J = *js[0];
   const Frame& f = J.f;
   const bool listed = !J.plan.tiles.empty();
+  // a forced or traced job is a whole frame (rank 0 of 1): it has no tile list
+  if (listed && (J.d_force || J.trace)) return JXG_ERR_INTERNAL;
   const uint32_t ntiles = listed ? (uint32_t)J.plan.tiles.size() : f.tiles_x * f.tiles_y;
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvStart], s));
   if (J.aq) {
@@ -433,10 +435,16 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
   }
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontStart], s));
   const auto fa = gather<FrontArgs>(js, k, [](Job& j) { return j.fa; });
-  if (listed)
+  if (listed) {
     launch_front_list(fa.data(), k, ntiles, s);
-  else if (J.plan.world == 1)
-    launch_front(fa.data(), k, f.tiles_x, f.tiles_y, s);
+  } else if (J.plan.world == 1) {
+    if (J.d_force)  // (batch_ok: k = 1)
+      launch_front_forced(fa[0], f.tiles_x, f.tiles_y, s);
+    else if (J.trace)
+      launch_front_trace(fa[0], f.tiles_x, f.tiles_y, s);
+    else
+      launch_front(fa.data(), k, f.tiles_x, f.tiles_y, s);
+  }
   JXG_HIP(hipGetLastError());
   for (uint32_t i = 0; i < k; i++) JXG_HIP(hipEventRecord(cs[i]->ev[kEvFrontDone], s));  // front kernel alone
   if (J.trace) {  // the front kernel's quant field, before merged varblocks take their maxima

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "jxg_acmodel.h"
+#include "jxg_coeff.h"
 #include "jxg_decode_core.h"
 
 namespace jxg {
@@ -294,16 +295,21 @@ struct ConcatPiece {
   uint32_t pad;
 };
 
-// distortion weight of a coefficient in the strategy search's estimates
-// (== oracle/front.c jxo_dist_weight): sqrt(area / 64) * w0[c] / w, in
-// double, rounded once; w0 = the DCT8 band-0 weights of X, Y, B
-inline float dist_weight(int c, int area, float w) {
-  static const float kW0[3] = {3150.0f, 560.0f, 512.0f};
-  return (float)(std::sqrt((double)area / 64.0) * ((double)kW0[c] / (double)w));
-}
-hipError_t set_front_constants(const float lut[256], const float wts[5][3][64], hipStream_t s);
+// (dist_weight, the estimates' distortion weight: jxg_coeff.h)
+// front_kernel's three translation units (jxg_front.hip: the search;
+// jxg_front_forced.hip; jxg_front_trace.hip), each with constant tables of its
+// own: the host's tables (jxg_front_tables.h) to one unit's, asynchronously --
+// `t` outlives the copies
+struct FrontTables;
+hipError_t upload_front_tables_search(const FrontTables& t, hipStream_t s);
+hipError_t upload_front_tables_forced(const FrontTables& t, hipStream_t s);
+hipError_t upload_front_tables_trace(const FrontTables& t, hipStream_t s);
+// the search: k frames of a batch, every tile / a shard's tile list
 void launch_front(const FrontArgs* a, uint32_t k, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
 void launch_front_list(const FrontArgs* a, uint32_t k, uint32_t ntiles, hipStream_t s);
+// one frame of a forced (a.force) / traced (a.tr_est) job, every tile
+void launch_front_forced(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
+void launch_front_trace(const FrontArgs& a, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
 // shard exchange: per-group block records (acs, qf, dc) <-> frame arrays
 struct PackArgs {
   uint8_t* acs;

@@ -3,7 +3,7 @@
 # output is not expected to be bit-exact): tools/build_patched.sh NAME 'sed script' [FILE ...]
 # -> tools/var/libjxg_NAME.so
 set -e
-NAME=$1; SED=$2; shift 2; FILES=${@:-jxg_front.hip}
+NAME=$1; SED=$2; shift 2; FILES=${@:-jxg_front_kernel.h}
 D=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d /tmp/jxgpatch.XXXX)
 mkdir -p $T/p

@@ -6,17 +6,20 @@
 #
 #   tools/kernel_isa_diff.sh OLD.hip.o NEW.hip.o [NAME-SUBSTRING ...]
 #
-# e.g. after a change to csrc/jxg_front.hip, against an object kept from the
+# e.g. after a change to csrc/jxg_front_kernel.h, against objects kept from the
 # commit before (the search instantiations of front_kernel must
-# not change when the forced one does):
-#   tools/kernel_isa_diff.sh old/jxg_front.hip.o build/jxg_front.hip.o front_kernelILb1 front_kernelILb0
-# A template's mangled name changes with its parameter list (front_kernelILb1EEE
-# became front_kernelILb1ELb0EEE): substrings are matched, first match per object.
+# not change when another unit's do), for each of the three units that include it:
+#   tools/kernel_isa_diff.sh old/jxg_front.hip.o build/jxg_front.hip.o front_kernelILb1 front_kernelILb0 homog_kernel
+#   tools/kernel_isa_diff.sh old/jxg_front_forced.hip.o build/jxg_front_forced.hip.o front_kernelILb0
+#   tools/kernel_isa_diff.sh old/jxg_front_trace.hip.o build/jxg_front_trace.hip.o front_kernelILb1 front_kernelILb0
+# A template's mangled name changes with its parameter list and namespace
+# (jxg12front_kernelILb1ELb0EEE became jxg9search_tu12front_kernelILb1ELb0ELb0EEE):
+# substrings are matched, first match per object.
 # Without names every kernel of OLD is compared with the kernel of the same name.
 set -euo pipefail
 LLVM=${LLVM:-/opt/rocm/llvm/bin}
 ARCH=${ARCH:-gfx950}
-[ $# -ge 2 ] || { sed -n 2,16p "$0"; exit 2; }
+[ $# -ge 2 ] || { sed -n 2,19p "$0"; exit 2; }
 old=$1; new=$2; shift 2
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for v in old new; do
