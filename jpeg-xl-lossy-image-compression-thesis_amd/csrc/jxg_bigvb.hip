@@ -17,7 +17,7 @@
 // global scratch slot (512 persistent workgroups, three column-major planes):
 //   transform  Y first, then X and B: rows from the tile-major XYB copy, then
 //              columns in place, one 32-point Lee DCT per lane in registers
-//              (a vector of 64 / 128 / 256 points over 2 / 4 / 8 adjacent
+//              (lee<32> of jxg_lee.h, the 64x64 tile stage's transform; a vector of 64 / 128 / 256 points over 2 / 4 / 8 adjacent
 //              lanes: the first splits evaluated from the elements, the upper
 //              recombinations by lane shuffles) -- the recursion's float ops;
 //   quantize   Y (its dequantized values replace its coefficients for the X
@@ -36,7 +36,7 @@
 
 #include "jxg_device.h"
 #include "jxg_kernels.h"
-#include "jxg_lee_tables.h"
+#include "jxg_lee.h"
 
 namespace jxg {
 
@@ -61,28 +61,6 @@ struct BigLds {
 
 __device__ __forceinline__ int ilog2i(int n) { return 31 - __clz(n); }
 
-// unnormalized DCT-II in registers, Lee's recursive even/odd split (== the
-// oracle's lee; constants of jxg_lee_tables.h)
-template <int N>
-__device__ __forceinline__ void lee_reg(float* x) {
-  if constexpr (N > 1) {
-    constexpr int h = N / 2, l = N == 2 ? 1 : (N == 4 ? 2 : (N == 8 ? 3 : (N == 16 ? 4 : (N == 32 ? 5 : 6))));
-    float a[h], b[h];
-#pragma unroll
-    for (int i = 0; i < h; i++) {
-      a[i] = x[i] + x[N - 1 - i];
-      b[i] = (x[i] - x[N - 1 - i]) * kLeeC[l][i];
-    }
-    lee_reg<h>(a);
-    lee_reg<h>(b);
-#pragma unroll
-    for (int k = 0; k < h; k++) x[2 * k] = a[k];
-#pragma unroll
-    for (int k = 0; k < h - 1; k++) x[2 * k + 1] = b[k] + b[k + 1];
-    x[N - 1] = b[h - 1];
-  }
-}
-
 // One N-point transform (N = 64, 128, 256) of a vector, element p = ld(p),
 // spread over NP = N / 32 adjacent lanes (D = log2 NP split levels).  Lane
 // r of the group (bit d - 1 of r: s_d, the branch taken at split level d,
@@ -100,7 +78,7 @@ __device__ __forceinline__ float vb_node(Ld ld, int i, int r, const BigLds& S) {
   if constexpr (d == 0) {
     return ld(i);
   } else {
-    constexpr int n = NN >> (d - 1), l = n == 64 ? 6 : (n == 128 ? 7 : 8);
+    constexpr int n = NN >> (d - 1), l = ilog2c<n>();
     const float u0 = vb_node<NN, d - 1>(ld, i, r, S), u1 = vb_node<NN, d - 1>(ld, n - 1 - i, r, S);
     const float c = l == 6 ? kLeeC[6][i] : S.lee_c[l * 128 + i];
     return ((r >> (d - 1)) & 1) ? (u0 - u1) * c : u0 + u1;
@@ -108,7 +86,7 @@ __device__ __forceinline__ float vb_node(Ld ld, int i, int r, const BigLds& S) {
 }
 template <int N, class Ld>
 __device__ __forceinline__ void vb_vec(Ld ld, int r, float* o, const BigLds& S) {
-  constexpr int NP = N / 32, D = NP == 2 ? 1 : (NP == 4 ? 2 : 3);
+  constexpr int NP = N / 32, D = ilog2c<NP>();
 #pragma unroll
   for (int j = 0; j < 32; j++) {
     o[j] = vb_node<N, D>(ld, j, r, S);
@@ -116,7 +94,7 @@ __device__ __forceinline__ void vb_vec(Ld ld, int r, float* o, const BigLds& S) 
     // all 32 x NP leaf loads would spill)
     if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
   }
-  lee_reg<32>(o);
+  lee<32>(o);
   // level D (64 points of v_{D-1}): the b-lanes' odd outputs, in-lane
   const bool bD = (r >> (D - 1)) & 1;
 #pragma unroll
@@ -155,7 +133,7 @@ __device__ __forceinline__ void pass_item(int i, int nv, int& c, int& v, int& r)
 template <int C>
 __device__ __forceinline__ void rows_pass(const MergeArgs& a, int bx, int by, int R, float* pl,
                                           int nch, int c0, int cstep, const BigLds& S) {
-  constexpr int NP = C / 32, L = C == 64 ? 6 : (C == 128 ? 7 : 8);
+  constexpr int NP = C / 32, L = ilog2c<C>();
   const int n = nch * R * NP;
   for (int base = 0; base < n; base += kBT) {
     const int i = base + (int)threadIdx.x;
@@ -184,7 +162,7 @@ __device__ __forceinline__ void rows_pass(const MergeArgs& a, int bx, int by, in
 // columns, in place: every lane of a round computes before any stores
 template <int R>
 __device__ __forceinline__ void cols_pass(int C, float* pl, int nch, int c0, int cstep, const BigLds& S) {
-  constexpr int NP = R / 32, L = R == 64 ? 6 : (R == 128 ? 7 : 8);
+  constexpr int NP = R / 32, L = ilog2c<R>();
   const int n = nch * C * NP;
   for (int base = 0; base < n; base += kBT) {
     const int i = base + (int)threadIdx.x;

@@ -9,6 +9,7 @@
 #include "jxg_acmodel.h"
 #include "jxg_coeff.h"
 #include "jxg_decode_core.h"
+#include "jxg_shapes.h"
 
 namespace jxg {
 
@@ -79,22 +80,8 @@ struct AqArgs {
 };
 void launch_aq(const AqArgs* a, uint32_t k, uint32_t ntiles, hipStream_t s);
 
-// merge stage (jxg_merge.hip): weight kinds (stored orientation) and the
-// nine merged shapes' pixel-orientation tables, column-major ([kx * R + ky])
-constexpr int kNumKinds = 6;
-constexpr int kKindOff[kNumKinds + 1] = {0, 128, 384, 896, 1920, 3968, 8064};
-constexpr int kNumShapes = 9;
-constexpr int kShapeOff[kNumShapes + 1] = {0, 128, 256, 512, 1024, 1536, 2560, 4608, 6656, 10752};
-// merge_write's varblock lists (MergeArgs::work): a tile holds at most
-// 64 / (blocks of the shape) varblocks of a shape, so list si has room for
-// ntiles * kShapeSlots[si] entries (every block pair merged: 105 per tile)
-constexpr int kMergeWorkHead = 16;  // the nine counts, padded
-constexpr int kShapeSlots[kNumShapes] = {32, 32, 16, 8, 8, 4, 2, 2, 1};
-constexpr int kShapeSlotOff[kNumShapes + 1] = {0, 32, 64, 80, 88, 96, 100, 102, 104, 105};
-constexpr size_t merge_list_off(int si, uint32_t ntiles) {
-  return kMergeWorkHead + (size_t)ntiles * kShapeSlotOff[si];
-}
-constexpr size_t merge_work_words(uint32_t ntiles) { return merge_list_off(kNumShapes, ntiles); }
+// merge stage (jxg_merge.hip: eval and the entries; jxg_merge_write.hip: the rest);
+// the nine merged shapes and their table / list offsets: jxg_shapes.h
 struct MergeArgs {
   const float* xyb;    // [tiles][3][64][64] XYB tiles (front kernel)
   uint32_t bxs, bys, tiles_x, ntiles;  // ntiles: entries of tile_list (or all tiles)
@@ -350,13 +337,19 @@ void launch_lf_code(const LfArgs* a, uint32_t k, uint32_t nchunks, hipStream_t s
 hipError_t set_cluster_table(const uint8_t* tab, hipStream_t s);
 hipError_t set_merge_constants(const float* llf_p /*[4][8]*/, const float* llf_ib /*[4][8][8]*/,
                          hipStream_t s);
+// merge stage of k frames of one size: eval, resolve, write (jxg_merge.hip)
 hipError_t launch_merge(const MergeArgs* a, uint32_t k, hipStream_t s);
 // forced encode (one frame): the lists from a.force, then merge_write
 hipError_t launch_force_merge(const MergeArgs& a, hipStream_t s);
+// the stage's other unit, launched by the two above: the list producers and
+// the dense write passes (jxg_merge_write.hip)
+void launch_merge_resolve(const Batch<MergeArgs>& b, uint32_t k, hipStream_t s);
+void launch_force_list(const MergeArgs& a, hipStream_t s);
+void launch_merge_write(const Batch<MergeArgs>& b, uint32_t k, hipStream_t s);
 void dump_merge_profile();  // JXG_MERGE_PROFILE experiment builds; no-op otherwise
 void dump_front_profile();  // JXG_FRONT_PROFILE experiment builds; no-op otherwise
 void dump_hist_profile();   // (the same builds: ac_hist's phase clock)
-void launch_vb_list(const VbArgs* a, uint32_t k, uint32_t nlf, hipStream_t s);
+void launch_vb_list(const VbArgs* a, uint32_t k, uint32_t nlf, hipStream_t s);  // jxg_vb_list.hip
 // decode-side quality (jxg_metrics.hip): orig / comp RGB8 interleaved rows
 struct MetricArgs {
   const uint8_t* orig;

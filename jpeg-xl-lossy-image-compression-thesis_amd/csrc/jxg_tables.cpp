@@ -210,13 +210,11 @@ MergeTables build_merge_tables() {
   // 16-byte column chunks [kx][ky] touched 64 cache lines per load and cost
   // merge_eval ~13 % in address processing)
   {
-    static const int kShapeDims[kNumShapes][3] = {{2, 1, 0}, {1, 2, 0}, {2, 2, 1}, {4, 2, 2}, {2, 4, 2},
-                                                 {4, 4, 3}, {8, 4, 4}, {4, 8, 4}, {8, 8, 5}};
     const int stot = kShapeOff[kNumShapes];
     std::vector<float> swk((size_t)3 * stot), ssdk((size_t)3 * stot), siwy(stot);
     std::vector<uint16_t> snat(stot);
     for (int sh = 0; sh < kNumShapes; sh++) {
-      const int cy = kShapeDims[sh][0], cx = kShapeDims[sh][1], k = kShapeDims[sh][2];
+      const int cy = 1 << kShapes[sh].lcy, cx = 1 << kShapes[sh].lcx, k = shape_kind(sh);
       const int R = 8 * cy, C = 8 * cx;
       for (int ky = 0; ky < R; ky++)
         for (int kx = 0; kx < C; kx++) {

@@ -4,8 +4,8 @@
 // exact-integer summary of the 8x8 scan's decisions.
 //
 // trace_planes_kernel   one thread per block: for each of the nine merged
-//   shapes (kTraceShapes == jxg_merge.hip kShapes) and the six big ones
-//   (== jxg_bigvb.hip kBig) the estimate of the candidate varblock whose first
+//   shapes (kShapes, jxg_shapes.h) and the six big ones (level x {tall, wide,
+//   full}, the order of jxg_bigvb.hip kBig) the estimate of the candidate varblock whose first
 //   block this is, read from merge_eval's mcost[tile][9][32] / big_eval's
 //   cost[group][30]; NaN wherever no candidate was evaluated.  merge_eval and
 //   big_eval leave the entries of unsearched levels and of regions that do not
@@ -24,13 +24,6 @@
 namespace jxg {
 
 namespace {
-
-struct TraceShape {
-  int lcy, lcx;  // blocks down / across (log2)
-};
-// (== kShapes of jxg_merge.hip: ids 6, 7, 4, 10, 11, 5, 19, 20, 18)
-constexpr TraceShape kTraceShapes[kNumShapes] = {{1, 0}, {0, 1}, {1, 1}, {2, 1}, {1, 2},
-                                                 {2, 2}, {3, 2}, {2, 3}, {3, 3}};
 
 constexpr int kTraceThreads = 256;
 
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(kTraceThreads) void trace_planes_kernel(TraceArgs a
     const int maxl = a.max_s >= 8 ? 3 : (a.max_s >= 4 ? 2 : 1);
 #pragma unroll
     for (int si = 0; si < kNumShapes; si++) {
-      const int lcy = kTraceShapes[si].lcy, lcx = kTraceShapes[si].lcx, ls = max(lcy, lcx);
+      const int lcy = kShapes[si].lcy, lcx = kShapes[si].lcx, ls = max(lcy, lcx);
       // searched at this effort; this is a first block on the shape's grid;
       // its level region lies inside the frame's blocks (setup_varblocks)
       const bool first = (lbx & ((1 << lcx) - 1)) == 0 && (lby & ((1 << lcy) - 1)) == 0;

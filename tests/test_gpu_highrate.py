@@ -1,7 +1,7 @@
 """Distances below 0.1 on the GPU (tests/highrate_cases.py: the frames, the
 table and what each case reaches; tests/test_highrate_cases.py asserts that
 from the oracle).  Down there the three quantizers (jxg_front.hip quant_lane /
-quant_xb, jxg_merge.hip quant_pass, jxg_bigvb.hip vb_quant) clamp at +-32767
+quant_xb, jxg_merge_kernel.h quant_pass, jxg_bigvb.hip vb_quant) clamp at +-32767
 and pack it as int16, the rate runs at 15-bit magnitudes, the token record
 (tok 63, nbits 13, 13 extra bits) is at the edge of every field in both rANS
 kernels, the prefix writer, the histogram / clustering, the rate kernel and the

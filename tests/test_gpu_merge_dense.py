@@ -1,5 +1,5 @@
 """merge_write's dense passes: a pass holds up to NV(shape) chosen varblocks
-of one shape, taken from any tiles (jxg_merge.hip).  Every case compares the
+of one shape, taken from any tiles (jxg_merge_write.hip).  Every case compares the
 GPU encode with the oracle -- codestream bytes and the acs / qf / dc maps --
 and first asserts on the oracle's acs that the frame fills the passes the way
 the case is about: full passes, partly filled last passes, lists shorter than

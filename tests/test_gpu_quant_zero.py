@@ -1,4 +1,4 @@
-"""The quantizers' wave-uniform zero path (jxg_merge.hip quant_pass, jxg_front.hip
+"""The quantizers' wave-uniform zero path (jxg_merge_kernel.h quant_pass, jxg_front.hip
 quant_xb): where every active lane of a wave quantizes its coefficients to 0, the
 rounding and rate arithmetic is skipped.  The frames here put the votes in every
 state -- all zero in every channel (flat), one lane non-zero in one wave (a

@@ -2,8 +2,8 @@
 item 8): round 3's outlined merge_write build faulted; one hypothesis was an
 out-of-range S.co / S.qsum / S.llf index that the DS instructions tolerate and
 a generic (flat) access does not.  This restates the index math of
-csrc/jxg_merge.hip (Pass, row_pass, col_pass, quant_pass, write_entry) in
-Python and enumerates every thread, item and loop index of every shape, with
+csrc/jxg_merge_kernel.h (Pass, col_pass, quant_pass) and
+csrc/jxg_merge_write.hip (row_pass, write_pass) in Python and enumerates every thread, item and loop index of every shape, with
 every varblock valid (the largest index set), checking each LDS index against
 its array.  CPU only: the kernels' own arithmetic is the same integer math."""
 import itertools

@@ -1,5 +1,5 @@
 """The float identities the round-5 quantization code relies on
-(csrc/jxg_front.hip quant_lane / quant_xb, csrc/jxg_merge.hip quant_pass),
+(csrc/jxg_front.hip quant_lane / quant_xb, csrc/jxg_merge_kernel.h quant_pass),
 checked in IEEE single precision on the CPU (numpy float32 arithmetic rounds
 to nearest like the GPU's VALU; no contraction is involved):
 
