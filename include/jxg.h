@@ -195,8 +195,9 @@ jxg_status jxg_encode_forced_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32
  * Effort < 5 has no search: JXG_ERR_UNSUPPORTED, nothing touched (*out =
  * {NULL, 0}; jxg_reconstruct_rgb8 still serves the encode before).
  * JXG_ERR_INVALID_ARG wherever jxg_encode_rgb8 returns it and while streamed
- * frames are pending.  There is no batch, streaming, sweep, sharded or forced
- * form.
+ * frames are pending.  There is no batch, streaming, sharded or forced form;
+ * a sweep carries the summary, not the planes, per point
+ * (jxg_set_sweep_trace below).
  *
  * jxg_search_trace copies the estimates out; either pointer may be NULL.  It
  * is valid when the context's last use of its buffers was a traced encode,
@@ -882,6 +883,30 @@ jxg_status jxg_ab_report_rgb8_device(jxg_ctx* a, jxg_ctx* b, const void* d_orig,
  * not that sweep's, or while streamed frames are pending. */
 jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n);
 jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n);
+/* Search-trace summaries in a sweep.  With the switch on
+ * (default 0; JXG_ERR_INVALID_ARG for a null ctx and while streamed frames are
+ * pending) every sweep -- quality 0 included, nothing here needs decoded pixels
+ * -- runs each accepted point whose effort is >= 5 as a traced job on its lane
+ * and reduces its jxg_trace_summary there.  A point of effort < 5 has no
+ * search: it is encoded exactly as with the switch off and its summary is
+ * zero-filled (blocks == 0 marks it), which is no error at point or call
+ * level; a refused point's summary is zero-filled too.  The planes
+ * (jxg_trace_maps) are not kept.  Codestreams are byte-identical to the same
+ * sweep with the switch off, and so to jxg_encode_rgb8 on a context created
+ * with the point; q[], MS-SSIM results, strategy, rate and A/B reports are
+ * unchanged, and with the switch off a sweep launches and allocates what it
+ * did before.  The trace planes, 115 bytes a block (59.6 MB at 7680 x 4320),
+ * are allocated per lane by the first traced sweep that reaches the slot and
+ * released with the lane.
+ * jxg_sweep_trace copies the last sweep's summaries out in point order, each
+ * bit-equal to the summary jxg_search_trace gives after jxg_encode_traced_rgb8
+ * of the image on a context created with that point; JXG_ERR_INVALID_ARG,
+ * nothing written, for a null ctx or out, when the last sweep computed none
+ * (the switch was off), when n is not that sweep's, or while streamed frames
+ * are pending.  jxg_search_trace after a sweep stays JXG_ERR_INVALID_ARG, as
+ * after any sweep. */
+jxg_status jxg_set_sweep_trace(jxg_ctx* ctx, int on);
+jxg_status jxg_sweep_trace(jxg_ctx* ctx, jxg_trace_summary* out, uint32_t n);
 
 /* Prepares the context for frames of xsize x ysize before the first one
  * arrives: encodes one synthetic frame of that size (device-generated, result

@@ -570,6 +570,12 @@ jxg_status jxg_set_sweep_ab(jxg_ctx* ctx, const int32_t* base, uint32_t n) {
 jxg_status jxg_sweep_ab(jxg_ctx* ctx, jxg_ab_report* out, uint32_t n) {
   return sweep_results(ctx, kRiderAb, out, n);
 }
+jxg_status jxg_set_sweep_trace(jxg_ctx* ctx, int on) {
+  return sweep_switch(ctx, kRiderTrace, on != 0);
+}
+jxg_status jxg_sweep_trace(jxg_ctx* ctx, jxg_trace_summary* out, uint32_t n) {
+  return sweep_results(ctx, kRiderTrace, out, n);
+}
 
 jxg_status jxg_strategy_report_rgb8(jxg_ctx* ctx, const uint8_t* orig, size_t orig_stride,
                                     jxg_strategy_report* out, uint32_t* block_sse) {

@@ -28,6 +28,11 @@
 // `--jxg_trace=FILE.csv` (not a cjxl option) makes the encode a traced one
 // (jxg_encode_traced_rgb8: the same codestream) and appends the summary of its
 // search trace, one row per scan index.  Not with --sweep or --jxg_strategy_in.
+//
+// `--jxg_sweep_trace=FILE.csv` (not a cjxl option; only with --sweep) appends
+// the same rows for every point of the sweep whose effort is >= 5, traced on its
+// lane (jxg_set_sweep_trace: the same codestreams); a point without a search
+// writes no rows and one line on stderr.
 #include <zlib.h>
 
 #include <cctype>
@@ -384,7 +389,7 @@ bool read_sweep_list(const char* path, std::vector<SweepLine>& out) {
 int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* outdir,
               const std::vector<SweepLine>& list, const std::vector<uint8_t>& rgb, uint32_t w,
               uint32_t h, const char* report_path, const char* rates_path, const char* ab_path,
-              uint32_t ab_base) {
+              uint32_t ab_base, const char* sweep_trace_path) {
   // with --jxg_ab the list's points with the base proposals go in front: point
   // m + i is the command line's own and is compared with point i
   const size_t m = list.size(), o = ab_path ? m : 0, n = m + o;
@@ -408,6 +413,7 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
   std::vector<jxg_strategy_report> reps(report_path ? n : 0);
   std::vector<struct jxg_rate_report> rates(rates_path ? n : 0);
   std::vector<jxg_ab_report> abs(ab_path ? n : 0);
+  std::vector<jxg_trace_summary> traces(sweep_trace_path ? n : 0);
   const std::string orig_name = std::filesystem::path(input).filename().string();
   const uint32_t un = (uint32_t)n;
   struct Rider {
@@ -425,6 +431,15 @@ int run_sweep(jxg_ctx* ctx, const jxg_params& p, const char* input, const char* 
       {ab_path, "A/B reports", [&] { return jxg_set_sweep_ab(ctx, base.data(), un); },
        [&] { return jxg_sweep_ab(ctx, abs.data(), un); },
        [&](const RowKey& k, size_t i) { return write_ab_rows(ab_path, k, abs[i], w, h); }},
+      // (a point without a search, effort < 5, has the zero summary: no rows)
+      {sweep_trace_path, "traces", [&] { return jxg_set_sweep_trace(ctx, 1); },
+       [&] { return jxg_sweep_trace(ctx, traces.data(), un); },
+       [&](const RowKey& k, size_t i) {
+         if (traces[i].blocks) return write_trace_rows(sweep_trace_path, k, traces[i]);
+         std::fprintf(stderr, "distance %s effort %d: no search to trace, no rows\n",
+                      rust_f64(k.distance).c_str(), k.effort);
+         return true;
+       }},
   };
   for (const Rider& r : riders)
     if (r.path && r.set() != JXG_OK) return 1;
@@ -542,7 +557,8 @@ int main(int argc, char** argv) {
                  "[--jxg_ab=FILE.csv [--jxg_ab_base=none|P|F|PF]] "
                  "[--jxg_strategy_in=MAP.pgm [--jxg_qf_in=MAP.pgm]] "
                  "[--jxg_strategy_out=MAP.pgm] [--jxg_qf_out=MAP.pgm] [--jxg_trace=FILE.csv]\n"
-                 "       %s INPUT OUTDIR --sweep=LIST [the same flags, no maps]   "
+                 "       %s INPUT OUTDIR --sweep=LIST [the same flags, no maps; "
+                 "--jxg_sweep_trace=FILE.csv in place of --jxg_trace]   "
                  "(LIST: `distance effort` lines)\n"
                  "defaults: cjxl's (ANS, --gaborish=1, --epf=-1, masking AQ)\n",
                  argv[0], argv[0]);
@@ -577,6 +593,10 @@ int main(int argc, char** argv) {
   // (jxg_encode_traced_rgb8, the same codestream) and its search trace's summary
   // is appended, one row per scan index; not with --sweep or --jxg_strategy_in
   const char* trace_path = nullptr;
+  // --jxg_sweep_trace=FILE.csv (not a cjxl option), only with --sweep: every
+  // point of effort >= 5 runs traced on its lane (jxg_set_sweep_trace, the same
+  // codestreams) and its summary is appended as --jxg_trace writes it
+  const char* sweep_trace_path = nullptr;
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     if (!std::strncmp(a, "--distance=", 11) || !std::strncmp(a, "-d=", 3))
@@ -639,6 +659,8 @@ int main(int argc, char** argv) {
       qf_out = a + 13;
     else if (!std::strncmp(a, "--jxg_trace=", 12))
       trace_path = a + 12;
+    else if (!std::strncmp(a, "--jxg_sweep_trace=", 18))
+      sweep_trace_path = a + 18;
     else {
       std::fprintf(stderr, "unknown argument: %s\n", a);
       return 1;
@@ -655,6 +677,10 @@ int main(int argc, char** argv) {
   if (trace_path && (sweep_path || acs_in)) {
     std::fprintf(stderr, "--jxg_trace: not with %s (a traced encode is one search encode)\n",
                  sweep_path ? "--sweep" : "--jxg_strategy_in");
+    return 1;
+  }
+  if (sweep_trace_path && !sweep_path) {
+    std::fprintf(stderr, "--jxg_sweep_trace: only with --sweep (one encode: --jxg_trace)\n");
     return 1;
   }
   if (qf_in && !acs_in) {
@@ -740,7 +766,7 @@ int main(int argc, char** argv) {
   }
   if (sweep_path) {
     const int rc = run_sweep(ctx, p, argv[1], argv[2], sweep_list, rgb, w, h, report_path,
-                             rates_path, ab_path, ab_base);
+                             rates_path, ab_path, ab_base, sweep_trace_path);
     std::fflush(nullptr);
     std::_Exit(rc);  // (as below: no exit-time teardown)
   }

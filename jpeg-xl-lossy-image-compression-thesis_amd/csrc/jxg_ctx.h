@@ -110,7 +110,7 @@ enum EncEvent : int {
 using RateReport = struct ::jxg_rate_report;
 // a sweep's riders: the optional per-point results of jxg_sweep_rgb8, each with
 // a switch (jxg_set_sweep_*), a getter (jxg_sweep_*) and a slot in Ctx::Sweep
-enum Rider { kRiderMsssim, kRiderReport, kRiderRates, kRiderAb, kRiders };
+enum Rider { kRiderMsssim, kRiderReport, kRiderRates, kRiderAb, kRiderTrace, kRiders };
 // what differs between them besides their enqueue functions (kRiderRules,
 // jxg_sweep.cpp): a rider rides on sweeps of quality >= min_quality; a point
 // stages `words` pinned 8-byte words, which rider_convert turns into its public
@@ -235,7 +235,9 @@ struct Ctx : EncArenas {
   // allocated by the first traced encode: the f32 planes [cand8_raw 6 | cand8 6
   // | merged 9 | big 6 | chosen 1][nb], the u8 planes [scan8 | front8 | qf8][nb]
   // and the summary words.  have: the last one-at-a-time encode was a traced
-  // one of a w x h frame (valid as long as rc.ok)
+  // one of a w x h frame (valid as long as rc.ok).  A sweep's lane with
+  // jxg_set_sweep_trace uses the same buffers, 115 bytes a block, allocated by
+  // the first traced point that lands on the slot and released with it
   struct Trace {
     DevBuf<float> f;
     DevBuf<uint8_t> b;
@@ -611,6 +613,11 @@ void trace_front_args(Ctx* c, FrontArgs& fa);
 jxg_status trace_copy_qf(Ctx* c, const Job& J);
 // on the job's stream behind the merge stage: the planes and the summary
 jxg_status trace_enqueue(Ctx* c, const Job& J);
+// a pinned result of a sweep's point: the summary's u32 words
+constexpr size_t kTraceWords = kTraceSummaryWords / 2;
+// a sweep's traced point on its lane, behind trace_enqueue: the summary's copy
+// to rq.h[kRiderTrace]
+jxg_status sweep_trace_enqueue(Ctx* lane, const SweepReq& rq);
 jxg_status search_trace(Ctx* c, jxg_trace_maps* maps, jxg_trace_summary* summary);
 
 // ---- jxg_decode_dev.cpp ----

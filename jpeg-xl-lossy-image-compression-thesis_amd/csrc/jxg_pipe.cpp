@@ -56,6 +56,7 @@ struct PipeFrame {
   std::future<jxg_status> codes;  // valid while a helper builds the codes
   bool sweep = false;  // a sweep's frame: its point (the lane's parameters) and quality request
   SweepReq rq;
+  bool traced = false;  // a sweep's frame that carries the trace slice: a traced job, alone in its batch
 };
 // frames launched together on one lane; the last of their codes launches the
 // batch's emission
@@ -221,14 +222,23 @@ static jxg_status pipe_launch_open(Ctx* c) {
   std::vector<Ctx*> cs;
   std::vector<Job*> js;
   for (PipeFrame* fr : B->frames) {
-    const jxg_status st = enc_prepare(fr->lane, fr->J, fr->src, fr->w, fr->h, fr->stride,
-                                      fr->rank, fr->world);
+    jxg_status st = JXG_OK;
+    // a sweep's traced point (pipe_submit: alone in its batch): the slot's trace
+    // buffers, before the argument blocks point into them.  The Job is the
+    // frame's own, so every other frame of the slot is a plain one
+    if (fr->traced) {
+      if ((st = trace_alloc(fr->lane, fr->w, fr->h))) return st;
+      fr->J.trace = true;
+    }
+    st = enc_prepare(fr->lane, fr->J, fr->src, fr->w, fr->h, fr->stride, fr->rank, fr->world);
     if (st) return st;
     cs.push_back(fr->lane);
     js.push_back(&fr->J);
   }
   jxg_status st = launch_stats(cs.data(), js.data(), k);
   if (st) return st;
+  for (PipeFrame* fr : B->frames)  // the summary, behind trace_enqueue on the lane's stream
+    if (fr->traced && (st = sweep_trace_enqueue(fr->lane, fr->rq))) return st;
   B->left.store((int)k);
   for (PipeFrame* fr : B->frames) fr->phase = 1;
   try {
@@ -363,9 +373,13 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
     return a.distance == b.distance && a.effort == b.effort && a.proposals == b.proposals &&
            a.flags == b.flags;
   };
+  // a sweep's point with the trace slice and a search (effort >= 5) is a traced
+  // job, which goes alone (batch_ok): the open batch goes out before it and it
+  // is launched as soon as it is in
+  const bool traced = rq && rq->h[kRiderTrace] && prm.effort >= 5;
   if (p.open && (p.open->w != w || p.open->h != h || p.open->rank != rank ||
                  p.open->world != world || !same_point(p.open->params, prm) ||
-                 p.open->frames.size() >= shape.batch))
+                 p.open->frames.size() >= shape.batch || traced))
     if ((st = pipe_launch_open(c))) return fail(st);
   if (!p.open) {
     // a free lane (no frame in flight or ready on it): complete the oldest
@@ -411,6 +425,7 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
   if (rq) {
     fr->sweep = true;
     fr->rq = *rq;
+    fr->traced = traced;
   }
   S->params = prm;
   if (!on_device) {
@@ -430,7 +445,7 @@ jxg_status pipe_submit(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, u
   B.frames.push_back(fr.get());
   p.inflight.push_back(std::move(fr));
   p.submitted++;
-  if (B.frames.size() >= shape.batch && (st = pipe_launch_open(c))) return fail(st);
+  if ((B.frames.size() >= shape.batch || traced) && (st = pipe_launch_open(c))) return fail(st);
   // frames one per lane: this thread waits for the codes of frame j - lag
   // (their emission launched), which paces the launches by the codes and
   // rANS chains instead of filling every lane with transform work at once

@@ -25,6 +25,12 @@
 // event; a comparing point's lane waits for it and reduces the snapshot against
 // its own triple (jxg_ab.hip); the table is one more pinned
 // result ahead of the metrics' end event.
+// With jxg_set_sweep_trace every point of effort >= 5 runs as a traced job on
+// its lane (jxg_trace.cpp): the trace instantiations of the
+// front kernel and of the 128 / 256 px levels, then the planes and the summary
+// behind the merge stage, whose 104 words are copied to pinned memory right
+// there -- long before the frame's completion event.  The planes stay in the
+// lane's Ctx::Trace (115 bytes a block, kept with the lane) and are not fetched.
 #include <cmath>
 #include <cstring>
 
@@ -105,11 +111,13 @@ jxg_status sweep_quality_enqueue(Ctx* S, const SweepReq& rq, const uint8_t* d_or
 // the riders' rules (jxg_ctx.h), in the order of enum Rider
 static_assert(sizeof(jxg_strategy_report) == kReportCells * 8, "copied as it is staged");
 static_assert(sizeof(jxg_ab_report) == kAbWords * 8, "copied as it is staged");
+static_assert(sizeof(jxg_trace_summary) == kTraceWords * 8, "copied as it is staged");
 const RiderRule kRiderRules[kRiders] = {
     {2, 2 * kMsScales, sizeof(jxg_msssim)},
     {1, kReportCells, sizeof(jxg_strategy_report)},
     {0, kRateWords, sizeof(RateReport)},
     {1, kAbWords, sizeof(jxg_ab_report)},
+    {0, kTraceWords, sizeof(jxg_trace_summary)},
 };
 // a point's staged words to its public struct (words null: MS-SSIM under kMsMinEdge)
 static void rider_convert(int r, uint32_t w, uint32_t h, const uint64_t* words, void* out) {
@@ -255,6 +263,13 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
     auto slice = [&](int r, uint32_t k) {
       return sw.rider[r].h.p + (size_t)k * kRiderRules[r].words;
     };
+    // valid point k has a result of rider r: A/B only where it compares, the
+    // trace only where there is a search (the others' structs stay zero)
+    auto has = [&](int r, uint32_t k) {
+      if (r == kRiderAb) return ab_of[k] >= 0;
+      if (r == kRiderTrace) return points[valid[k]].effort >= 5;
+      return true;
+    };
     // point valid[got]'s codestream (its completion event covers the quality
     // and riders' results) and its share of the timings
     auto take = [&]() {
@@ -262,8 +277,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
       if ((e = pipe_receive(c, &outs[i]))) return;
       sw.stats.ms_encode += c->stats.ms_total;
       for (int r = 0; r < kRiders; r++) {
-        // (A/B: only a comparing point has a table; the others' reports stay zero)
-        if (!rides[r] || (r == kRiderAb && ab_of[k] < 0)) continue;
+        if (!rides[r] || !has(r, k)) continue;
         rider_convert(r, w, h, runs[r] ? slice(r, k) : nullptr,
                       sw.rider[r].out.data() + (size_t)i * kRiderRules[r].out_bytes);
       }
@@ -294,7 +308,7 @@ jxg_status sweep(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_
         rq.ev = sw.ev.data() + 3 * (size_t)k;
       }
       for (int r = 0; r < kRiders; r++)
-        if (runs[r] && (r != kRiderAb || ab_of[k] >= 0)) rq.h[r] = slice(r, k);
+        if (runs[r] && has(r, k)) rq.h[r] = slice(r, k);
       if (ms_run) {
         rq.pyr_o = sw.pyr_o.p;
         rq.ev_pyr = sw.ev_pyr;

@@ -64,6 +64,15 @@ jxg_status trace_enqueue(Ctx* c, const Job& J) {
   return JXG_OK;
 }
 
+// (no host wait: the frame's completion event covers the copy, and the lane's
+// next traced frame clears tr.sum behind it in stream order)
+jxg_status sweep_trace_enqueue(Ctx* lane, const SweepReq& rq) {
+  static_assert(kTraceWords * 8 == sizeof(jxg_trace_summary), "staged as 8-byte words");
+  JXG_HIP(hipMemcpyAsync(rq.h[kRiderTrace], lane->tr.sum.p, sizeof(jxg_trace_summary),
+                         hipMemcpyDeviceToHost, lane->stream));
+  return JXG_OK;
+}
+
 jxg_status search_trace(Ctx* c, jxg_trace_maps* maps, jxg_trace_summary* summary) {
   if (!c->rc.ok || !c->tr.have || c->tr.w != c->rc.w || c->tr.h != c->rc.h)
     return JXG_ERR_INVALID_ARG;

@@ -239,6 +239,7 @@ EXPORTS = ("jxg_status_str", "jxg_create", "jxg_destroy", "jxg_encode_rgb8",
            "jxg_set_sweep_ab", "jxg_sweep_ab",
            "jxg_check_strategy_map", "jxg_encode_forced_rgb8", "jxg_encode_forced_rgb8_device",
            "jxg_encode_traced_rgb8", "jxg_encode_traced_rgb8_device", "jxg_search_trace",
+           "jxg_set_sweep_trace", "jxg_sweep_trace",
 )
 
 _lib = None
@@ -364,6 +365,8 @@ def load():
     lib.jxg_encode_traced_rgb8_device.argtypes = traced_args
     lib.jxg_search_trace.argtypes = [vp, ctypes.POINTER(_TraceMaps),
                                      ctypes.POINTER(_TraceSummary)]
+    lib.jxg_set_sweep_trace.argtypes = [vp, ctypes.c_int]
+    lib.jxg_sweep_trace.argtypes = [vp, ctypes.POINTER(_TraceSummary), ctypes.c_uint32]
     _lib = lib
     return lib
 
@@ -804,10 +807,12 @@ class Encoder:
          lambda r: {"ab": r.as_dict()}),
         ("rates", "jxg_set_sweep_rates", (0,), "jxg_sweep_rates", _RateReport,
          lambda r: {"rates": r.as_dict()}),
+        ("trace", "jxg_set_sweep_trace", (0,), "jxg_sweep_trace", _TraceSummary,
+         lambda r: {"trace": r.as_dict()}),
     )
 
     def _sweep_call(self, fn, ptr, w, h, stride, points, quality, strict, strategies=False,
-                    rates=False, ab=None):
+                    rates=False, ab=None, trace=False):
         if quality not in self._QUALITY:
             raise ValueError("quality: 'msssim', 'ssim', 'psnr' or None")
         level = self._QUALITY[quality]
@@ -829,6 +834,7 @@ class Encoder:
         on = {"msssim": (1,) if quality == "msssim" else None,
               "strategies": (1,) if strategies else None,
               "rates": (1,) if rates else None,
+              "trace": (1,) if trace else None,
               "ab": ((ctypes.c_int32 * n)(*ab), n) if ab is not None else None}
         riders = [r for r in self._RIDERS if on[r[0]] is not None]
         c_pts = (_SweepPoint * n)(*pts)
@@ -862,14 +868,15 @@ class Encoder:
             if level:
                 q = {k: getattr(qs[i], k) for k in ("sse", "samples", "mse", "psnr", "ssim")}
             for name, _, _, _, _, put in riders:
-                # (quality None: rates alone, the others were refused above)
+                # (quality None: rates and trace alone, the others were refused above)
                 if name in got and (name != "ab" or ab[i] >= 0):
                     q = dict(q or {}, **put(got[name][i]))
             res.append((self._take(outs[i]), q))
         return res
 
     def sweep(self, rgb: np.ndarray, points, quality="ssim", strict: bool = True,
-              strategies: bool = False, rates: bool = False, ab=None) -> list:
+              strategies: bool = False, rates: bool = False, ab=None,
+              trace: bool = False) -> list:
         """One host (H, W, 3) uint8 image encoded at every point of ``points``
         in one call (jxg_sweep_rgb8): the image is uploaded once and the points
         run through the streaming pipeline's lanes of this context, whose own
@@ -895,24 +902,30 @@ class Encoder:
         with a base >= 0 gains ``"ab"``, the :func:`ab_report` of the base point
         (side A) and this point (side B), reduced on its lane against a snapshot
         of the base point's maps (jxg_set_sweep_ab; all zero where the base
-        point was refused).  Afterwards :meth:`reconstruct`
-        raises until the next :meth:`encode`."""
+        point was refused).  ``trace=True`` (allowed with ``quality=None``):
+        each point's dict gains ``"trace"``, the summary of
+        :meth:`search_trace` after :meth:`encode_traced` with that point,
+        reduced on its lane (jxg_set_sweep_trace); a point of effort < 5 has no
+        search and gets the all-zero summary (``blocks == 0``); the planes are
+        not kept.  Afterwards :meth:`reconstruct` and :meth:`search_trace`
+        raise until the next :meth:`encode` / :meth:`encode_traced`."""
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("expected (H, W, 3) uint8")
         h, w = rgb.shape[:2]
         return self._sweep_call(load().jxg_sweep_rgb8, rgb.ctypes.data, w, h, w * 3, points,
-                                quality, strict, strategies, rates, ab)
+                                quality, strict, strategies, rates, ab, trace)
 
     def sweep_device(self, ptr: int, width: int, height: int, points, quality="ssim",
                      strict: bool = True, row_stride: int | None = None,
-                     strategies: bool = False, rates: bool = False, ab=None) -> list:
+                     strategies: bool = False, rates: bool = False, ab=None,
+                     trace: bool = False) -> list:
         """:meth:`sweep` of a device-resident RGB8 image (rows of ``row_stride``
         bytes, default 3 * width), which must stay unchanged until the call
         returns (jxg_sweep_rgb8_device)."""
         return self._sweep_call(load().jxg_sweep_rgb8_device, ctypes.c_void_p(ptr), width, height,
                                 row_stride or width * 3, points, quality, strict, strategies,
-                                rates, ab)
+                                rates, ab, trace)
 
     def sweep_timings(self) -> dict:
         """The last :meth:`sweep` (jxg_sweep_timings): points encoded, lanes,

@@ -41,7 +41,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from . import comp_image_name, rust_f32, rust_f64
+from . import STRATEGY_NAMES, TRACE_SCAN_IDS, comp_image_name, rust_f32, rust_f64
 
 RESULT_HEADER = [
     "Original Image Name", "Compressed Image Name", "Distance", "Effort",
@@ -396,6 +396,77 @@ def read_ab_stats(file_name: str):
     return _read_stats(AbStat, file_name)
 
 
+TRACE_HEADER = [
+    "Original Image Name", "Compressed Image Name", "Distance", "Effort", "Scan Index", "Strategy",
+    "Name", "Blocks", "Max Px", "Scan Wins", "Raw DCT8", "Raw DCT4X4", "Raw DCT2X2", "Raw DCT4X8",
+    "Raw DCT8X4", "Raw IDENTITY", "Hook P", "Merged Over", "Margin 0", "Margin 1", "Margin 2",
+    "Margin 3", "Margin 4", "Margin 5", "Margin 6", "Margin 7", "Margin Skipped",
+]
+
+
+@dataclass
+class TraceStat(_StatRow):
+    """One scan index s of one encode's search-trace summary
+    (Encoder.search_trace / a sweep point's ``"trace"``): the
+    blocks the 8x8 scan gave to s (``scan_wins``, the column sum of ``flip``), of
+    them by the winner of the scan without hook F (``raw_*`` = ``flip[r][s]``),
+    the hook-P overrides with target s, the blocks merged over, the margin
+    histogram and the blocks it skipped; beside them the point's ``blocks`` and
+    ``max_px``, the same on every row of it.  Every value is an integer."""
+    orig_image_name: str
+    comp_image_name: str
+    distance: float  # f32
+    effort: int
+    scan_index: int
+    strategy: int
+    name: str
+    blocks: int
+    max_px: int
+    scan_wins: int
+    raw_dct8: int
+    raw_dct4x4: int
+    raw_dct2x2: int
+    raw_dct4x8: int
+    raw_dct8x4: int
+    raw_identity: int
+    hook_p: int
+    merged_over: int
+    margin_0: int
+    margin_1: int
+    margin_2: int
+    margin_3: int
+    margin_4: int
+    margin_5: int
+    margin_6: int
+    margin_7: int
+    margin_skipped: int
+
+
+def trace_stats(orig_name: str, comp_name: str, distance: float, effort: int, summary: dict):
+    """The six TraceStat rows of one summary (Encoder.search_trace / a sweep
+    point's ``"trace"``), one per scan index, with the values ``jxg_cjxl
+    --jxg_trace`` writes."""
+    flip = np.asarray(summary["flip"]).astype(np.int64).reshape(6, 6)
+    margin = np.asarray(summary["margin"]).astype(np.int64).reshape(6, 8)
+    rows = []
+    for s, sid in enumerate(TRACE_SCAN_IDS):
+        rows.append(TraceStat(
+            orig_name, comp_name, float(np.float32(distance)), int(effort), s, sid,
+            STRATEGY_NAMES[sid], int(summary["blocks"]), int(summary["max_px"]),
+            int(flip[:, s].sum()), *[int(flip[r, s]) for r in range(6)],
+            int(summary["hook_p"][s]), int(summary["merged_over"][s]),
+            *[int(margin[s, k]) for k in range(8)], int(summary["margin_skipped"][s])))
+    return rows
+
+
+def write_trace_stats(rows, trace_file: str) -> None:
+    _append_stats(rows, trace_file, TRACE_HEADER)
+
+
+def read_trace_stats(file_name: str):
+    return _read_stats(TraceStat, file_name)
+
+
 _DIFF_FIELDS = [f.name for f in fields(ComparisonResult)[4:]]
 
 
@@ -519,7 +590,7 @@ def encode_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_
 def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_size: int, points,
                       result_file: str | None = None, ssim: bool = True, ms_ssim: bool = False,
                       strategy_file: str | None = None, rate_file: str | None = None,
-                      ab_file: str | None = None, ab_base=None):
+                      ab_file: str | None = None, ab_base=None, trace_file: str | None = None):
     """The harness's per-image loop (benchmark.rs:637-677) in one call: the
     image is encoded at every point (dicts with ``distance`` / ``effort`` and
     optionally ``proposals`` / ``flags``) by ``encoder.sweep`` -- one upload,
@@ -538,7 +609,11 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     appended to that file.  ``ab_file`` with ``ab_base`` (one base index per
     point: -1, or the index of an earlier point): every point with a base is
     compared with it on its lane (``ab=ab_base``) and one AbStat row per
-    non-empty cell of that A/B report is appended to that file."""
+    non-empty cell of that A/B report is appended to that file.
+    ``trace_file``: every point of effort >= 5 runs traced on its lane
+    (``trace=True``, the same codestreams) and the six TraceStat rows of its
+    search-trace summary are appended to that file; a point without a search
+    (``blocks == 0``) writes none."""
     if (ab_file is None) != (ab_base is None):
         raise ValueError("ab_file and ab_base go together")
     if ms_ssim and not ssim:
@@ -550,6 +625,7 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
     points = list(points)
     res = encoder.sweep(o, points, quality=("msssim" if ms_ssim else "ssim") if ssim else "psnr",
                         strategies=strategy_file is not None, rates=rate_file is not None,
+                        trace=trace_file is not None,
                         **({} if ab_base is None else {"ab": list(ab_base)}))
     stem = os.path.splitext(orig_name)[0]
     raw = w * h * 3
@@ -572,4 +648,6 @@ def sweep_and_compare(encoder, orig_name: str, orig_rgb: np.ndarray, orig_file_s
         if ab_file is not None and ab_base[i] >= 0:
             write_ab_stats(ab_stats(orig_name, names[ab_base[i]], names[i], d, e, q["ab"], w, h),
                            ab_file)
+        if trace_file is not None and int(q["trace"]["blocks"]) != 0:
+            write_trace_stats(trace_stats(orig_name, names[i], d, e, q["trace"]), trace_file)
     return datas, records

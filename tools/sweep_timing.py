@@ -6,6 +6,7 @@ each doing encode + reconstruct_device + compare_device.
 
     python tools/sweep_timing.py [--reps 5] [--sizes 8k,768] [--queues N] [--cli]
     python tools/sweep_timing.py --strategies [--reps 5] [--sizes 8k,768] [--queues N]
+    python tools/sweep_timing.py --rates | --ab | --trace [the same options]
 
 Per frame size (the 8K synthetic frame and a 768 x 512 one), input (host /
 device) and quality level (0 none, 1 sse/psnr, 2 also ssim): warm contexts,
@@ -31,6 +32,12 @@ library without the switch only the switch-off rows are measured.
 with its base -- with jxg_set_sweep_ab off and on, alternating; then the added
 kernels alone by the events of a two-point sweep, and the wall time of
 ab_report_device after two encodes.  On a library without the switch only the
+switch-off rows are measured.
+--trace: the cost of the search-trace summaries: the grid's
+`sweep_device` at quality 0 and 2 with jxg_set_sweep_trace off and on,
+alternating; jxg_sweep_timings' ms_call (median, min..max) and the ms_encode of
+the median sweep, and the device memory the sweeping context holds without and
+with the lanes' trace planes.  On a library without the switch only the
 switch-off rows are measured."""
 import argparse
 import json
@@ -375,6 +382,68 @@ def ab(args):
         del d_img
 
 
+def trace(args):
+    import torch
+
+    import jxg
+    from jxg.synth import SEED_BASE, synth_rgb8_device
+
+    has_switch = hasattr(jxg.load(), "jxg_set_sweep_trace")
+    points = [dict(distance=d, effort=e, proposals=0, flags=jxg.FLAGS_CJXL_DEFAULTS)
+              for d in DISTANCES for e in EFFORTS]
+    for name in args.sizes.split(","):
+        w, h, seed = SIZES[name]
+        d_img = synth_rgb8_device(w, h, SEED_BASE + seed, 0)
+        torch.cuda.synchronize()
+        base = used_mib(torch)
+        sweeper = jxg.Encoder()
+
+        def sweep(level, on):
+            kw = {"trace": True} if on else {}
+            return sweeper.sweep_device(d_img.data_ptr(), w, h, points, quality=QUALITY[level],
+                                        **kw)
+
+        want = sweep(2, False)  # warm, all buffers
+        mem_off = used_mib(torch) - base
+        mem_on = mem_off
+        if has_switch:
+            got = sweep(2, True)
+            mem_on = used_mib(torch) - base
+            assert [g[0] for g in got] == [r[0] for r in want], "bytes differ with the switch on"
+            nb = ((w + 7) // 8) * ((h + 7) // 8)
+            for g, r in zip(got, want):
+                assert g[1]["trace"]["blocks"] == nb == int(g[1]["trace"]["flip"].sum())
+                assert g[1]["sse"] == r[1]["sse"]
+        modes = (False, True) if has_switch else (False,)
+        for level in (0, 2):
+            wall = {m: [] for m in modes}
+            split = {m: [] for m in modes}
+            for rep in range(args.reps + 1):
+                for m in modes:
+                    sweep(level, m)
+                    if rep:
+                        tm = sweeper.sweep_timings()
+                        wall[m].append(tm["ms_call"])
+                        split[m].append(tm)
+            res = {"frame": name, "trace": True, "library": os.path.relpath(jxg.LIB_PATH, ROOT),
+                   "quality": level, "points": len(points), "reps": args.reps,
+                   "queues": os.environ.get("GPU_MAX_HW_QUEUES", "default"),
+                   "lanes": sweeper.sweep_timings()["lanes"],
+                   "mib_switch_off": round(mem_off, 1), "mib_switch_on": round(mem_on, 1)}
+            for m in modes:
+                mid = sorted(range(len(wall[m])), key=lambda i: wall[m][i])[len(wall[m]) // 2]
+                key = "on" if m else "off"
+                res["ms_call_" + key] = spread(wall[m])
+                res["ms_encode_" + key] = round(split[m][mid]["ms_encode"], 3)
+            if has_switch:
+                res["ms_added_per_point"] = round(
+                    (statistics.median(wall[True]) - statistics.median(wall[False])) / len(points),
+                    4)
+            print(json.dumps(res), flush=True)
+        sweeper.close()
+        del d_img
+
+
 def cli(args):
     import jxg
     from jxg.synth import SEED_BASE, synth_rgb8
@@ -422,6 +491,7 @@ def main():
     ap.add_argument("--strategies", action="store_true")
     ap.add_argument("--rates", action="store_true")
     ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--trace", action="store_true")
     args = ap.parse_args()
     if not 0 <= args.queues <= 32:
         ap.error("--queues: at most 32 hardware queues (0: leave the environment's)")
@@ -437,6 +507,8 @@ def main():
         return rates(args)
     if args.ab:
         return ab(args)
+    if args.trace:
+        return trace(args)
     library(args)
 
 
