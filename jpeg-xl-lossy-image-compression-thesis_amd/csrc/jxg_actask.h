@@ -1,22 +1,22 @@
 // jxg_actask.h -- the task rules of a pass group's AC token stream: which
 // (slice, channel) task a thread of a band workgroup owns, how many tokens the
 // task holds without walking it, and where its records lie.  Shared by the
-// kernel that writes the records (ac_hist_kernel, jxg_ac.hip) and the one that
-// prices them (rate_kernel, jxg_rate.hip), so the two cannot
-// disagree about a record's owner.  Device code only.
+// kernel that writes the records (ac_hist_kernel, jxg_ac_hist.hip) and the one
+// that prices them (rate_kernel, jxg_rate.hip), so the two
+// cannot disagree about a record's owner; first_block also serves the A/B
+// report (jxg_ab.hip).  What a reader of a group's stream needs -- the record,
+// slot_group, kBands, rec_index -- is jxg_acrec.h; varblock_dims is
+// jxg_acmodel.h's.  Device code only.
 #pragma once
 #include "jxg_device.h"
 #include "jxg_kernels.h"
+#include "jxg_acrec.h"
 
 namespace jxg {
 
 struct GroupGeom {
   int bx0, by0, gw, gh;
 };
-// pass group of launch slot i: a shard's group list, or the range g0 + i
-__device__ __forceinline__ uint32_t slot_group(const uint32_t* glist, uint32_t g0, uint32_t i) {
-  return glist ? glist[i] : g0 + i;
-}
 __device__ __forceinline__ GroupGeom group_geom(const AcArgs& a, int g) {
   GroupGeom r;
   const int gx = g % (int)a.gxs, gy = g / (int)a.gxs;
@@ -45,28 +45,6 @@ __device__ __forceinline__ int32_t coef(const uint32_t* w, int k) {
 
 __device__ __forceinline__ int channel_of(int ci) { return ci == 0 ? 1 : (ci == 1 ? 0 : 2); }
 
-// covered blocks of a raw strategy id: log2 and blocks across / down
-__device__ __forceinline__ void varblock_dims(int type, int& lcb, int& cx, int& cy) {
-  switch (type) {
-    case 6: lcb = 1, cx = 1, cy = 2; break;   // 16x8
-    case 7: lcb = 1, cx = 2, cy = 1; break;   // 8x16
-    case 4: lcb = 2, cx = 2, cy = 2; break;   // 16x16
-    case 10: lcb = 3, cx = 2, cy = 4; break;  // 32x16
-    case 11: lcb = 3, cx = 4, cy = 2; break;  // 16x32
-    case 5: lcb = 4, cx = 4, cy = 4; break;   // 32x32
-    case 19: lcb = 5, cx = 4, cy = 8; break;  // 64x32
-    case 20: lcb = 5, cx = 8, cy = 4; break;  // 32x64
-    case 18: lcb = 6, cx = 8, cy = 8; break;  // 64x64
-    case 22: lcb = 7, cx = 8, cy = 16; break;   // 128x64 (effort >= 8)
-    case 23: lcb = 7, cx = 16, cy = 8; break;   // 64x128
-    case 21: lcb = 8, cx = 16, cy = 16; break;  // 128x128
-    case 25: lcb = 9, cx = 16, cy = 32; break;  // 256x128
-    case 26: lcb = 9, cx = 32, cy = 16; break;  // 128x256
-    case 24: lcb = 10, cx = 32, cy = 32; break; // 256x256
-    default: lcb = 0, cx = 1, cy = 1; break;  // 8x8 class
-  }
-}
-
 // The first block (ox, oy) of the varblock of strategy `type` that covers
 // frame block (bx, by).  The search places a varblock on its shape's own grid,
 // where masking the position finds it; a forced map (jxg_encode_forced_rgb8)
@@ -87,35 +65,6 @@ __device__ __forceinline__ void first_block(const uint8_t* acs, uint32_t bxs, in
         ox = x;
         oy = y;
       }
-}
-
-// ac_hist runs one 256-thread workgroup per BAND of a pass group: 8 block
-// rows (one row of 64x64 tiles) x 32 block columns.  Varblocks up to 64x64
-// lie inside one 64x64 tile, so a band holds whole
-// varblocks, and the group's token stream (varblocks by first block raster)
-// is the concatenation of its four bands' streams: band j writes its records
-// at [j * kBandTokStride, ...) of the group's record space and its token
-// count to bandtok[g][j]; the coders read the group's stream through
-// rec_index (a 4-entry prefix).  Four workgroups per group give small frames
-// (1080p: 40 groups) 160 workgroups instead of 40.  At effort >= 8 varblocks
-// of 128 / 256 px span bands: the kernel then runs with BR = 32 (one
-// 1024-thread workgroup = one band = the whole group; bands 1-3 empty).
-constexpr int kBands = 4;  // bandtok entries per group (the coders' view)
-static_assert(kBands * kBandTokStride == kGroupTokStride, "band record spaces tile the group's");
-
-// record space index of stream position k of a group whose band counts are bt[4]
-// (band j holds stream positions [c_j, c_j+1), c_j = bt[0] + ... + bt[j-1];
-// the bounds are cumulative, so k >= c_j holds for a prefix of the bands)
-__device__ __forceinline__ uint32_t rec_index(const uint32_t* bt, uint32_t k) {
-  uint32_t j = 0, lo = 0, cum = 0;
-#pragma unroll
-  for (int i = 0; i < kBands - 1; i++) {
-    cum += bt[i];
-    const bool past = k >= cum;
-    lo = past ? cum : lo;
-    j += past ? 1u : 0u;
-  }
-  return j * (uint32_t)kBandTokStride + (k - lo);
 }
 
 // One thread per block of the band: slice `sl` of the varblock whose first
@@ -232,17 +181,14 @@ __device__ __forceinline__ void fill_slices(const AcArgs& a, const GroupGeom& G,
   }
 }
 
-// workgroup (NT threads) exclusive scan; *total = sum of all values
+// workgroup (NT threads) exclusive scan; *total = sum of all values.  Holds a
+// barrier.  (jxg_entropy.hip block_excl_scan256 is the same scan in the form
+// lf_code_kernel was built with; DESIGN.md §3.13 "The AC coding stage's units".)
 template <int NT>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sWave,
                                                     uint32_t* total) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
+  const uint32_t incl = wave_incl_scan(v);
   if (lane == 63) sWave[wv] = incl;
   __syncthreads();
   uint32_t before = 0, all = 0;

@@ -5,10 +5,11 @@
 //
 // One encode = one stream-ordered pipeline on the context's HIP stream:
 //   front (RGB8 -> ACS/QF/DC/AC)            [jxg_front.hip]
-//   ac_hist + lf_hist (token statistics)     [jxg_entropy.hip]
+//   ac_hist + lf_hist (token statistics)     [jxg_ac_hist.hip, jxg_entropy.hip]
 //   -> D2H histograms; host builds prefix codes, LfGlobal/HfGlobal and the
 //      LF-group stream preludes (a few KB of header bits)
 //   ac_emit or the rANS chain + ans_emit, lf_code (bit emission into scratch)
+//                                 [jxg_ac_emit.hip, jxg_ans.hip, jxg_entropy.hip]
 //   -> D2H section sizes; host writes headers + TOC and the piece list
 //   concat (bit-exact assembly) -> D2H codestream
 // The byte stream equals the CPU oracle's (oracle/encode.c) bit for bit.

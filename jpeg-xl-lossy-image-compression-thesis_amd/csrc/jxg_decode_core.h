@@ -16,11 +16,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define JXG_HD __host__ __device__
-#else
-#define JXG_HD
-#endif
+#include "jxg_acmodel.h"  // JXG_HD; the AC context model
+
 // The includer of the kernel defines JXG_WAVE_SYNC (a workgroup barrier of the
 // one-wave workgroup) before including this header: it orders the lanes' LDS
 // writes of the non-zero map against the next reads.  Nothing on the host.
@@ -195,38 +192,13 @@ JXG_HD inline uint32_t read_ctx(BitReader& br, const SR& S, uint32_t ctx, uint32
   return read_hybrid(br, h, tok);
 }
 
-// raw strategy id -> covered blocks (down | across << 8); 0: not a strategy
-// this encoder writes
-JXG_HD inline uint32_t strategy_shape(uint32_t t) {
-  const uint16_t k[27] = {0x0101, 0x0101, 0x0101, 0x0101, 0x0202, 0x0404, 0x0102, 0x0201, 0,
-                          0,      0x0204, 0x0402, 0x0101, 0x0101, 0,      0,      0,      0,
-                          0x0808, 0x0408, 0x0804, 0x1010, 0x0810, 0x1008, 0x2020, 0x1020, 0x2010};
-  return t < 27 ? k[t] : 0u;
-}
-JXG_HD inline uint32_t strategy_order(uint32_t t) {
-  const uint8_t k[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1,
-                         1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-  return k[t];
-}
-// default block context map [channel (Y, X, B)][order]
-JXG_HD inline uint32_t block_ctx(uint32_t i) {
-  const uint8_t k[39] = {0, 1, 2, 2, 3,  3,  4,  5,  6,  6,  6,  6,  6,
-                         7, 8, 9, 9, 10, 11, 12, 13, 14, 14, 14, 14, 14,
-                         7, 8, 9, 9, 10, 11, 12, 13, 14, 14, 14, 14, 14};
-  return k[i];
-}
-// the zero-density context tables of the format, as arithmetic (both sit on
-// the token chain of the walk: a table load there is a memory latency per token)
-JXG_HD inline uint32_t freq_ctx(uint32_t i) {  // i < 64: 0 0 1 .. 14, pairs 15 .. 22, fours 23 .. 30
-  return i < 2 ? 0u : (i < 16 ? i - 1 : (i < 32 ? 15 + ((i - 16) >> 1) : 23 + ((i - 32) >> 2)));
-}
-JXG_HD inline uint32_t nnz_ctx(uint32_t i) {
-  return i < 2 ? 0u
-               : (i < 3 ? 31u
-                        : (i < 5 ? 62u
-                                 : (i < 9 ? 93u
-                                          : (i < 13 ? 123u : (i < 21 ? 152u : (i < 33 ? 180u : 206u))))));
-}
+// the format's AC context model (jxg_acmodel.h), the expression forms the
+// walk's token chain was tuned with
+using jxg::block_ctx;
+using jxg::freq_ctx;
+using jxg::nnz_ctx;
+using jxg::strategy_order;
+using jxg::strategy_shape;
 
 struct GroupGeom {
   uint32_t bx0, by0, gw, gh, bxs;  // first block, blocks across / down, frame blocks per row
@@ -296,6 +268,8 @@ JXG_HD inline int decode_pass_group(BitReader& br, const SR& S, uint32_t npreset
         else
           pred = (uni(nz_c[(by - 1) * 32 + bx]) + uni(nz_c[by * 32 + bx - 1]) + 1) >> 1;
         const uint32_t bctx = block_ctx((c < 2 ? c ^ 1 : 2) * 13 + ordi);
+        // nz_bucket(pred) in the walk's unsigned form (calling it moves 4
+        // instructions of the kernels; tests/test_ac_model.py pins the two equal)
         const uint32_t pp = pred < 64 ? pred : 64;
         const uint32_t bucket = pp < 8 ? pp : 4 + pp / 2;
         const uint32_t nz = read_ctx(br, S, off + bucket * 15 + bctx, state);

@@ -115,23 +115,7 @@ __device__ __forceinline__ void quant_dc3(const float* dc, const float* dc_mul,
   q[2] = bv >= 0.0f ? (int)(bv + 0.5f) : -(int)(-bv + 0.5f);
 }
 
-// [ext] AC context model tables (libjxl ac_context.h)
-__device__ __constant__ static const uint8_t kStrategyOrder[27] = {
-    0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-__device__ __constant__ static const uint8_t kDefaultCtxMap[39] = {
-    0, 1, 2, 2, 3,  3,  4,  5,  6,  6,  6,  6,  6,  7, 8, 9, 9, 10, 11, 12,
-    13, 14, 14, 14, 14, 14, 7, 8, 9, 9, 10, 11, 12, 13, 14, 14, 14, 14, 14};
-__device__ __constant__ static const uint8_t kFreqCtx[64] = {
-    0,  0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 15, 16, 16, 17, 17,
-    18, 18, 19, 19, 20, 20, 21, 21, 22, 22, 23, 23, 23, 23, 24, 24, 24, 24, 25, 25, 25, 25,
-    26, 26, 26, 26, 27, 27, 27, 27, 28, 28, 28, 28, 29, 29, 29, 29, 30, 30, 30, 30};
-__device__ __constant__ static const uint16_t kNnzCtx[64] = {
-    0,   0,   31,  62,  62,  93,  93,  93,  93,  123, 123, 123, 123, 152, 152, 152,
-    152, 152, 152, 152, 152, 180, 180, 180, 180, 180, 180, 180, 180, 180, 180, 180,
-    180, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206,
-    206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206};
-
-// (the context model's sizes, bclass and ac_cluster: jxg_acmodel.h)
+// (the AC context model -- sizes, context functions, nz_bucket, ac_cluster: jxg_acmodel.h)
 
 __host__ __device__ __forceinline__ uint32_t pack_signed(int32_t v) {
   return v >= 0 ? (uint32_t)v * 2u : (uint32_t)(-(int64_t)v) * 2u - 1u;
@@ -158,11 +142,6 @@ __host__ __device__ __forceinline__ void hybrid420(uint32_t v, uint32_t& tok, ui
 }
 
 // (the strategy ids, the natural order and co_index_rt: jxg_coeff.h)
-
-__device__ __forceinline__ int nz_bucket(int n) {
-  if (n >= 64) n = 64;
-  return n < 8 ? n : 4 + n / 2;
-}
 
 // Lane exchange inside 8-lane groups with DPP (no LDS traffic, no address
 // VGPRs): xor 1 / 2 are quad permutes; xor 4 = quad_perm(3,2,1,0) followed by
@@ -219,6 +198,17 @@ struct BitSink {
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the sum of v over the lanes up to and including this one (the bit
+// placement of ac_emit and ans_emit, the scan of jxg_actask.h)
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d);
+    if (lane >= d) v += t;
+  }
   return v;
 }
 

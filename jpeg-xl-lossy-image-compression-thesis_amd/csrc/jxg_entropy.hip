@@ -1,6 +1,6 @@
 // jxg_entropy.hip -- token statistics and bit emission on gfx950.
 //
-// (pass-group AC kernels: jxg_ac.hip)
+// (pass-group AC kernels: jxg_ac_hist.hip, jxg_ac_emit.hip, jxg_ans.hip)
 // LF groups (modular streams of quantized DC and AC metadata) are processed
 // in chunks of <= 4096 samples of one stream per workgroup, 16 consecutive
 // samples per thread: lf_hist -> (host codes) -> lf_code.
@@ -156,7 +156,11 @@ __global__ __launch_bounds__(256) void lf_hist_kernel(Batch<LfArgs> bt_) {
 }
 
 // workgroup exclusive scan of one value per thread (256 threads); sWave
-// holds the four wave totals afterwards
+// holds the four wave totals afterwards.  (jxg_actask.h block_excl_scan<256>
+// is the same scan with the sum of `before` unrolled; lf_code_kernel compiles
+// to other code with it, and already with wave_incl_scan in the place of the
+// loop below -- DESIGN.md §3.13 "The AC coding stage's units" -- so this
+// form stays.)
 __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* sWave) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t incl = v;

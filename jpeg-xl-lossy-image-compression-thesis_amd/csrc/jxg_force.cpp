@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/jxg.h"
+#include "jxg_acmodel.h"
 
 namespace {
 
@@ -15,20 +16,11 @@ namespace {
 struct Extent {
   uint8_t cy, cx;
 };
+// (the shapes of up to 64 px: what fits one 64x64 tile)
 Extent extent_of(uint8_t id) {
-  switch (id) {
-    case 0: case 1: case 2: case 3: case 12: case 13: return {1, 1};  // the 8x8 class
-    case 6: return {2, 1};
-    case 7: return {1, 2};
-    case 4: return {2, 2};
-    case 10: return {4, 2};
-    case 11: return {2, 4};
-    case 5: return {4, 4};
-    case 19: return {8, 4};
-    case 20: return {4, 8};
-    case 18: return {8, 8};
-    default: return {0, 0};
-  }
+  const uint32_t s = jxg::strategy_shape(id);
+  const uint8_t cy = (uint8_t)(s & 0xFF), cx = (uint8_t)(s >> 8);
+  return cy <= 8 && cx <= 8 ? Extent{cy, cx} : Extent{0, 0};
 }
 
 constexpr uint8_t kConflict = 0xFF;  // claimed by two varblocks (0x80 | 0x7F is no accepted id)

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "jxg_acmodel.h"
+#include "jxg_acrec.h"
 #include "jxg_coeff.h"
 #include "jxg_decode_core.h"
 #include "jxg_shapes.h"
@@ -195,17 +196,14 @@ struct AcArgs {
   const uint64_t* base;  // [ngroups] scratch bit offset (emit pass)
   uint32_t* scratch;     // bit buffer (emit pass, zeroed)
   uint32_t* bits;        // [ngroups] exact bits (emit pass)
-  uint32_t* tokens;      // token records (cluster | tok << 8 | nbits << 14 | bits << 18),
+  uint32_t* tokens;      // token records (jxg_acrec.h ac_record),
                          //   slot i (group glist[i] or g0 + i) at i * kGroupTokStride,
                          //   band j of it at + j * kBandTokStride (hist pass writes them)
   uint32_t* bandtok;     // [ngroups][4] tokens of each 8-block-row band (hist pass)
 };
-// records per pass group: 1024 blocks x 3 channels x <= 64 tokens per slice;
-// per band (8 of the group's 32 block rows): a quarter of that
-constexpr uint64_t kGroupTokStride = 1024ull * 3 * 64;
-constexpr uint64_t kBandTokStride = 256ull * 3 * 64;
+// (kGroupTokStride, kBandTokStride, kAnsMaxChunks: jxg_acrec.h)
 
-// ANS coding of the pass groups' token records (jxg_ac.hip)
+// ANS coding of the pass groups' token records (jxg_ans.hip)
 // (the table blob's layout, kAnsHists / kAnsInvOff / kAnsMapOff / kAnsTabBytes:
 // jxg_acmodel.h)
 struct AnsArgs {
@@ -229,7 +227,6 @@ struct AnsArgs {
   uint32_t* csum;          // [slots][kAnsMaxChunks] emitted bits of every 64-record chunk
   uint32_t max_tokens;     // most tokens of any group (ans_emit's segments per group)
 };
-constexpr uint32_t kAnsMaxChunks = (uint32_t)(kGroupTokStride / 64);
 // rANS chains + bit placement of k frames (same plan); streamed: the frames
 // belong to the streaming pipeline (other frames' kernels share the GPU)
 void launch_ans(const AnsArgs* a, uint32_t k, hipStream_t s, bool streamed);

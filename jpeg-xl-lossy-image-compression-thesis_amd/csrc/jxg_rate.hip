@@ -31,7 +31,6 @@
 
 namespace jxg {
 
-constexpr int kRateTok = 64;  // AC tokens are < 64 (jxg_ac.hip kAcTok)
 #ifndef JXG_RATE_BATCH  // (experiment builds override it)
 #define JXG_RATE_BATCH 8
 #endif
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
   // records of the workgroup's band space (the whole group's with BR = 32)
   constexpr uint32_t kSpace = (uint32_t)(BR == 32 ? kGroupTokStride : kBandTokStride);
   const AcArgs& a = ra.ac;
-  __shared__ uint16_t sCost[kMaxClusters * kRateTok];
+  __shared__ uint16_t sCost[kMaxClusters * kAcTok];
   __shared__ AcLds<BR> L;
   __shared__ uint32_t sTask[3][kBandBlocks];  // tokens per (channel slot Y, X, B; slice task)
   __shared__ uint32_t sBase[kBandBlocks];     // first record of each varblock (first block)
@@ -56,8 +55,8 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
   const int y0 = (int)band * BR;
   if (y0 >= G.gh) return;  // below a partial bottom group: no block, no record
   const int me = threadIdx.x;
-  for (int i = me; i < kMaxClusters * kRateTok; i += kBandBlocks) {
-    const uint32_t clu = (uint32_t)i / kRateTok, tok = (uint32_t)i % kRateTok;
+  for (int i = me; i < kMaxClusters * kAcTok; i += kBandBlocks) {
+    const uint32_t clu = (uint32_t)i / kAcTok, tok = (uint32_t)i % kAcTok;
     uint32_t cost;
     if (ra.ans_tab) {
       const uint32_t h = min((uint32_t)ra.ans_tab[kAnsMapOff + clu], kAnsHists - 1);
@@ -126,9 +125,8 @@ __global__ __launch_bounds__(BR * 32) void rate_kernel(RateArgs ra) {
       for (int u = 0; u < kRateBatch; u++) {
         if (js[u] < 0) break;
         const uint32_t r = r8[u];
-        const uint32_t clu = min(r & 0xFFu, (uint32_t)kMaxClusters - 1);
-        const uint32_t cost =
-            (uint32_t)sCost[clu * kRateTok + ((r >> 8) & 63u)] + ((r >> 14) & 15u) * kRateUnit;
+        const uint32_t clu = min(rec_cluster(r), (uint32_t)kMaxClusters - 1);
+        const uint32_t cost = (uint32_t)sCost[clu * kAcTok + rec_token(r)] + rec_nbits(r) * kRateUnit;
         const uint32_t sum = wave_sum(on8[u] ? cost : 0u);
         const int cell = __builtin_amdgcn_readlane(first, js[u]);
         if (lane == 0 && sum) atomicAdd(&sCell[c][cell], sum);

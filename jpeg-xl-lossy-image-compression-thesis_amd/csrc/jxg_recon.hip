@@ -42,11 +42,23 @@ constexpr int kRP = 64 * kRS;   // floats of one LDS plane
 constexpr int kRB = 512;        // recon_big_kernel threads
 
 // raw strategy id -> blocks down, blocks across, weight kind (0xFF: 8x8 class)
-__constant__ uint8_t c_rc_shape[27][3] = {
+// (the host twin initialises the device table, so that its first two columns
+// can be checked against strategy_shape where they are typed)
+struct RcShapes {
+  uint8_t v[27][3];
+};
+constexpr RcShapes kRcShapes = {{
     {1, 1, 0xFF}, {1, 1, 0xFF}, {1, 1, 0xFF}, {1, 1, 0xFF}, {2, 2, 1},     {4, 4, 3},    {2, 1, 0},
     {1, 2, 0},    {0, 0, 0xFF}, {0, 0, 0xFF}, {4, 2, 2},    {2, 4, 2},     {1, 1, 0xFF}, {1, 1, 0xFF},
     {0, 0, 0xFF}, {0, 0, 0xFF}, {0, 0, 0xFF}, {0, 0, 0xFF}, {8, 8, 5},     {8, 4, 4},    {4, 8, 4},
-    {16, 16, 7},  {16, 8, 6},   {8, 16, 6},   {32, 32, 9},  {32, 16, 8},   {16, 32, 8}};
+    {16, 16, 7},  {16, 8, 6},   {8, 16, 6},   {32, 32, 9},  {32, 16, 8},   {16, 32, 8}}};
+constexpr bool rc_shapes_are_the_models() {
+  for (uint32_t t = 0; t < 27; t++)
+    if ((kRcShapes.v[t][0] | kRcShapes.v[t][1] << 8) != (int)strategy_shape(t)) return false;
+  return true;
+}
+static_assert(rc_shapes_are_the_models(), "c_rc_shape's blocks down / across restate strategy_shape");
+__constant__ RcShapes c_rc_shape = kRcShapes;
 __constant__ int c_rc_koff[10] = {0, 128, 384, 896, 1920, 3968, 8064, 16256, 32640, 65408};
 // raw id of the 8x8 class -> weight table of kRcTabW8 (DCT8, DCT4X4, DCT4X8 /
 // DCT8X4, IDENTITY, DCT2X2)
@@ -109,7 +121,7 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     if (bx < a.bxs && by < a.bys) {
       const int raw = a.acs[(size_t)by * a.bxs + bx];
       if (!(raw & 0x80) && raw < 27) {
-        const int cy = c_rc_shape[raw][0], cx = c_rc_shape[raw][1];
+        const int cy = c_rc_shape.v[raw][0], cx = c_rc_shape.v[raw][1];
         if (raw >= 21) {  // 128 / 256 px: recon_big_kernel
           const uint32_t i = atomicAdd(a.biglist, 1u);
           if (i < a.bigcap) a.biglist[1 + i] = by * a.bxs + bx;
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     if (hb == 0xFF) continue;
     const int t = sType[hb];
     const int hx = hb & 7, hy = hb >> 3;
-    const int cy = c_rc_shape[t][0], cx = c_rc_shape[t][1], kind = c_rc_shape[t][2];
+    const int cy = c_rc_shape.v[t][0], cx = c_rc_shape.v[t][1], kind = c_rc_shape.v[t][2];
     int ky, kx;
     float wx, wy, wb;
     if (kind == 0xFF) {
@@ -180,7 +192,7 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     if (hb == 0xFF) continue;
     const int t = sType[hb];
     const int hx = hb & 7, hy = hb >> 3;
-    const int cy = c_rc_shape[t][0], cx = c_rc_shape[t][1];
+    const int cy = c_rc_shape.v[t][0], cx = c_rc_shape.v[t][1];
     const int ky = (b >> 3) - hy, kx = (b & 7) - hx;
     const float* fy = tab + kRcTabFwd + rc_fwd_off(rc_log2(cy)) + ky * cy;
     const float* fx = tab + kRcTabFwd + rc_fwd_off(rc_log2(cx)) + kx * cx;
@@ -207,7 +219,7 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     if (hb == 0xFF) continue;
     const int t = sType[hb];
     if (t == 1 || t == 2 || t == 3 || t == 12 || t == 13) continue;
-    const int R = 8 * c_rc_shape[t][0];
+    const int R = 8 * c_rc_shape.v[t][0];
     const int y0 = (hb >> 3) * 8;
     const float* m = tab + kRcTabIdct + rc_idct_off(rc_log2(R)) + (y - y0);
     const float* src = sC + c * kRP + y0 * kRS + x;
@@ -324,7 +336,7 @@ __global__ __launch_bounds__(kRT) void recon_tile_kernel(ReconArgs a) {
     if (hb == 0xFF) continue;
     const int t = sType[hb];
     if (t == 1 || t == 2 || t == 3 || t == 12 || t == 13) continue;
-    const int C = 8 * c_rc_shape[t][1];
+    const int C = 8 * c_rc_shape.v[t][1];
     const int x0 = (hb & 7) * 8;
     const float* m = tab + kRcTabIdct + rc_idct_off(rc_log2(C)) + (x - x0);
     const float* src = sT + c * kRP + y * kRS + x0;
@@ -362,7 +374,7 @@ __global__ __launch_bounds__(kRB) void recon_big_kernel(ReconArgs a) {
   const uint32_t bx = gh % a.bxs, by = gh / a.bxs;
   const int t = a.acs[gh];
   if (t < 21 || t > 26) return;
-  const int cy = c_rc_shape[t][0], cx = c_rc_shape[t][1], kind = c_rc_shape[t][2];
+  const int cy = c_rc_shape.v[t][0], cx = c_rc_shape.v[t][1], kind = c_rc_shape.v[t][2];
   if (bx + cx > a.bxs || by + cy > a.bys) return;
   const int R = 8 * cy, C = 8 * cx;
   const int lcx = rc_log2(cx), lC = lcx + 3, lR = rc_log2(R);

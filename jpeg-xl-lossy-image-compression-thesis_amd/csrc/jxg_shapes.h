@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "jxg_acmodel.h"  // strategy_shape
+
 namespace jxg {
 
 // raw id, blocks down / across (log2), cost multiplier.  16 bytes: the kernels
@@ -48,11 +50,14 @@ constexpr bool shape_tables_ok() {
     const int blocks = 1 << (kShapes[si].lcy + kShapes[si].lcx), k = shape_kind(si);
     if (kShapeOff[si] != off || kShapeSlotOff[si] != slot || kShapeSlots[si] != 64 / blocks) return false;
     if (k < 0 || k >= kNumKinds || kKindOff[k + 1] - kKindOff[k] != 64 * blocks) return false;
+    // blocks down | across << 8 of the raw id, as the AC context model has them
+    if (strategy_shape((uint32_t)kShapes[si].type) != (1u << kShapes[si].lcy | 256u << kShapes[si].lcx)) return false;
     off += 64 * blocks;
     slot += 64 / blocks;
   }
   return kShapeOff[kNumShapes] == off && kShapeSlotOff[kNumShapes] == slot;
 }
-static_assert(shape_tables_ok(), "kShapeOff / kShapeSlots / kShapeSlotOff / kKindOff restate kShapes");
+static_assert(shape_tables_ok(),
+              "kShapeOff / kShapeSlots / kShapeSlotOff / kKindOff restate kShapes, kShapes strategy_shape");
 
 }  // namespace jxg

@@ -3,7 +3,7 @@ test_gpu_highrate.py and test_oracle_ubsan.py; not a conftest).
 
 The library accepts 0 < distance <= 25 and computes with max(distance, 1e-6)
 (include/jxg.h JXG_MIN_DISTANCE).  Down there the quantizers clamp at +-32767,
-the token record (csrc/jxg_kernels.h: cluster | tok << 8 | nbits << 14 | bits
+the token record (csrc/jxg_acrec.h: cluster | tok << 8 | nbits << 14 | bits
 << 18) is at the edge of every field (|q| = 32767 -> tok 63, nbits 13), the raw
 quant field is at its ceiling of 256 (stored 255) and the global scale at its
 clamp of 73727 for distance <= 0.79 * 1024 / 73727 = 0.010972.

@@ -1,4 +1,4 @@
-"""The lane-per-chain protocol of the rANS chain kernel (csrc/jxg_ac.hip
+"""The lane-per-chain protocol of the rANS chain kernel (csrc/jxg_ans.hip
 ans_chain) restated in Python and checked against the sequential encoder, in
 the style of test_ans_lane_model.py: a toy rANS step (the kernel's arithmetic
 is checked on the GPU against the oracle); what this pins is which lane codes

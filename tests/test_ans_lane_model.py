@@ -1,4 +1,4 @@
-"""The lane protocol of the rANS chain kernel (csrc/jxg_ac.hip ans_chain)
+"""The lane protocol of the rANS chain kernel (csrc/jxg_ans.hip ans_chain)
 restated over 64 model lanes and checked against a sequential encoder on
 random record streams: the diagonal hand-over by a whole-wave rotation, the
 pre-step state each lane captures, and the final state of a stream (the lane

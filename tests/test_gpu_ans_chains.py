@@ -1,4 +1,4 @@
-"""The rANS chain kernels (csrc/jxg_ac.hip: ans_chain, one lane per chain, codes
+"""The rANS chain kernels (csrc/jxg_ans.hip: ans_chain, one lane per chain, codes
 the streamed frames -- submit / receive; ans_chain_diag, one wave per chain,
 codes a frame encoded by itself -- encode) at the group counts where the
 lane-per-chain mapping changes: exactly one full wave of chains (64 pass

@@ -19,6 +19,10 @@
 #   tools/kernel_isa_diff.sh old/jxg_merge.hip.o build/jxg_merge.hip.o merge_eval_kernel
 #   tools/kernel_isa_diff.sh old/jxg_merge.hip.o build/jxg_merge_write.hip.o merge_resolve_kernel force_list_kernel merge_write_kernel
 #   tools/kernel_isa_diff.sh old/jxg_merge.hip.o build/jxg_vb_list.hip.o vb_list_kernel
+# and jxg_ac.hip into the walk, the prefix-code emitter and the rANS coder:
+#   tools/kernel_isa_diff.sh old/jxg_ac.hip.o build/jxg_ac_hist.hip.o ac_hist_kernelILi32 ac_hist_kernelILi8
+#   tools/kernel_isa_diff.sh old/jxg_ac.hip.o build/jxg_ac_emit.hip.o ac_emit_kernel
+#   tools/kernel_isa_diff.sh old/jxg_ac.hip.o build/jxg_ans.hip.o ans_encode_kernel ans_encode_diag_kernel ans_sums_kernel ans_emit_kernel
 # A template's mangled name changes with its parameter list and namespace
 # (jxg12front_kernelILb1ELb0EEE became jxg9search_tu12front_kernelILb1ELb0ELb0EEE):
 # substrings are matched, first match per object.
@@ -26,7 +30,7 @@
 set -euo pipefail
 LLVM=${LLVM:-/opt/rocm/llvm/bin}
 ARCH=${ARCH:-gfx950}
-[ $# -ge 2 ] || { sed -n 2,25p "$0"; exit 2; }
+[ $# -ge 2 ] || { sed -n 2,29p "$0"; exit 2; }
 old=$1; new=$2; shift 2
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for v in old new; do
@@ -45,6 +49,7 @@ done
 # count file
 mnemonics() {
   awk -v n="$2" '/^[0-9a-f]+ <.*>:/{p=($0 ~ "<" n ">:")} p' "$1" | grep -v '^[0-9a-f]* <' |
+    grep -E '^[[:space:]]+[a-z_][a-z0-9_]*([[:space:]]|$)' |  # instructions only (objdump ends some listings with "..." for elided zeros)
     sed -E 's/^[[:space:]]+//' | awk 'NF{print $1}' |
     awk -v pad="$3" '{l[NR]=$0} END{n=NR; while (n && l[n]=="s_nop") n--;
                      for (i=1;i<=n;i++) print l[i]; print NR-n > pad}'
