@@ -97,16 +97,21 @@ def test_cjxl_flags_override_defaults(jxg_mod, oracle, tmp_path):
 
 
 @pytest.mark.parametrize("distance,effort,proposals", [(1.0, 7, "none"), (2.0, 5, "PF"),
-                                                       (0.5, 7, "F")])
-def test_cli_and_c_abi_give_the_same_bytes(jxg_mod, oracle, tmp_path, distance, effort, proposals):
+                                                       (0.5, 7, "F"), (1.0, 8, "none")])
+def test_cli_and_c_abi_give_the_same_bytes(jxg_mod, oracle, decoder, tmp_path, distance, effort,
+                                           proposals):
     """The two drop-in routes agree: the same PNG through
     `jxg_cjxl IN OUT --distance=D --effort=E [--proposals=..]` and through the
     C ABI (jxg_create with JXG_FLAGS_CJXL_DEFAULTS, jxg_encode_rgb8 -- what
     INTEGRATION.md's Rust execute_cjxl does) give identical bytes, equal to the
-    oracle's encode of cjxl's defaults."""
+    oracle's encode of cjxl's defaults.  The effort-8 case is a
+    frame that chooses 128 px varblocks: the CLI encodes it on a context whose
+    first frame was the warm-up's, and HfGlobal must list exactly the quant
+    tables of the kinds in the strategy map."""
     from jxg.synth import natural_rgb8
+    from test_recon_cases import gradient_rgb8
 
-    img = natural_rgb8(419, 263, 11)
+    img = gradient_rgb8(520, 300, 520 * 7 + 300) if effort == 8 else natural_rgb8(419, 263, 11)
     src = tmp_path / "in.png"
     write_png(str(src), img)
     out = tmp_path / "cli.jxl"
@@ -116,6 +121,11 @@ def test_cli_and_c_abi_give_the_same_bytes(jxg_mod, oracle, tmp_path, distance, 
     with jxg_mod.Encoder(distance=distance, effort=effort, proposals=props,
                          flags=jxg_mod.FLAGS_CJXL_DEFAULTS) as enc:
         lib_bytes = enc.encode(img)
+    ref = oracle.encode(img, distance, effort, props, 1, jxg_mod.ORACLE_FILTERS_CJXL_DEFAULTS)
     assert out.read_bytes() == lib_bytes
-    assert lib_bytes == oracle.encode(img, distance, effort, props, 1,
-                                      jxg_mod.ORACLE_FILTERS_CJXL_DEFAULTS).bytes
+    assert lib_bytes == ref.bytes
+    if effort == 8:
+        big = {int(t) for t in np.unique(ref.acs[(ref.acs & 0x80) == 0]) if t >= 21}
+        assert big, "the frame chooses no 128 / 256 px varblock"
+        kinds = sorted({decoder.SHAPES[t][2] for t in big})
+        assert sorted(decoder.decode(out.read_bytes(), groups=[]).qm_params) == kinds

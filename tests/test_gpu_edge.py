@@ -3,7 +3,8 @@ library must refuse (empty, past the 2^18 side limit, a row stride shorter
 than the row) leave the context usable, and the next frames still equal the
 oracle's bytes -- 1-pixel-wide and 1-pixel-high strips, a frame that is a
 single partial 8x8 block, and sides one past a group / tile boundary at the
-headline preset (cjxl's defaults)."""
+headline preset (cjxl's defaults); and the largest side the library accepts,
+2^18, in either direction."""
 import ctypes
 
 import numpy as np
@@ -57,3 +58,32 @@ def test_edge_sizes_at_cjxl_defaults(jxg_mod, oracle, decoder, w, h):
     assert got == ref.bytes
     dec = decoder.decode(got)
     assert dec.rgb.shape[:2] == (h, w)
+
+
+# the side limit itself: 2^18 in either direction is 1024 pass groups, 128 LF
+# groups and 4096 tiles in one row or column (2 Mpx) -- every grid dimension
+# and 16-bit index at its largest
+LIMIT = 1 << 18
+LIMIT_FRAMES = [(LIMIT, 8, 7), (8, LIMIT, 7), (LIMIT, 1, 7), (1, LIMIT, 7), (LIMIT, 9, 8)]
+
+
+@pytest.mark.parametrize("w,h,effort", LIMIT_FRAMES)
+def test_frames_at_the_side_limit(jxg_mod, oracle, w, h, effort):
+    """cjxl's defaults at d1, effort 7 with both proposals, effort 8 without"""
+    import metrics
+    from jxg.synth import synth_rgb8
+
+    img = synth_rgb8(w, h, 0x4A584C50 + (w & 0xFF) + h % 251)
+    props = 3 if effort == 7 else 0
+    ref = oracle.encode(img, 1.0, effort, props, 1, CJXL)
+    with jxg_mod.Encoder(distance=1.0, effort=effort, proposals=props,
+                         flags=jxg_mod.FLAGS_CJXL_DEFAULTS) as enc:
+        got = enc.encode(img)
+        assert got == ref.bytes
+        info = jxg_mod.stream_info(got)
+        assert (info["xsize"], info["ysize"]) == (w, h)
+        assert info["num_groups"] == 1024 and info["num_lf_groups"] == 128
+        if min(w, h) == 8:
+            rec = enc.reconstruct()
+            assert enc.compare(img, rec)["sse"] == metrics.sse(img, rec)
+            assert np.array_equal(enc.decode(got), rec)
