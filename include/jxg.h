@@ -150,20 +150,31 @@ jxg_status jxg_encode_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsiz
 /* Forced encode: the caller's AC-strategy map instead of the search
  * (DESIGN.md 3.19).  `acs` is [ysize_blocks][xsize_blocks] u8 in the layout of
  * jxg_stats.ac_strategy / jxg_decode_maps: a varblock's first block holds its
- * raw id, every other block it covers 0x80 | id.  Accepted ids: the 8x8 class
- * (0, 1, 2, 3, 12, 13) and the nine merged shapes up to 64 px (4, 5, 6, 7, 10,
- * 11, 18, 19, 20); a merged varblock may sit at any block position inside one
- * 64x64 tile and the frame's blocks (the decoder's tile rule), not only at the
- * multiples of its size the search produces.
+ * raw id, every other block it covers 0x80 | id.  Accepted ids:
+ *   - the 8x8 class (0, 1, 2, 3, 12, 13);
+ *   - the nine merged shapes up to 64 px (4, 5, 6, 7, 10, 11, 18, 19, 20), at
+ *     any block position inside one 64x64 tile and the frame's blocks (the
+ *     decoder's tile rule), not only at the multiples of their size the search
+ *     produces;
+ *   - the six kinds of 128 / 256 px, as (rows, columns) of blocks 21 = 16x16,
+ *     22 = 16x8, 23 = 8x16, 24 = 32x32, 25 = 32x16, 26 = 16x32, on the shape's
+ *     own grid alone: block row a multiple of its blocks down, block column a
+ *     multiple of its blocks across, inside the frame's blocks.  There a
+ *     varblock never crosses a 256x256 pass group.  A decoder reads some other
+ *     placements of these kinds; this encoder has no transform path for them.
  *
  * jxg_check_strategy_map (host only, no context) says whether a map is
- * accepted: JXG_ERR_UNSUPPORTED for a first block's id outside the 15 (AFV,
- * 32X8 / 8X32, the 128 / 256 px kinds); JXG_ERR_INVALID_ARG for a null map, a
- * size jxg_encode_rgb8 refuses, a varblock reaching past the frame's blocks or
- * across a tile border, a covered byte that is not 0x80 | id of the varblock
- * covering it, a covered byte no varblock covers, or overlap.  On refusal
- * *bad_block (may be NULL) is the raster index of the first offending block
- * in raster order.
+ * accepted.  A first block is judged in this order: claimed by another
+ * varblock, id and placement supported, fits the frame (up to 64 px: and the
+ * tile).  JXG_ERR_UNSUPPORTED for a first block's id without a shape here
+ * (AFV 8, 9; 32X8 / 8X32 14 - 17; ids >= 27) and for an id 21 - 26 off its own
+ * grid; JXG_ERR_INVALID_ARG for a null map, a size jxg_encode_rgb8 refuses, a
+ * varblock reaching past the frame's blocks (ids 21 - 26 on their grid
+ * included) or, up to 64 px, across a tile border, a covered byte that is not
+ * 0x80 | id of the varblock covering it, a covered byte no varblock covers, a
+ * first block inside another varblock, or overlap.  On refusal *bad_block
+ * (may be NULL) is the raster index of the first offending block in raster
+ * order.
  *
  * The encode calls validate the map before anything is uploaded or launched;
  * a refused map returns the validator's status with *out = {NULL, 0} and
@@ -175,7 +186,8 @@ jxg_status jxg_encode_rgb8_device(jxg_ctx* ctx, const void* d_rgb, uint32_t xsiz
  * Everything that is not a choice (XYB, Gaborish, DC, chroma from luma, the
  * coder, the filters signalled) is what an effort-7 encode of the context's
  * distance and flags computes; the context's effort and proposals play no
- * part and jxg_stats.homogeneity is NULL.  In every other respect this is
+ * part -- a map with ids 21 - 26 is encoded on a context of any effort -- and
+ * jxg_stats.homogeneity is NULL.  In every other respect this is
  * jxg_encode_rgb8: JXG_FLAG_KEEP_MAPS, jxg_get_stats, jxg_reconstruct_rgb8 and
  * the reports serve it alike; JXG_ERR_INVALID_ARG for null arguments, a stride
  * under 3 * xsize or streamed frames pending.  There is no batch, streaming,

@@ -90,8 +90,10 @@ static jxg_status encode_forced(jxg_ctx* ctx, const void* src, bool on_device, u
   Ctx* c;
   jxg_status st = ctx_enter(ctx, true, &c);
   if (st) return st;
-  if ((st = jxg_check_strategy_map(acs, w, h, nullptr))) return st;
-  return encode_one(c, static_cast<const uint8_t*>(src), on_device, w, h, stride, out, t0, acs, qf);
+  uint32_t big_kinds = 0;  // the map's kinds of 128 / 256 px
+  if ((st = check_strategy_map(acs, w, h, nullptr, &big_kinds))) return st;
+  return encode_one(c, static_cast<const uint8_t*>(src), on_device, w, h, stride, out, t0, acs, qf,
+                    false, big_kinds);
 }
 
 jxg_status jxg_encode_forced_rgb8(jxg_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h,

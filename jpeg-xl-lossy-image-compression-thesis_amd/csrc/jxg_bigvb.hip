@@ -32,6 +32,8 @@
 // varblock per task), big_resolve (one thread per region), big_list (the
 // chosen big varblocks), big_write (transform + quantization + coefficients /
 // non-zero counts / quant field / LLF-derived DC of every covered block).
+// A forced encode runs force_big_list (the big varblocks of the caller's map)
+// in the place of cur / eval / resolve / list, then big_write.
 #include <float.h>
 
 #include "jxg_device.h"
@@ -543,6 +545,44 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(4))) void b
   }
 }
 
+// Forced encode (jxg_encode_forced_rgb8): the second producer
+// of big_write's list, in the place of eval + resolve + big_list.  One
+// workgroup per pass group of the plan; the 16 positions of the group's 64 px
+// grid in raster order, each judged by all lanes alike (the byte read is
+// uniform): a first block of id 21 - 26 in the caller's map (b.m.force,
+// validated on the host: on its own grid, inside the frame, nothing overlaps)
+// is appended to b.work and counted into b.kinds by lane 0, and the lanes
+// share the varblock's bytes into acs -- the front kernel left DCT8 there,
+// force_list_kernel passes these ids by.  At most 16 per group: the list's
+// capacity.  The count word is zeroed by the launch (launch_force_big), not
+// here: a workgroup cannot clear what another may already have added to.
+__global__ __launch_bounds__(64) void force_big_list_kernel(Batch<BigArgs> bt_) {
+  const BigArgs& b = bt_.a[blockIdx.z];
+  const MergeArgs& a = b.m;
+  const uint32_t gi = blockIdx.x;
+  if (gi >= b.ng) return;
+  const uint32_t g = b.glist ? b.glist[gi] : b.g0 + gi;
+  const uint32_t gx0 = (g % b.gxs) * 32, gy0 = (g / b.gxs) * 32;
+  for (uint32_t p = 0; p < 16; p++) {
+    const uint32_t bx = gx0 + (p & 3) * 8, by = gy0 + (p >> 2) * 8;
+    if (bx >= a.bxs || by >= a.bys) continue;
+    const uint32_t gb = by * a.bxs + bx;
+    const uint8_t t = a.force[gb];
+    if (t < 21 || t > 26) continue;
+    int si = 0;
+    for (int i = 0; i < 6; i++) si = kBig[i].type == t ? i : si;
+    const int lcx = kBig[si].lcx, n = 1 << (kBig[si].lcy + lcx);
+    if (threadIdx.x == 0) {
+      b.work[1 + atomicAdd(b.work, 1u)] = gb;
+      atomicAdd(b.kinds + kBig[si].kind, 1u);
+    }
+    for (int i = threadIdx.x; i < n; i += 64) {
+      const uint32_t iy = (uint32_t)(i >> lcx), ix = (uint32_t)(i & ((1 << lcx) - 1));
+      a.acs[(size_t)(by + iy) * a.bxs + bx + ix] = (uint8_t)(i ? 0x80 | t : t);
+    }
+  }
+}
+
 // levels 128 and 256 of k frames (same plan): eval / resolve per level, then
 // the chosen varblocks' write pass
 hipError_t launch_big(const BigArgs* a, uint32_t k, hipStream_t s) {
@@ -559,6 +599,16 @@ hipError_t launch_big(const BigArgs* a, uint32_t k, hipStream_t s) {
   }
   hipLaunchKernelGGL(big_list_kernel, dim3(ng, 1, k), dim3(64), 0, s, bt);
   hipLaunchKernelGGL(big_write_kernel, dim3(min(ng * 16u, a[0].slots), 1, k), dim3(kBT), 0, s, bt);
+  return hipGetLastError();
+}
+// forced encode (one frame): the list from a.m.force, then big_write as above
+hipError_t launch_force_big(const BigArgs& a, hipStream_t s) {
+  if (!a.ng || !a.m.force) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(a.work, 0, sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  const Batch<BigArgs> bt = make_batch(&a, 1);
+  hipLaunchKernelGGL(force_big_list_kernel, dim3(a.ng, 1, 1), dim3(64), 0, s, bt);
+  hipLaunchKernelGGL(big_write_kernel, dim3(min(a.ng * 16u, a.slots), 1, 1), dim3(kBT), 0, s, bt);
   return hipGetLastError();
 }
 

@@ -205,6 +205,9 @@ struct Ctx : EncArenas {
     // coefficients and maps are still in this context's buffers
     bool ok = false;
     uint32_t w = 0, h = 0;
+    // ... and may hold varblocks of 128 / 256 px (Job::big: an effort >= 8
+    // search, or a forced map with a big kind on a context of any effort)
+    bool has_big = false;
   } rc;
   // rate report (jxg_rate_report, a sweep's lane; jxg_rate.cpp): the symbol
   // cost table (uploaded once), the 27 x 6 table, the device map of the host
@@ -347,6 +350,9 @@ struct Job {
   // job runs as effort 7 without proposals, never in a batch
   const uint8_t* d_force = nullptr;
   const uint8_t* d_force_qf = nullptr;
+  // ... and whether the map holds a kind of 128 / 256 px (the validator's mask):
+  // the job then runs force_big_list + big_write behind the 64 px write pass
+  bool force_big = false;
   // traced encode (jxg_encode_traced_rgb8): a search job whose front kernel,
   // merge stage and 128 / 256 px levels keep every estimate (c->tr); never in
   // a batch
@@ -363,7 +369,7 @@ struct Job {
   AqArgs qa{};
   MergeArgs ma{};
   BigArgs ba{};
-  bool big = false;  // merge levels 128 / 256 px (effort >= 8)
+  bool big = false;  // varblocks of 128 / 256 px: the search's levels (effort >= 8) or a forced map's
   VbArgs va{};
   AnsArgs na{};
   bool aq = false;  // masking quant field (aq_kernel before the front kernel)
@@ -428,11 +434,16 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out, Clock::time_p
 // jxg_reconstruct_rgb8 may read afterwards (src: host memory, or device memory
 // ordered after the caller's input stream)
 // force_acs: a forced encode -- the caller's strategy map (host memory,
-// validated by jxg_check_strategy_map) and its quant field or null
+// validated by check_strategy_map) and its quant field or null; force_big: the
+// validator's mask of the big kinds the map holds
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                       size_t stride, jxg_buffer* out, Clock::time_point t_call,
                       const uint8_t* force_acs = nullptr, const uint8_t* force_qf = nullptr,
-                      bool trace = false);
+                      bool trace = false, uint32_t force_big = 0);
+// jxg_force.cpp (host only): jxg_check_strategy_map, and in *big_kinds (may be
+// null) bit k for every big kind k (big_list_kernel's numbering) an accepted map holds
+jxg_status check_strategy_map(const uint8_t* acs, uint32_t xsize, uint32_t ysize,
+                              uint32_t* bad_block, uint32_t* big_kinds);
 jxg_status warmup(Ctx* c, uint32_t w, uint32_t h);
 
 // ---- jxg_pipe.cpp: the streaming pipeline ----
@@ -554,8 +565,12 @@ struct ReconSse {
 };
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, const ReconMaps& M, uint8_t* d_rgb,
                               size_t stride, const ReconSse* q = nullptr);
-// the frame constants of a w x h frame encoded with parameters P
+// the frame constants of a w x h frame encoded with parameters P (a sweep's
+// point: big varblocks are possible from effort 8 on)
 ReconFrame recon_frame_of_encode(uint32_t w, uint32_t h, const jxg_params& P);
+// ... of the last one-at-a-time encode of c (rc.w x rc.h; rc.has_big, not the
+// effort, says whether it may hold big varblocks: a forced map may)
+ReconFrame recon_frame_of_last(const Ctx* c);
 // the last one-at-a-time encode's decoded image, into device / host memory
 jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_device);
 

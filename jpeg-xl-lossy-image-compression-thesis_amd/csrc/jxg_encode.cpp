@@ -315,8 +315,10 @@ jxg_status build_front(Ctx* c, Job& J) {
     ma.work = c->mwork.p;
     ma.nwrite = 256 * 3 * 4;  // CUs x resident workgroups (3) x 4 rounds
   }
-  // effort >= 8: the 128 / 256 px levels over the plan's pass groups
-  J.big = J.max_s && P.effort >= 8 && !J.d_force;
+  // the 128 / 256 px levels over the plan's pass groups: the search's from
+  // effort 8 on; a forced job's when its map holds a big kind, whatever the
+  // context's effort (the tables and buffers below grow on demand)
+  J.big = J.max_s && (J.d_force ? J.force_big : P.effort >= 8);
   if (J.big) {
     if (!c->big_ready) {
       static const BigTables bt = build_big_tables();
@@ -457,7 +459,9 @@ jxg_status launch_transform(Ctx* const* cs, Job* const* js, uint32_t k) {
       JXG_HIP(launch_force_merge(J.ma, s));
     else
       JXG_HIP(launch_merge(ma.data(), k, s));
-    if (J.big) {  // levels 128 / 256 px (effort >= 8)
+    if (J.big && J.d_force) {  // the map's big varblocks: listed, then big_write
+      JXG_HIP(launch_force_big(J.ba, s));
+    } else if (J.big) {  // levels 128 / 256 px (effort >= 8)
       const auto ba = gather<BigArgs>(js, k, [](Job& j) { return j.ba; });
       JXG_HIP(launch_big(ba.data(), k, s));
       // test hook: JXG_DEBUG_BIGCOST=path writes frame 0's candidate estimates
@@ -964,7 +968,8 @@ jxg_status enc_finish(Ctx* c, Job& J, bool split, jxg_buffer* out,
 
 static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32_t h,
                                 size_t stride, jxg_buffer* out, Clock::time_point t_call,
-                                const uint8_t* force_acs, const uint8_t* force_qf, bool trace) {
+                                const uint8_t* force_acs, const uint8_t* force_qf, bool trace,
+                                uint32_t force_big) {
   // streamed frames in flight use this context as a lane (and its helper
   // threads its host state): one-at-a-time calls wait until they are received
   if (pipe_busy(c)) return JXG_ERR_INVALID_ARG;
@@ -974,6 +979,7 @@ static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32
     JXG_HIP(c->force_acs.ensure(nb));
     JXG_HIP(hipMemcpyAsync(c->force_acs.p, force_acs, nb, hipMemcpyHostToDevice, c->stream));
     J.d_force = c->force_acs.p;
+    J.force_big = force_big != 0;
     if (force_qf) {
       JXG_HIP(c->force_qf.ensure(nb));
       JXG_HIP(hipMemcpyAsync(c->force_qf.p, force_qf, nb, hipMemcpyHostToDevice, c->stream));
@@ -990,12 +996,14 @@ static jxg_status encode_device(Ctx* c, const uint8_t* d_rgb, uint32_t w, uint32
   // frames are one section; several contexts keep the one-stream assembly)
   const bool split = J.f.ngroups > 1 && lone_context();
   if ((st = enc_codes(c, J, !split))) return st;
+  c->rc.has_big = J.big;
   return enc_finish(c, J, split, out, t_call);
 }
 
 jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, uint32_t h,
                       size_t stride, jxg_buffer* out, Clock::time_point t_call,
-                      const uint8_t* force_acs, const uint8_t* force_qf, bool trace) {
+                      const uint8_t* force_acs, const uint8_t* force_qf, bool trace,
+                      uint32_t force_big) {
   c->rc.ok = false;
   c->tr.have = false;
   if (on_device) {
@@ -1009,7 +1017,7 @@ jxg_status encode_one(Ctx* c, const uint8_t* src, bool on_device, uint32_t w, ui
     src = c->rgb.p;
   }
   const jxg_status st =
-      encode_device(c, src, w, h, stride, out, t_call, force_acs, force_qf, trace);
+      encode_device(c, src, w, h, stride, out, t_call, force_acs, force_qf, trace, force_big);
   if (!st) {
     c->rc.ok = true;
     c->rc.w = w;

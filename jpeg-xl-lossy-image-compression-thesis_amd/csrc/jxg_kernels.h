@@ -139,6 +139,9 @@ struct BigArgs {
   int trace;               // traced encode: big_eval evaluates every candidate in full (no +inf)
 };
 hipError_t launch_big(const BigArgs* a, uint32_t k, hipStream_t s);
+// forced encode (one frame): force_big_list_kernel's list of the big first
+// blocks of a.m.force, then big_write (no eval, no resolve)
+hipError_t launch_force_big(const BigArgs& a, hipStream_t s);
 // search trace (jxg_trace.hip), behind a traced encode's merge
 // stage.  The planes are over the block grid, nb = bxs * bys.
 constexpr uint32_t kTraceSummaryWords = 2 + 36 + 6 + 6 + 48 + 6;  // jxg_trace_summary as u32 words

@@ -1,7 +1,7 @@
 // jxg_reconstruct.cpp -- decode-side reconstruction (jxg_recon.hip, DESIGN.md
 // §3.11).  The decoded image of the last one-at-a-time encode, from the
 // context's coefficient and map buffers (read only): tile transform kernel
-// (+ the 128 / 256 px varblocks at effort >= 8), Gaborish and EPF passes as
+// (+ the 128 / 256 px varblocks where the encode may hold them), Gaborish and EPF passes as
 // the frame header signals them; the last kernel of the chain writes RGB8.
 // The decoder (jxg_decode_dev.cpp) runs the same chain on what it parsed.
 #include <cmath>
@@ -14,6 +14,11 @@ namespace jxg {
 ReconFrame recon_frame_of_encode(uint32_t w, uint32_t h, const jxg_params& P) {
   const Frame f = make_frame(w, h, P.distance);
   return ReconFrame{w, h, f.G, f.qdc, lf_code(P.flags, P.distance), 1.0f, 1.0f, P.effort >= 8};
+}
+ReconFrame recon_frame_of_last(const Ctx* c) {
+  ReconFrame R = recon_frame_of_encode(c->rc.w, c->rc.h, c->params);
+  R.maybe_big = c->rc.has_big;
+  return R;
 }
 
 jxg_status reconstruct_device(Ctx* c, const ReconFrame& R, uint8_t* d_rgb, size_t stride) {
@@ -153,13 +158,11 @@ jxg_status reconstruct_last(Ctx* c, uint8_t* rgb, size_t row_stride, bool on_dev
   if (on_device) {
     const jxg_status st = order_input(c, c);  // the caller's earlier use of rgb
     if (st) return st;
-    return reconstruct_device(c, recon_frame_of_encode(c->rc.w, c->rc.h, c->params), rgb,
-                              row_stride);
+    return reconstruct_device(c, recon_frame_of_last(c), rgb, row_stride);
   }
   const size_t row = (size_t)c->rc.w * 3;
   JXG_HIP(c->rc.rgb.ensure(row * c->rc.h));
-  const jxg_status st =
-      reconstruct_device(c, recon_frame_of_encode(c->rc.w, c->rc.h, c->params), c->rc.rgb.p, row);
+  const jxg_status st = reconstruct_device(c, recon_frame_of_last(c), c->rc.rgb.p, row);
   if (st) return st;
   JXG_HIP(hipMemcpy2DAsync(rgb, row_stride, c->rc.rgb.p, row, row, c->rc.h,
                            hipMemcpyDeviceToHost, c->stream));
@@ -198,7 +201,7 @@ jxg_status block_sse_enqueue(Ctx* c, const uint8_t* orig, size_t orig_stride, bo
   JXG_HIP(c->q.bsse.ensure(nb));
   JXG_HIP(hipMemsetAsync(c->q.sse.p, 0, sizeof(uint64_t), s));
   const ReconSse e{d_orig, so, c->q.sse.p, false, c->q.bsse.p};
-  return reconstruct_device(c, recon_frame_of_encode(w, h, c->params),
+  return reconstruct_device(c, recon_frame_of_last(c),
                             ReconMaps{c->acs.p, c->qf.p, c->dc.p, c->ac.p, c->cmap.p}, nullptr, so,
                             &e);
 }

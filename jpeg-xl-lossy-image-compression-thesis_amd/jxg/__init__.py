@@ -471,7 +471,9 @@ class Encoder:
         map instead of the search (jxg_encode_forced_rgb8).  `strategy` is uint8
         (ysize_blocks, xsize_blocks) in the layout of ``stats()["acs"]`` (see
         :func:`make_strategy_map`), `quant_field` (optional) the same shape,
-        raw - 1 per block as ``stats()["qf"]``.  A map the validator refuses
+        raw - 1 per block as ``stats()["qf"]``.  The ids of FORCED_SHAPES are
+        taken, those of 128 / 256 px (21 - 26) on their own grid and on a context
+        of any effort.  A map the validator refuses
         raises JxgError and leaves the context as it was (:func:`check_strategy_map`
         names the block)."""
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
@@ -1229,7 +1231,10 @@ def ab_report_device(enc_a: Encoder, enc_b: Encoder, ptr: int, row_stride: int |
 # blocks across)
 FORCED_SHAPES = {0: (1, 1), 1: (1, 1), 2: (1, 1), 3: (1, 1), 12: (1, 1), 13: (1, 1),
                  6: (2, 1), 7: (1, 2), 4: (2, 2), 10: (4, 2), 11: (2, 4), 5: (4, 4),
-                 19: (8, 4), 20: (4, 8), 18: (8, 8)}
+                 19: (8, 4), 20: (4, 8), 18: (8, 8),
+                 # the kinds of 128 / 256 px: accepted on their own grid alone (block row a
+                 # multiple of the blocks down, block column of the blocks across)
+                 22: (16, 8), 23: (8, 16), 21: (16, 16), 25: (32, 16), 26: (16, 32), 24: (32, 32)}
 
 
 def check_strategy_map(strategy: np.ndarray, xsize: int, ysize: int):
@@ -1252,8 +1257,10 @@ def make_strategy_map(bys: int, bxs: int, varblocks=(), fill: int = 0) -> np.nda
     (id, block row, block column) of `varblocks` gets its first block's id and
     0x80 | id on the other blocks it covers, every block left over is the
     8x8-class id `fill`.  Raises ValueError for an id outside FORCED_SHAPES, a
-    varblock reaching past the map, or overlap (the tile rule is
-    :func:`check_strategy_map`'s to judge)."""
+    varblock reaching past the map, or overlap (the tile rule of the shapes up
+    to 64 px and the own-grid rule of ids 21 - 26 are
+    :func:`check_strategy_map`'s to judge: a big id placed off its grid is made
+    here and refused there)."""
     if fill not in FORCED_SHAPES or FORCED_SHAPES[fill] != (1, 1):
         raise ValueError("fill must be an 8x8-class id, got %r" % (fill,))
     acs = np.full((bys, bxs), fill, np.uint8)
