@@ -12,11 +12,9 @@
 // exit 0 only if every file was written.
 //
 // .ppm writes a binary P6, .png an 8-bit RGB PNG (filter type 0, zlib level 1;
-// jxg_cjxl's own PNG reader reads it back).  Exit 0 on success; on failure
+// csrc/jxg_cli_io.h has the writer beside the reader jxg_cjxl uses).  Exit 0 on success; on failure
 // exit 1 with one line on stderr: jxg_status_str of the status, or the I/O
 // error.
-#include <zlib.h>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,62 +22,11 @@
 #include <vector>
 
 #include "../../include/jxg.h"
+#include "jxg_cli_io.h"
 
 namespace {
 
-void put_be32(std::vector<uint8_t>& o, uint32_t v) {
-  for (int s = 24; s >= 0; s -= 8) o.push_back((uint8_t)(v >> s));
-}
-
-void put_chunk(std::vector<uint8_t>& o, const char* type, const uint8_t* body, size_t len) {
-  put_be32(o, (uint32_t)len);
-  const size_t at = o.size();
-  o.insert(o.end(), type, type + 4);
-  o.insert(o.end(), body, body + len);
-  put_be32(o, (uint32_t)crc32(0L, o.data() + at, (uInt)(4 + len)));
-}
-
-bool encode_png(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, std::vector<uint8_t>& out) {
-  static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
-  out.assign(sig, sig + 8);
-  std::vector<uint8_t> ihdr;
-  put_be32(ihdr, w);
-  put_be32(ihdr, h);
-  const uint8_t tail[5] = {8, 2, 0, 0, 0};  // 8-bit RGB, deflate, adaptive filtering, no interlace
-  ihdr.insert(ihdr.end(), tail, tail + 5);
-  put_chunk(out, "IHDR", ihdr.data(), ihdr.size());
-  const size_t row = (size_t)w * 3;
-  std::vector<uint8_t> raw((row + 1) * h);
-  for (uint32_t y = 0; y < h; y++) {
-    raw[(row + 1) * y] = 0;  // filter type None
-    std::memcpy(&raw[(row + 1) * y + 1], &rgb[row * y], row);
-  }
-  z_stream zs{};
-  if (deflateInit(&zs, 1) != Z_OK) return false;
-  std::vector<uint8_t> buf((size_t)1 << 20);
-  zs.next_in = raw.data();
-  size_t left = raw.size();
-  int zr = Z_OK;
-  while (zr != Z_STREAM_END) {
-    const size_t piece = left < ((size_t)1 << 30) ? left : ((size_t)1 << 30);
-    zs.avail_in = (uInt)piece;
-    left -= piece;
-    do {
-      zs.next_out = buf.data();
-      zs.avail_out = (uInt)buf.size();
-      zr = deflate(&zs, left ? Z_NO_FLUSH : Z_FINISH);
-      if (zr == Z_STREAM_ERROR) {
-        deflateEnd(&zs);
-        return false;
-      }
-      const size_t n = buf.size() - zs.avail_out;
-      if (n) put_chunk(out, "IDAT", buf.data(), n);
-    } while (zs.avail_out == 0 && zr != Z_STREAM_END);
-  }
-  deflateEnd(&zs);
-  put_chunk(out, "IEND", nullptr, 0);
-  return true;
-}
+using namespace jxg_cli;
 
 bool ends_with(const std::string& s, const char* suffix) {
   const size_t n = std::strlen(suffix);
@@ -92,33 +39,14 @@ bool ends_with(const std::string& s, const char* suffix) {
   return true;
 }
 
-bool read_file(const char* path, std::vector<uint8_t>& data) {
-  FILE* f = std::fopen(path, "rb");
-  if (!f) return false;
-  uint8_t buf[1 << 16];
-  size_t n;
-  while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) data.insert(data.end(), buf, buf + n);
-  std::fclose(f);
-  return true;
-}
-
 // one line on stderr and false when the image cannot be written
 bool write_image(const char* path, bool png, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h) {
   std::vector<uint8_t> file;
-  if (png) {
-    if (!encode_png(rgb, w, h, file)) {
-      std::fprintf(stderr, "PNG deflate failed\n");
-      return false;
-    }
-  } else {
-    char head[64];
-    const int n = std::snprintf(head, sizeof(head), "P6\n%u %u\n255\n", w, h);
-    file.assign(head, head + n);
-    file.insert(file.end(), rgb.begin(), rgb.end());
+  if (png && !encode_png(rgb, w, h, file)) {
+    std::fprintf(stderr, "PNG deflate failed\n");
+    return false;
   }
-  FILE* f = std::fopen(path, "wb");
-  const bool wr = f && std::fwrite(file.data(), 1, file.size(), f) == file.size();
-  if ((f && std::fclose(f) != 0) || !wr) {
+  if (!(png ? write_file(path, file.data(), file.size()) : write_ppm(path, rgb.data(), w, h))) {
     std::fprintf(stderr, "cannot write %s\n", path);
     return false;
   }
@@ -140,22 +68,20 @@ jxg_ctx* create_ctx(int device) {
   return ctx;
 }
 
-// --batch=LIST: every IN<TAB>OUT line of the list through one context and one
-// jxg_decode_batch_rgb8 call; a failed file is one stderr line, the others are
-// still written.  0 only if every file was written.
-int run_batch(const char* list_path, int device) {
+struct Item {  // one IN<TAB>OUT line of a batch list
+  std::string in, out;
+  bool png = false, ok = false;
+  std::vector<uint8_t> data, rgb;
+  jxg_stream_info info{};
+};
+
+// the list's lines; one line on stderr and false for a list that cannot be run
+bool read_batch_list(const char* list_path, std::vector<Item>& items) {
   std::vector<uint8_t> list;
   if (!read_file(list_path, list)) {
     std::fprintf(stderr, "cannot read %s\n", list_path);
-    return 1;
+    return false;
   }
-  struct Item {
-    std::string in, out;
-    bool png = false, ok = false;
-    std::vector<uint8_t> data, rgb;
-    jxg_stream_info info{};
-  };
-  std::vector<Item> items;
   const std::string text(list.begin(), list.end());
   for (size_t at = 0; at < text.size();) {
     size_t nl = text.find('\n', at);
@@ -167,17 +93,23 @@ int run_batch(const char* list_path, int device) {
     const size_t tab = line.find('\t');
     if (tab == std::string::npos || tab == 0 || tab + 1 == line.size()) {
       std::fprintf(stderr, "%s: a line is not IN<TAB>OUT\n", list_path);
-      return 1;
+      return false;
     }
     Item it;
     it.in = line.substr(0, tab);
     it.out = line.substr(tab + 1);
     items.push_back(std::move(it));
   }
-  if (items.empty()) {
-    std::fprintf(stderr, "%s: no files listed\n", list_path);
-    return 1;
-  }
+  if (items.empty()) std::fprintf(stderr, "%s: no files listed\n", list_path);
+  return !items.empty();
+}
+
+// --batch=LIST: every IN<TAB>OUT line of the list through one context and one
+// jxg_decode_batch_rgb8 call; a failed file is one stderr line, the others are
+// still written.  0 only if every file was written.
+int run_batch(const char* list_path, int device) {
+  std::vector<Item> items;
+  if (!read_batch_list(list_path, items)) return 1;
   // the files the call can take: readable, a codestream, a known output type
   std::vector<Item*> sent;
   for (Item& it : items) {

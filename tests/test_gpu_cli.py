@@ -129,3 +129,26 @@ def test_cli_and_c_abi_give_the_same_bytes(jxg_mod, oracle, decoder, tmp_path, d
         assert big, "the frame chooses no 128 / 256 px varblock"
         kinds = sorted({decoder.SHAPES[t][2] for t in big})
         assert sorted(decoder.decode(out.read_bytes(), groups=[]).qm_params) == kinds
+
+
+def test_cjxl_failures_after_the_context_exists(jxg_mod, tmp_path):
+    """Exit status exactly 1 and one message on the failing paths that hold
+    something: the reader refuses the input while the second thread is making
+    the context; the output cannot be written after the encode; the A/B
+    report cannot be written while its base context exists."""
+    from jxg.synth import synth_rgb8
+
+    src = tmp_path / "in.png"
+    write_png(str(src), synth_rgb8(64, 64, 0x4A584C0A))
+    cut = tmp_path / "cut.png"
+    cut.write_bytes(src.read_bytes()[:-40])  # the IDAT chunk runs past the end of the file
+    missing = tmp_path / "no-such-directory"
+    out = tmp_path / "out.jxl"
+    cases = [([str(cut), str(out)], "%s: truncated PNG\n" % cut),
+             ([str(src), str(missing / "out.jxl")], "cannot write %s\n" % (missing / "out.jxl")),
+             ([str(src), str(out), "--jxg_ab=%s" % (missing / "ab.csv")],
+              "cannot write %s\n" % (missing / "ab.csv"))]
+    for args, message in cases:
+        p = subprocess.run([jxg_mod.CLI_PATH] + args, capture_output=True, text=True)
+        assert p.returncode == 1, (args, p.returncode, p.stderr)
+        assert p.stderr == message and p.stdout == ""

@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "jpeg-xl-lossy-image-compression-thesis_amd", "csrc")
 INVALID_ARG = -1
 
 
@@ -55,12 +54,11 @@ def test_the_header_describes_the_getter():
 
 
 def _cli_header():
-    src = open(os.path.join(CSRC, "jxg_cjxl.cpp")).read()
-    body = src[src.index("bool write_trace_rows("):]
-    body = body[:body.index("if (!f) return false;")]
-    text = "".join(re.findall(r'"((?:[^"\\]|\\.)*)"', body))
-    assert text.endswith("\\n")
-    return text[:-2].split(",")
+    """the header line the compiled writer (csrc/jxg_cli_csv.h) puts into a new file"""
+    from test_cli_csv import cli_csv_files
+
+    text = cli_csv_files()["trace"][0].decode().split("\n", 1)[0]
+    return text.split(",")
 
 
 def test_the_harness_header_is_the_command_lines():
